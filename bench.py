@@ -20,7 +20,13 @@ Multi-GPU (one process per GPU, index replicated, no collective on the data path
       against its own single-GPU pass over it.  --slice K/N (one GPU): score only the shard rank K of N would get.
   --scaling weak: every rank scores its own full-size copy of the workload (different seeds).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--scaling strong|weak]
+A plain run sets up, warms up, times the steps and prints the line (its `roofline` read back from profiles/ where that holds the
+configuration's bytes).  --full adds everything else: the CPU baseline and the whole-workload parity against the oracle, the live
+rocprofv3 --pmc passes and the GPU algorithm's own byte counts, the sustained / concurrent / host-to-host figures and, with N > 1,
+the check of the gathered records against a single-GPU pass (--no-cpu-baseline, --no-traffic, --no-extras leave parts of it out).
+--dump-outputs DIR writes the records of the last timed step as DIR/<name>.npy (dump_outputs).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--scaling strong|weak] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -84,6 +90,38 @@ def same_psms(fa, ca, fb, cb):
     return fa[valid].tobytes() == fb[valid].tobytes()
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> array; one row per spectrum or PSM along axis 0, the same number of rows in each) as
+    path/<name>.npy — float32 arrays as they are, every other type as float64 (exact for the integer fields).  When the rows
+    would take more than DUMP_BYTES, a fixed seeded sample of them, in order; row_index.npy holds the rows written."""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: a if a.dtype == np.float32 else a.astype(np.float64) for k, a in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = 8 + sum(a.itemsize * (a.size // max(n, 1)) for a in arrays.values())
+    m = min(n, (DUMP_BYTES - 256 * (len(arrays) + 1)) // row_bytes)  # (each .npy file has a header of 128 bytes)
+    rows = np.arange(n) if m == n else np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+    if m < n:
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    arrays["row_index"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
+def psm_arrays(feats, counts):
+    """The PSM records a caller of the search path receives, as dump_outputs' arrays: one [spectra, report_psms] array per Feature
+    field and the counts.  Slots beyond a spectrum's count are no part of the result (the device leaves them untouched): 0 here."""
+    import numpy as np
+    valid = np.arange(feats.shape[1])[None, :] < counts[:, None]
+    out = {k: np.where(valid, feats[k], 0).astype(feats.dtype[k]) for k in feats.dtype.names if k != "pad"}
+    out["counts"] = counts
+    return out
+
+
 def rescore_bench(args):
     """Secondary measurement: the post-search rescoring (mass-error KDE, LDA, posterior-error KDE, q-values, picked peptide /
     protein FDR) over one synthetic Feature table resident on the host, single GPU.  A "step" is one complete rescoring."""
@@ -106,6 +144,9 @@ def rescore_bench(args):
         wall.append((time.perf_counter() - t0) * 1e3)
         dev.append(res.device_ms)
     ms = float(np.mean(wall))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: getattr(res, k) for k in ("discriminant_score", "posterior_error", "spectrum_q",
+                                                                      "peptide_q", "protein_q", "order")})
     # the Gaussian-kernel sums dominate: (mass bins + 1000 + 1000 + 1000) bins x samples evaluations of exp()
     kde_evals = 100 * n + 1000 * n + 1000 * npk + 1000 * npr
     cpu = None
@@ -486,7 +527,14 @@ def main():
     ap.add_argument("--rescore-psms", type=int, default=0,
                     help="measure the post-search rescoring (sage_hip_rescore, SURVEY 8f rank 4) on this many synthetic PSMs "
                          "instead of the search path; not the headline metric")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: CPU baseline and parity against the oracle, rocprofv3 --pmc passes, GPU algorithm "
+                         "bytes, sustained / concurrent / host-to-host figures, the N > 1 check against a single-GPU pass")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the records the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_traffic = args.no_extras = True
     if args.rescore_psms:
         return rescore_bench(args)
 
@@ -522,12 +570,12 @@ def main():
         # Every rank generates ITS shard only: spectra [total r / N, total (r + 1) / N) of the run (whole chunks of SPECTRA_CHUNK
         # spectra except at the two ends; chunk c depends on (seed, c) only).  The synthetic run is shuffled, so
         # equal counts are equal work to ~0.5 % (sharding.plan_shards with sharding.estimate_work's weights is what a real,
-        # retention-time-ordered run needs: sage_amd/cli.py).  Rank 0 generates the whole run AFTER the timed region, for the
-        # check of the gathered result against a single-GPU pass.
+        # retention-time-ordered run needs: sage_amd/cli.py).  With --full, rank 0 generates the whole run AFTER the timed region,
+        # for the check of the gathered result against a single-GPU pass.
         batch, gidx = generate_workload(cfg, host, total, seed_shift, gen_workers, span=(total * rank // world, total * (rank + 1) // world))
         shards, lo, hi = None, None, None  # (positions in the whole run: known after the ranks have exchanged their counts)
         whole_run = None
-        if rank == 0:
+        if rank == 0 and args.full:
             import multiprocessing as mp
             ctx = mp.get_context("fork")
             whole_conn, child_conn = ctx.Pipe()
@@ -697,9 +745,11 @@ def main():
 
     # how many ranks took part, as counted by the exchange itself (every rank reads every rank's file): in the line as n_ranks_seen
     ranks_seen = len(xchg.all_gather(int(batch.n), "alive")) if xchg is not None else 1
-    # ---- strong scaling: ordered gather of the ranks' records, checked against rank 0's own pass over everything ----
+    # ---- strong scaling: ordered gather of the ranks' records (--dump-outputs), with --full checked against rank 0's own pass over
+    #      everything ----
     sharding = None
-    if world > 1 and args.scaling == "strong":
+    gathered = None
+    if world > 1 and args.scaling == "strong" and (args.full or args.dump_outputs):
         from sage_amd.sharding import gather_features, gather_features_by_index
         t0 = time.perf_counter()
         sizes = xchg.all_gather(int(batch.n), "sizes")
@@ -712,7 +762,8 @@ def main():
             shards = [(int(sum(sizes[:r])), int(sum(sizes[:r + 1]))) for r in range(world)]
             gf, gc = gather_features(feats, counts, lo, exchange=xchg)  # host-side, input order, spec_index rebased
         t_gather = time.perf_counter() - t0
-        if rank == 0:
+        gathered = gf, gc
+        if rank == 0 and args.full:
             whole_conn.send("go")
             msg = whole_conn.recv()
             whole_run.join(timeout=60)
@@ -731,6 +782,8 @@ def main():
                 raise SystemExit(f"bench.py: the gathered {world}-GPU result differs from the single-GPU result")
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, psm_arrays(*(gathered or (feats, counts))))
         n_psm = int(counts.sum())
         extras = {}
         link = None

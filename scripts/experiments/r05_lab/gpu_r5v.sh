@@ -2,7 +2,7 @@
 # round 5, call v: PMC traffic of a rank's shard of an 8-GPU run, cut by mass blocks against cut by input position (same spectrum counts)
 OUT=gpurun_out/r5v; mkdir -p $OUT; export TMPDIR=/tmp
 for BY in mass input; do
-  timeout 900 python bench.py --config C3 --slice 3/8 --shard-by $BY --steps 40 --warmup 5 --no-cpu-baseline --no-extras --traffic-timeout 400 > $OUT/slice_$BY.json 2> $OUT/slice_$BY.err; echo "rc=$?"
+  timeout 900 python bench.py --full --config C3 --slice 3/8 --shard-by $BY --steps 40 --warmup 5 --no-cpu-baseline --no-extras --traffic-timeout 400 > $OUT/slice_$BY.json 2> $OUT/slice_$BY.err; echo "rc=$?"
   python - <<PY
 import json
 j = json.loads([l for l in open("$OUT/slice_$BY.json") if l.startswith("{")][-1])

@@ -3,7 +3,7 @@
 # scripts/gpu_r6_evidence.sh for C3 only (the round's GPU budget ended here: the other configurations' lines, the SQ counters and
 # the phase clocks in profiles/ are of the pass one commit earlier, without the early requests)
 TAG=r06; C=C3; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-( time timeout 100 python bench.py --config $C ) > $OUT/${TAG}_${C}_bench.json.new 2> $OUT/bench_$C.err; rc=$?; echo "bench $C rc=$rc"; tail -4 $OUT/bench_$C.err | grep real
+( time timeout 100 python bench.py --full --config $C ) > $OUT/${TAG}_${C}_bench.json.new 2> $OUT/bench_$C.err; rc=$?; echo "bench $C rc=$rc"; tail -4 $OUT/bench_$C.err | grep real
 if [ $rc -eq 0 ] && grep -q '^{' $OUT/${TAG}_${C}_bench.json.new; then mv $OUT/${TAG}_${C}_bench.json.new $OUT/${TAG}_${C}_bench.json; else exit 1; fi
 timeout 60 rocprofv3 --kernel-trace --stats -d $OUT/trace_$C -o t -- python bench.py --config $C --steps 5 --warmup 2 --no-cpu-baseline --no-traffic --no-extras > $OUT/trace_$C.log 2>&1; echo "trace $C rc=$?"
 DB=$(find $OUT/trace_$C -name '*.db' | head -1)

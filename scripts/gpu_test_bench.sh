@@ -6,7 +6,7 @@ python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"
 tail -25 $OUT/pytest_gpu.log
 for CFG in ${2:-C3 C4 C5 C2}; do
-  timeout 900 python bench.py --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err; echo "$CFG rc=$?"
+  timeout 900 python bench.py --full --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err; echo "$CFG rc=$?"
   python - <<PY
 import json
 try:

@@ -28,7 +28,7 @@ def _last_json(stdout):
 
 @pytest.mark.gpu
 def test_bench_single_rank_line(gpu_required):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--spectra", "3000", "--proteins", "400",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--spectra", "3000", "--proteins", "400",
                         "--cpu-sample", "512", "--traffic-timeout", "90"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
@@ -53,11 +53,11 @@ def test_bench_single_rank_line(gpu_required):
     assert h2h["page_locked"] > 0 and h2h["pageable"] > 0 and j["pcie_inclusive_value"] == h2h["page_locked"]
 
 
-def _torchrun(n, extra, timeout=900):
+def _torchrun(n, extra, timeout=900, full=True):
     env = dict(os.environ, SAGE_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", str(n), "--steps", "3", "--warmup", "1", "--proteins", "300",
-           "--no-extras"] + extra
+           "--master-port", str(_free_port()), "bench.py", "--gpus", str(n), "--steps", "3", "--warmup", "1", "--proteins", "300"] \
+        + (["--full", "--no-extras"] if full else []) + extra
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     return _last_json(r.stdout)
@@ -88,3 +88,43 @@ def test_bench_weak_scaling_mode(gpu_required):
     assert j["n_gpus"] == 2 and j["scaling"] == "weak" and j["sharding"] is None
     per_rank = j["config"]["spectra_this_rank"]
     assert 1500 < per_rank <= 2000 and abs(j["config"]["spectra_total"] - 2 * per_rank) < 100
+
+
+def _dumped(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_same_outputs_every_time(gpu_required, tmp_path):
+    """A plain run (no --full) times the steps and prints the headline line only; --dump-outputs writes the last timed step's
+    records, the same from run to run, and a 2-rank strong-scaling run gathers the same records in input order."""
+    import numpy as np
+    args = ["--steps", "4", "--warmup", "1", "--spectra", "3000", "--proteins", "300"]
+    lines, dumps = [], []
+    for i in range(2):
+        d = str(tmp_path / f"run{i}")
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", *args, "--dump-outputs", d], cwd=ROOT, capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(_last_json(r.stdout))
+        dumps.append(_dumped(d))
+    j = lines[0]
+    assert j["steps"] == 4 and j["warmup"] == 1 and j["unit"] == "spectra/s" and j["dtype"] == "f32" and j["higher_is_better"] is True
+    assert abs(j["value"] - j["config"]["spectra_total"] * 1000.0 / j["ms_per_step"]) / j["value"] < 1e-9
+    assert j["cpu_baseline"] is None and j["parity"] is None and j["sustained"] is None and j["concurrent"] is None
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"counts", "row_index", "hyperscore", "peptide_idx", "spec_index"} <= set(a)
+    assert sum(os.path.getsize(os.path.join(tmp_path, "run0", f)) for f in os.listdir(tmp_path / "run0")) <= 64_000_000
+    n = j["config"]["spectra_this_rank"]
+    assert np.array_equal(a["row_index"], np.arange(n)) and int(a["counts"].sum()) == j["config"]["psms_per_step_rank0"]
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and len(a[k]) == n, k
+        assert np.array_equal(a[k], b[k]), k
+    d = str(tmp_path / "two_ranks")
+    j2 = _torchrun(2, ["--spectra", "3000", "--dump-outputs", d], full=False)
+    assert j2["n_gpus"] == 2 and j2["config"]["spectra_total"] == n and j2["sharding"] is None
+    c = _dumped(d)
+    assert sorted(c) == sorted(a)
+    for k in a:
+        assert np.array_equal(a[k], c[k]), k

@@ -13,7 +13,8 @@ from sage_amd.mzml import _f32, read_mzml, write_mzml
 from sage_amd.synthetic import synthetic_fasta, synthetic_spectra
 from test_oracle_golden import load_c1
 
-REF_MZML = "/root/reference/tests/LQSRPAAPPAPGPGQLTLR.mzML"
+# the reference's own test file (lazear/sage tests/LQSRPAAPPAPGPGQLTLR.mzML), stored as a fixture
+REF_MZML = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "LQSRPAAPPAPGPGQLTLR.mzML")
 
 
 def c1_raw():
@@ -46,7 +47,6 @@ def test_mzml_round_trip_and_reader_semantics(tmp_path):
     assert np.float32(b.scan_start_time) == np.float32(raw.scan_start_time)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MZML), reason="reference checkout not mounted (GPU box)")
 def test_reader_on_the_reference_fixture_matches_the_committed_decode():
     """The reference's own test file, read by read_mzml, equals tests/golden/c1_fixture.json (decoded independently
     by tests/golden/make_c1_fixture.py)."""
@@ -306,7 +306,7 @@ def _assert_same_run(batch, spectra, context):
 
 def test_native_mzml_reader_matches_the_python_reader(tmp_path):
     """csrc/mzml_reader.cpp against sage_amd/mzml.py (itself checked against the reference's fixture): synthetic files, a
-    hand-written file with the awkward cases, and the reference's own mzML when the checkout is present.  CPU only."""
+    hand-written file with the awkward cases, and the reference's own mzML (tests/golden).  CPU only."""
     import base64
     import zlib
     from sage_amd.mzml import read_mzml_native
@@ -378,9 +378,7 @@ def test_native_mzml_reader_matches_the_python_reader(tmp_path):
     assert ms2.precursor_charge[0] == 3 and np.float32(ms2.precursor_mz[0]) == np.float32(500.2500001)
     assert np.float32(ms2.isolation_lo[0]) == np.float32(-0.8) and np.float32(ms2.scan_start_time[0]) == np.float32(754.321) / np.float32(60)
     assert np.float32(ms2.precursor_mz[1]) == np.float32(733.3333333) and np.isnan(ms2.isolation_lo[1])
-    ref = "/root/reference/tests/LQSRPAAPPAPGPGQLTLR.mzML"
-    if os.path.exists(ref):
-        _assert_same_run(read_mzml_native(ref, 0, 2), read_mzml(ref, 0, 2), "reference fixture")
+    _assert_same_run(read_mzml_native(REF_MZML, 0, 2), read_mzml(REF_MZML, 0, 2), "reference fixture")
     with pytest.raises(Exception):
         read_mzml_native(str(tmp_path / "missing.mzML"))
 

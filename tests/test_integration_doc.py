@@ -8,18 +8,15 @@ definitions and to include/sage_hip.h mechanically:
 * every `extern "C"` function is declared in the header with the same number of parameters;
 * enum discriminants (Tolerance, ScoreType) agree with the header's constants.
 
-The reference's field lists live in tests/golden/reference_fields.json (made by tests/golden/make_reference_fields.py);
-when the checkout is mounted the list itself is re-derived and compared.
+The reference's field lists live in tests/golden/reference_fields.json, made from a reference checkout by
+tests/golden/make_reference_fields.py (run it again and diff the file to hold the list to a newer checkout).
 """
 import json
 import os
 import re
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_fields.json")
-REFERENCE = "/root/reference"
 
 
 def golden():
@@ -96,16 +93,6 @@ def function_bodies(code):
         out.setdefault(m.group(1), "")
         out[m.group(1)] += code[start:matching(code, start) + 1]
     return out
-
-
-def test_golden_matches_the_checkout():
-    if not os.path.isdir(os.path.join(REFERENCE, "crates", "sage", "src")):
-        pytest.skip("reference checkout not mounted")
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("mrf", os.path.join(ROOT, "tests", "golden", "make_reference_fields.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    assert mod.parse(REFERENCE) == golden()
 
 
 def test_feature_literal_names_exactly_the_reference_fields():
