@@ -5,14 +5,20 @@ database's ion kinds / min_ion_index / enzyme / bucket size are drawn TOGETHER f
 thought of meet — an asymmetric Da fragment tolerance under a chimeric wide-window search with five isotope errors, six ion kinds with
 fragment charge 4 behind an overridden precursor charge, a one-sided precursor window that selects nothing.  Every case goes
 through World.check: the preliminary lists (heap layout), every Feature field, a second step on the same handle, and the
-host-to-host entry point.  The seeds are fixed: the suite is deterministic, and a case that ever fails is reproduced by its id."""
+host-to-host entry point.  The same case then goes through the two other device paths the library ships: annotate_matches
+(annotate_kernel, every other case) against OracleDb.annotate, and quick_score in both flavours (quick_mark_kernel; rescore_kernel
+writing `keep`) against OracleDb.quick_score — the batch's keep array and, so that a wrong pick for one spectrum cannot hide behind
+another spectrum keeping the same peptide, the keep arrays of a few spectra scored alone.  A fourth world is C3T's digest over
+paralog families (workloads.py), where equal scores at every cut are common.  The seeds are fixed: the suite is deterministic, and
+a case that ever fails is reproduced by its id."""
+import copy
 import os
 
 import numpy as np
 import pytest
 
-from sage_amd.api import DatabaseParameters, ScorerParams, SpectrumBatch, Tolerance
-from sage_amd.synthetic import synthetic_fasta
+from sage_amd.api import DatabaseParameters, Scorer, ScorerParams, SpectrumBatch, Tolerance
+from sage_amd.synthetic import paralog_fasta, synthetic_fasta
 from test_gpu_parity import World
 
 pytestmark = pytest.mark.gpu
@@ -28,7 +34,16 @@ WORLDS = {
     "y_only": (dict(bucket_size=8192, enzyme=dict(missed_cleavages=0, cleave_at="FWYL", restrict=None, c_terminal=False, min_len=5, max_len=30),
                     ion_kinds=["y"], min_ion_index=3, generate_decoys=False),
                dict(annotate_charge=False, noise_peaks=30, keep_prob=0.8), 160, 40),
+    # C3T's digest over paralog families (workloads.py): shared, near-identical and I/L-twin peptides — equal scores at the
+    # cut of every k-select, where quick_score's order-free trims must keep the same SET as bounded_min_heapify
+    "paralog": (dict(bucket_size=8192, enzyme=dict(missed_cleavages=1, min_len=5, max_len=50, cleave_at="KR", restrict="P"),
+                     static_mods={"C": 57.0215}, variable_mods={"M": [15.9949], "[": [42.010565]}, max_variable_mods=2),
+                dict(varmod_frac=0.15), 200, 150),
 }
+# a world's index seeds its proteome and its cases (the order the worlds were added in: a case keeps its draws)
+ORDER = ["abcxyz", "by", "y_only", "paralog"]
+# spectra per case whose quick_score is also checked ALONE: a wrong pick for one spectrum cannot hide behind the batch's OR
+QUICK_SINGLES = 8
 # The suite's cases: 24 per world, salt 2026.  A campaign (scripts/gpu_fuzz_campaign.sh, filed as profiles/r06_fuzz_campaign.txt) runs
 # the same test over other cases: SAGE_FUZZ_CASES per world, drawn under SAGE_FUZZ_SALT.
 CASES_PER_WORLD = int(os.environ.get("SAGE_FUZZ_CASES", "24"))
@@ -100,18 +115,19 @@ def _coarse_peaks(batch, rng, zeros):
                          batch.scan_start_time, batch.inverse_ion_mobility, batch.file_id)
 
 
-@pytest.fixture(scope="module", params=sorted(WORLDS))
+@pytest.fixture(scope="module", params=ORDER)
 def world(request, gpu_required):
     db, spectra, n, peaks = WORLDS[request.param]
-    fasta = synthetic_fasta(180, seed=31 + sorted(WORLDS).index(request.param))
-    w = World(fasta, DatabaseParameters(**db), spectra, n, seed=41 + sorted(WORLDS).index(request.param), max_peaks=peaks)
+    k = ORDER.index(request.param)
+    fasta = paralog_fasta(45, 4, seed=31 + k) if request.param == "paralog" else synthetic_fasta(180, seed=31 + k)
+    w = World(fasta, DatabaseParameters(**db), spectra, n, seed=41 + k, max_peaks=peaks)
     w.name = request.param
     return w
 
 
 @pytest.mark.parametrize("case", range(CASES_PER_WORLD))
 def test_random_scorer_configuration(world, case):
-    rng = np.random.default_rng([sorted(WORLDS).index(world.name), case, SALT])
+    rng = np.random.default_rng([ORDER.index(world.name), case, SALT])
     params, open_search = _params(rng)
     batch = world.batch
     if open_search or params.wide_window or params.report_psms >= 20:
@@ -123,4 +139,41 @@ def test_random_scorer_configuration(world, case):
     how = rng.random()
     if how < 0.35:
         batch = _coarse_peaks(batch, rng, zeros=how < 0.1)
-    world.check(params, f"{world.name}/{case}: {params}", batch=batch)
+    context = f"{world.name}/{case}: {params}"
+    world.check(params, context, batch=batch)
+    more = np.random.default_rng([ORDER.index(world.name), case, SALT, 1])  # (the draws above stay those of earlier campaigns)
+    if case % 2 == 0:
+        check_annotation(world, params, batch, context)
+    check_quick_score(world, params, batch, more.choice(batch.n, min(QUICK_SINGLES, batch.n), replace=False), context)
+
+
+def check_annotation(world, params, batch, context):
+    """Scorer.annotate_matches (scoring.rs:722-752) against OracleDb.annotate: the PSM offsets and every Fragments array, bit for
+    bit.  A case may report PSMs with no matched fragment at all (min_matched_peaks 0) — then so must the oracle."""
+    params = copy.copy(params)
+    params.annotate_matches = True
+    scorer = Scorer(world.dev, params)
+    dbatch = scorer.upload(batch)
+    gf, gc = scorer.score_resident(dbatch)
+    goff, garr = scorer.annotate(dbatch, gf.copy(), gc.copy())
+    ooff, oarr = world.orc.annotate(params, batch)
+    np.testing.assert_array_equal(goff, ooff, err_msg=f"{context}: annotate: PSM offsets")
+    for k in ("kinds", "charges", "fragment_ordinals", "intensities", "mz_calculated", "mz_experimental"):
+        np.testing.assert_array_equal(garr[k], oarr[k], err_msg=f"{context}: annotate: Fragments.{k}")
+    assert len(garr["kinds"]) == int(goff[-1]) == len(oarr["kinds"])
+
+
+def check_quick_score(world, params, batch, singles, context):
+    """Scorer::quick_score (scoring.rs:255-298), both flavours: the batch's keep array, then the keep array of each spectrum in
+    `singles` scored alone."""
+    scorer = Scorer(world.dev, params)
+    dbatch = scorer.upload(batch)
+    alone = [(int(i), batch.subset(np.array([i]))) for i in singles]
+    dalone = [scorer.upload(b) for _, b in alone]
+    for low_memory in (False, True):
+        gk = scorer.quick_score(dbatch, low_memory)
+        np.testing.assert_array_equal(gk, world.orc.quick_score(params, batch, low_memory),
+                                      err_msg=f"{context}: quick_score low_memory={low_memory}")
+        for (i, b), d in zip(alone, dalone):
+            np.testing.assert_array_equal(scorer.quick_score(d, low_memory), world.orc.quick_score(params, b, low_memory),
+                                          err_msg=f"{context}: quick_score low_memory={low_memory}, spectrum {i} alone")

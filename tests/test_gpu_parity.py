@@ -114,6 +114,28 @@ def test_narrow_kernel_variants(small_world, monkeypatch, variant):
     small_world.check(ScorerParams(precursor_tol=Tolerance("da", -0.5, 0.5)), f"{variant}: charge None", batch=unknown)
 
 
+@pytest.mark.parametrize("keep_pm", [None, "1"])
+def test_stream_variant_with_the_kept_and_the_rebuilt_fragment_list(small_world, monkeypatch, keep_pm):
+    """The stream variant walks the peptide-major fragment list.  By default the index build releases it and the first batch
+    of the stream variant makes it again from a tile copy (capi.hip: ensure_pm_frag); SAGE_HIP_KEEP_PM_FRAG=1 keeps the one
+    the index was built from.  Both orders give the oracle's records (a new DeviceDatabase: the switch is read when the
+    database is created)."""
+    if keep_pm:
+        monkeypatch.setenv("SAGE_HIP_KEEP_PM_FRAG", keep_pm)
+    else:
+        monkeypatch.delenv("SAGE_HIP_KEEP_PM_FRAG", raising=False)
+    dev = DeviceDatabase(small_world.host, 0)
+    monkeypatch.delenv("SAGE_HIP_KEEP_PM_FRAG", raising=False)
+    monkeypatch.setenv("SAGE_HIP_NARROW", "stream")
+    small_world.check(ScorerParams(), f"keep_pm={keep_pm}: narrow ±10ppm", dev=dev)
+    small_world.check(ScorerParams(precursor_tol=Tolerance("da", -1.5, 1.5), report_psms=3, max_fragment_charge=3),
+                      f"keep_pm={keep_pm}: ±1.5 Da", dev=dev)
+    b = small_world.batch
+    unknown = SpectrumBatch(b.peak_off, b.masses, b.intensities, b.precursor_mz, np.zeros(b.n, np.uint8), b.total_ion_current)
+    small_world.check(ScorerParams(min_isotope_err=-1, max_isotope_err=2, precursor_tol=Tolerance("ppm", -20.0, 20.0)),
+                      f"keep_pm={keep_pm}: isotope -1..2, charge None", batch=unknown, dev=dev)
+
+
 @pytest.mark.parametrize("no_sched", [None, "1"])
 def test_schedule_records_and_the_order_array(small_world, monkeypatch, no_sched):
     """prelim_kernel / rescore_kernel start a block from the batch's schedule records (DevBatchView::sched: spectrum, peak range,
@@ -577,6 +599,24 @@ def test_quick_score_prefilter(small_world, low_memory):
         ok = small_world.orc.quick_score(params, batch, low_memory)
         np.testing.assert_array_equal(gk, ok, err_msg=f"quick_score low_memory={low_memory} {ctx}")
         assert gk.sum() > 10
+
+
+def test_quick_score_with_an_exhausted_arena(small_world, monkeypatch):
+    """An open-search quick_score whose large-window candidates overflow a 1 MiB arena: the resident entry point does not
+    split the batch (only score_batch does), so it must either give the oracle's keep array or refuse with an error that names
+    the arena — never a silently different keep array."""
+    monkeypatch.setenv("SAGE_HIP_ARENA_MB", "1")
+    params = ScorerParams(precursor_tol=Tolerance("da", -500.0, 100.0), report_psms=2)
+    sub = small_world.batch.subset(np.arange(0, small_world.batch.n, 3))
+    for low_memory in (False, True):
+        scorer = Scorer(small_world.dev, params)
+        try:
+            gk = scorer.quick_score(scorer.upload(sub), low_memory)
+        except L.SageHipError as e:
+            assert "arena" in str(e), e
+            continue
+        np.testing.assert_array_equal(gk, small_world.orc.quick_score(params, sub, low_memory),
+                                      err_msg=f"quick_score low_memory={low_memory}, 1 MiB arena")
 
 
 def _experiments_built(world, monkeypatch):
