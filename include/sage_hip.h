@@ -450,6 +450,78 @@ int sage_hip_write_results(const char* path, int format, const SageHostDb* db, c
                            const uint64_t* order, const uint64_t* psm_id, const char* const* filenames, uint32_t n_files,
                            const char* const* spec_ids, const SagePostColumns* post);
 
+/* ---- label-free MS1 quantification (sage-cli runner.rs:562-575: lfq::build_feature_map(..).quantify(..) then
+ * fdr::picked_precursor; crates/sage/src/lfq.rs, isotopes.rs, fdr.rs:228-287), MS1 spectra without ion mobility.
+ *   feature map   host: the first confident target feature per peptide; device: the charge x isotope x forward/decoy windows
+ *                 (tol_bounds, no FMA), rocPRIM sorts by (rt, peptide, charge, isotope, decoy) and, per 16 384-window page,
+ *                 by (mass_lo, rt position)
+ *   MS1 peaks     device: mz - PROTON, every peak, stably sorted by mass per spectrum (spectrum.rs:380-412)
+ *   traces        device: rt_slice + mass_lookup + Grid::add_entry; every grid cell adds its contributions in the order
+ *                 (MS1 spectrum as given, peak, match) — bit-identical to a sequential pass
+ *   integration   device, one block per grid: smoothing, spectral angle, time warps (slack 75), scores, peak bounds, areas
+ *   q-values      host: picked_precursor, ties of the f32 score kept in grid order
+ * Grids are reported in ascending (peptide_idx, charge, decoy) order; charge is 0 when charge states are combined. */
+enum { SAGE_LFQ_RETENTION_TIME = 0, SAGE_LFQ_SPECTRAL_ANGLE = 1, SAGE_LFQ_INTENSITY = 2, SAGE_LFQ_HYBRID = 3 };
+enum { SAGE_LFQ_APEX = 0, SAGE_LFQ_SUM = 1 };
+typedef struct SageLfqSettings {   /* lfq.rs:45-54 */
+    int32_t peak_scoring;          /* SAGE_LFQ_RETENTION_TIME .. SAGE_LFQ_HYBRID */
+    int32_t integration;           /* SAGE_LFQ_APEX / SAGE_LFQ_SUM */
+    double spectral_angle;
+    float ppm_tolerance;
+    float mobility_pct_tolerance;  /* accepted; MS1 spectra carry no mobility here */
+    float peptide_q_value;
+    uint8_t combine_charge_states;
+    uint8_t min_charge, max_charge;/* the search's precursor_charge range */
+    uint8_t pad;
+} SageLfqSettings;
+
+typedef struct SageLfqInput {
+    uint64_t n_features;
+    const SageFeature* features;   /* [n]: peptide_idx, label, calcmass, file_id are read */
+    const uint32_t* order;         /* [n] confidence order (SageRescoreOutput.order) or NULL: input order */
+    const float* aligned_rt;       /* [n], input order */
+    const float* peptide_q;        /* [n], input order */
+    const SageAlignment* alignments; /* [n_files], indexed by file id (SageRtOutput.alignments) */
+    uint32_t n_files;
+    uint32_t n_ms1;
+    const SageRawBatch* ms1;       /* [n_ms1] raw MS1 spectra (mz, intensities, scan_start_time, file_id), traced in order */
+    uint64_t n_peptides;
+    const uint16_t* carbon;        /* [n_peptides] mass.rs:78-104 composition of db[i].sequence */
+    const uint16_t* sulfur;
+    SageLfqSettings settings;
+} SageLfqInput;
+
+typedef struct SageLfqOutput {
+    /* caller-allocated host arrays of capacity `cap` grids (n_files areas / warps per grid) */
+    uint64_t cap;
+    uint32_t* peptide_idx;
+    uint8_t* charge;               /* 0: charge states combined */
+    uint8_t* decoy;
+    uint8_t* has_peak;             /* Traces::integrate returned Some */
+    uint32_t* peak_rt;             /* best RT bin */
+    uint32_t* left;                /* integration bounds [left, right) */
+    uint32_t* right;
+    double* score;
+    double* spectral_angle;
+    float* q_value;                /* 1.0 without a peak */
+    double* areas;                 /* [cap * n_files] */
+    int32_t* warps;                /* [cap * n_files] or NULL */
+    double* matrix;                /* [cap * n_files * 3 * 100] or NULL: each grid's summed intensities before smoothing */
+    /* filled by the call */
+    uint64_t n_grids;              /* grids that received at least one MS1 peak */
+    uint64_t n_windows;            /* precursor windows of the feature map */
+    uint64_t n_contributions;      /* (peak, window) matches */
+    uint64_t passing;              /* target peaks with q <= 0.05 (fdr.rs:270-277) */
+    float build_ms, ms1_ms, trace_ms, integrate_ms, device_ms; /* HIP-event times of the stages and of the whole call */
+} SageLfqOutput;
+
+/* SAGE_HIP_ERR_INVALID when `cap` is smaller than the grids the call finds (n_grids then holds the number needed). */
+int sage_hip_lfq(int device, const SageLfqInput* in, SageLfqOutput* out);
+
+/* lfq.tsv (sage-cli runner.rs:1182-1235): target grids with a peak, in the order given (rows: indices into the arrays). */
+int sage_hip_write_lfq(const char* path, const SageHostDb* db, const SageLfqOutput* grids, const uint64_t* rows, uint64_t n_rows,
+                       const char* const* filenames, uint32_t n_files);
+
 /* The competition keys of SageRescoreInput for `n` PSMs given their peptide indices (host work: string keys). */
 int sage_hip_hostdb_competition_keys(const SageHostDb* db, const uint32_t* peptide_idx, uint64_t n, uint32_t* peptide_key,
                                  uint32_t* n_peptide_keys, uint32_t* protein_key, uint32_t* n_protein_keys);

@@ -204,6 +204,28 @@ class SageRtOutput(C.Structure):
                 ("device_ms", C.c_float)]
 
 
+class SageLfqSettings(C.Structure):
+    _fields_ = [("peak_scoring", C.c_int32), ("integration", C.c_int32), ("spectral_angle", C.c_double),
+                ("ppm_tolerance", C.c_float), ("mobility_pct_tolerance", C.c_float), ("peptide_q_value", C.c_float),
+                ("combine_charge_states", C.c_uint8), ("min_charge", C.c_uint8), ("max_charge", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class SageLfqInput(C.Structure):
+    _fields_ = [("n_features", C.c_uint64), ("features", C.c_void_p), ("order", c_u32_p), ("aligned_rt", c_float_p),
+                ("peptide_q", c_float_p), ("alignments", C.POINTER(SageAlignment)), ("n_files", C.c_uint32),
+                ("n_ms1", C.c_uint32), ("ms1", C.POINTER(SageRawBatch)), ("n_peptides", C.c_uint64),
+                ("carbon", C.POINTER(C.c_uint16)), ("sulfur", C.POINTER(C.c_uint16)), ("settings", SageLfqSettings)]
+
+
+class SageLfqOutput(C.Structure):
+    _fields_ = [("cap", C.c_uint64), ("peptide_idx", c_u32_p), ("charge", c_u8_p), ("decoy", c_u8_p), ("has_peak", c_u8_p),
+                ("peak_rt", c_u32_p), ("left", c_u32_p), ("right", c_u32_p), ("score", C.POINTER(C.c_double)),
+                ("spectral_angle", C.POINTER(C.c_double)), ("q_value", c_float_p), ("areas", C.POINTER(C.c_double)),
+                ("warps", C.POINTER(C.c_int32)), ("matrix", C.POINTER(C.c_double)), ("n_grids", C.c_uint64),
+                ("n_windows", C.c_uint64), ("n_contributions", C.c_uint64), ("passing", C.c_uint64), ("build_ms", C.c_float),
+                ("ms1_ms", C.c_float), ("trace_ms", C.c_float), ("integrate_ms", C.c_float), ("device_ms", C.c_float)]
+
+
 class SagePostColumns(C.Structure):
     _fields_ = [(k, c_float_p) for k in ("discriminant_score", "posterior_error", "spectrum_q", "peptide_q", "protein_q",
                                          "aligned_rt", "predicted_rt", "delta_rt_model", "predicted_ims", "delta_ims_model")]
@@ -273,6 +295,9 @@ def load():
         "sage_hip_mzml_free": (None, [vp]),
         "sage_hip_write_results": (C.c_int, [C.c_char_p, C.c_int, vp, vp, C.c_uint64, c_u64_p, c_u64_p, C.POINTER(C.c_char_p),
                                              C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(SagePostColumns)]),
+        "sage_hip_lfq": (C.c_int, [C.c_int, C.POINTER(SageLfqInput), C.POINTER(SageLfqOutput)]),
+        "sage_hip_write_lfq": (C.c_int, [C.c_char_p, vp, C.POINTER(SageLfqOutput), c_u64_p, C.c_uint64, C.POINTER(C.c_char_p),
+                                         C.c_uint32]),
         "sage_hip_fasta_num_targets": (C.c_int, [C.c_char_p, C.POINTER(SageDbParams), c_u64_p]),
         "sage_hip_prefilter_chunk_size": (C.c_int, [C.c_char_p, C.POINTER(SageDbParams), C.c_uint64, c_u64_p]),
         "sage_hip_hostdb_build_chunk": (C.c_int, [C.c_char_p, C.POINTER(SageDbParams), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
@@ -297,6 +322,7 @@ EXPORTED_SYMBOLS = [
     "sage_hip_rescore", "sage_hip_hostdb_competition_keys", "sage_hip_fasta_num_targets", "sage_hip_prefilter_chunk_size",
     "sage_hip_hostdb_build_chunk", "sage_hip_hostdb_merge_kept", "sage_hip_predict_rt", "sage_hip_hostdb_feature_peptides",
     "sage_hip_write_results", "sage_hip_mzml_read", "sage_hip_mzml_view", "sage_hip_mzml_check_searchable", "sage_hip_mzml_spectrum_id", "sage_hip_mzml_free",
+    "sage_hip_lfq", "sage_hip_write_lfq",
 ]
 
 

@@ -824,3 +824,129 @@ def predict_rt(features: np.ndarray, n_files: int, seq_off, seq, monoisotopic, d
 
 def device_count() -> int:
     return int(L.load().sage_hip_device_count())
+
+
+# ---- label-free MS1 quantification (sage_hip_lfq) ---------------------------------------------------------------------------
+LFQ_SCORING = ("RetentionTime", "SpectralAngle", "Intensity", "Hybrid")  # lfq.rs:25-31 PeakScoringStrategy
+LFQ_INTEGRATION = ("Apex", "Sum")                                         # lfq.rs:33-37 IntegrationStrategy
+
+
+@dataclass
+class LfqSettings:  # lfq.rs:45-68 (defaults of LfqSettings::default)
+    peak_scoring: str = "Hybrid"
+    integration: str = "Sum"
+    spectral_angle: float = 0.70
+    ppm_tolerance: float = 5.0
+    mobility_pct_tolerance: float = 1.0
+    combine_charge_states: bool = True
+    peptide_q_value: float = 0.01
+
+    def to_c(self, precursor_charge) -> "L.SageLfqSettings":
+        if self.peak_scoring not in LFQ_SCORING or self.integration not in LFQ_INTEGRATION:
+            raise ValueError(f"unknown LFQ strategy {self.peak_scoring!r} / {self.integration!r}")
+        return L.SageLfqSettings(LFQ_SCORING.index(self.peak_scoring), LFQ_INTEGRATION.index(self.integration),
+                                 float(self.spectral_angle), float(self.ppm_tolerance), float(self.mobility_pct_tolerance),
+                                 float(self.peptide_q_value), int(bool(self.combine_charge_states)), int(precursor_charge[0]),
+                                 int(precursor_charge[1]), 0)
+
+
+# mass.rs:78-104 composition(aa): carbon and sulfur atoms per residue
+_CARBON = np.zeros(256, dtype=np.uint16)
+_SULFUR = np.zeros(256, dtype=np.uint16)
+for _aa, _c, _s in (("A", 3, 0), ("R", 6, 0), ("N", 4, 0), ("D", 4, 0), ("C", 3, 1), ("E", 5, 0), ("Q", 5, 0), ("G", 2, 0),
+                    ("H", 6, 0), ("I", 6, 0), ("L", 6, 0), ("K", 6, 0), ("M", 5, 1), ("F", 9, 0), ("P", 5, 0), ("S", 3, 0),
+                    ("T", 4, 0), ("W", 11, 0), ("Y", 9, 0), ("V", 5, 0), ("U", 3, 0), ("O", 12, 0)):
+    _CARBON[ord(_aa)], _SULFUR[ord(_aa)] = _c, _s
+
+
+def peptide_compositions(seq_off, seq):
+    """(carbon[n], sulfur[n]) of every peptide: the Composition sum of lfq.rs:258-263 (u16)."""
+    off = np.asarray(seq_off, dtype=np.int64)
+    s = np.asarray(seq, dtype=np.uint8)
+    n = len(off) - 1
+    if n <= 0:
+        return np.zeros(0, np.uint16), np.zeros(0, np.uint16)
+    cs = np.concatenate([[0], np.cumsum(_CARBON[s].astype(np.int64))])
+    ss = np.concatenate([[0], np.cumsum(_SULFUR[s].astype(np.int64))])
+    return ((cs[off[1:]] - cs[off[:-1]]).astype(np.uint16), (ss[off[1:]] - ss[off[:-1]]).astype(np.uint16))
+
+
+@dataclass
+class LfqResult:
+    """Grids of sage_hip_lfq in ascending (peptide_idx, charge, decoy) order; charge 0 when charge states are combined.
+    areas / warps: [n, n_files]; matrix: [n, n_files * 3, 100] (debug=True) or None."""
+    peptide_idx: np.ndarray
+    charge: np.ndarray
+    decoy: np.ndarray
+    has_peak: np.ndarray
+    peak_rt: np.ndarray
+    left: np.ndarray
+    right: np.ndarray
+    score: np.ndarray
+    spectral_angle: np.ndarray
+    q_value: np.ndarray
+    areas: np.ndarray
+    warps: np.ndarray
+    matrix: Optional[np.ndarray]
+    n_windows: int
+    n_contributions: int
+    passing: int
+    stage_ms: dict
+
+    def target_rows(self) -> np.ndarray:
+        """the rows lfq.tsv holds (runner.rs:1207-1210: targets; Traces::integrate returned a peak)"""
+        return np.flatnonzero((self.decoy == 0) & (self.has_peak != 0)).astype(np.uint64)
+
+    def to_c(self, keep: list) -> "L.SageLfqOutput":
+        arr = lambda a, t: (keep.append(a), L.as_ptr(a, t))[1]
+        return L.SageLfqOutput(len(self.peptide_idx), arr(self.peptide_idx, C.c_uint32), arr(self.charge, C.c_uint8),
+                               arr(self.decoy, C.c_uint8), arr(self.has_peak, C.c_uint8), arr(self.peak_rt, C.c_uint32),
+                               arr(self.left, C.c_uint32), arr(self.right, C.c_uint32), arr(self.score, C.c_double),
+                               arr(self.spectral_angle, C.c_double), arr(self.q_value, C.c_float),
+                               arr(np.ascontiguousarray(self.areas), C.c_double), None, None, len(self.peptide_idx))
+
+
+def lfq(features: np.ndarray, order, aligned_rt, peptide_q, alignments: np.ndarray, ms1: Sequence[RawBatch], carbon, sulfur,
+        settings: LfqSettings, precursor_charge, device: int = 0, debug: bool = False) -> LfqResult:
+    """build_feature_map(..).quantify(..) + picked_precursor (sage-cli runner.rs:562-575) on the device.
+    features / aligned_rt / peptide_q: the run's PSMs (input order) and their rescoring outputs; order: confidence order
+    (RescoreResult.order) or None; alignments: RtPrediction.alignments; ms1: raw MS1 spectra (RawBatch per file, file_id set);
+    carbon / sulfur: peptide_compositions of the database.  debug: also the warps and the grid matrices."""
+    f = np.ascontiguousarray(features, dtype=L.FEATURE_DTYPE).reshape(-1)
+    n = len(f)
+    order_a = None if order is None else np.ascontiguousarray(order, dtype=np.uint32)
+    art = np.ascontiguousarray(aligned_rt, dtype=np.float32)
+    pq = np.ascontiguousarray(peptide_q, dtype=np.float32)
+    al = np.ascontiguousarray(alignments, dtype=ALIGNMENT_DTYPE)
+    carbon = np.ascontiguousarray(carbon, dtype=np.uint16)
+    sulfur = np.ascontiguousarray(sulfur, dtype=np.uint16)
+    assert len(art) == n and len(pq) == n and (order_a is None or len(order_a) == n) and len(carbon) == len(sulfur)
+    n_files = len(al)
+    nz = int(precursor_charge[1]) - int(precursor_charge[0]) + 1
+    cand = (pq <= np.float32(settings.peptide_q_value)) & (f["label"] == 1)
+    cap = len(np.unique(f["peptide_idx"][cand])) * (2 if settings.combine_charge_states else 2 * nz)
+    batches = [b.to_c() for b in ms1]
+    cms1 = (L.SageRawBatch * max(len(batches), 1))(*batches)
+    cin = L.SageLfqInput(n, f.ctypes.data, None if order_a is None else L.as_ptr(order_a, C.c_uint32), L.as_ptr(art, C.c_float),
+                         L.as_ptr(pq, C.c_float), C.cast(al.ctypes.data, C.POINTER(L.SageAlignment)), n_files, len(batches), cms1,
+                         len(carbon), L.as_ptr(carbon, C.c_uint16), L.as_ptr(sulfur, C.c_uint16), settings.to_c(precursor_charge))
+    r = LfqResult(np.zeros(cap, np.uint32), np.zeros(cap, np.uint8), np.zeros(cap, np.uint8), np.zeros(cap, np.uint8),
+                  np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.float64),
+                  np.zeros(cap, np.float64), np.ones(cap, np.float32), np.zeros((cap, n_files), np.float64),
+                  np.zeros((cap, n_files), np.int32), np.zeros((cap, n_files * 3, 100), np.float64) if debug else None, 0, 0, 0, {})
+    keep = []
+    cout = r.to_c(keep)
+    cout.warps = L.as_ptr(r.warps, C.c_int32)
+    if debug:
+        cout.matrix = L.as_ptr(r.matrix, C.c_double)
+    L.check(L.load().sage_hip_lfq(device, C.byref(cin), C.byref(cout)))
+    g = int(cout.n_grids)
+    for k in ("peptide_idx", "charge", "decoy", "has_peak", "peak_rt", "left", "right", "score", "spectral_angle", "q_value",
+              "areas", "warps", "matrix"):
+        v = getattr(r, k)
+        if v is not None:
+            setattr(r, k, v[:g])
+    r.n_windows, r.n_contributions, r.passing = int(cout.n_windows), int(cout.n_contributions), int(cout.passing)
+    r.stage_ms = {"build_ms": float(cout.build_ms), "ms1_ms": float(cout.ms1_ms), "trace_ms": float(cout.trace_ms),
+                  "integrate_ms": float(cout.integrate_ms), "device_ms": float(cout.device_ms)}
+    return r

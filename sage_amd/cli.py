@@ -7,8 +7,8 @@ crates/sage-cli/src/input.rs (Input -> Search, :298-385; `database` = sage-core 
 flow of runner.rs (read mzML -> SpectrumProcessor::process -> keep MS2 with >= min_peaks peaks -> Scorer::score,
 :311-325, :398-461) and the `results.sage.tsv` / `matched_fragments.sage.tsv` writers (:687-935).  Everything downstream
 of Scorer::score is limited to the LDA rescoring, q-values and picked peptide / protein FDR (runner.rs:536-541, on the
-device: rescore.hip) and the optional percolator .pin file; retention-time / mobility prediction, protein grouping, LFQ/TMT,
-parquet, cloud IO are out of scope and their columns carry the defaults a Feature is born with (scoring.rs:576-592).  The search itself runs on the GPU through
+device: rescore.hip), label-free MS1 quantification when `quant.lfq` is true (runner.rs:562-575, lfq.hip: `lfq.tsv`) and the
+optional percolator .pin file; protein grouping, TMT, parquet, cloud IO are out of scope and their columns carry the defaults a Feature is born with (scoring.rs:576-592).  The search itself runs on the GPU through
 libsage_hip.so; there is no CPU fallback.
 """
 import argparse
@@ -21,8 +21,8 @@ import numpy as np
 
 from . import output
 from ._lib import FEATURE_DTYPE as L_FEATURE_DTYPE
-from .api import (DatabaseParameters, DeviceDatabase, RawBatch, Scorer, ScorerParams, SpectrumBatch, SpectrumProcessor,
-                  Tolerance, device_count, predict_rt, rescore)
+from .api import (LFQ_INTEGRATION, LFQ_SCORING, DatabaseParameters, DeviceDatabase, LfqSettings, RawBatch, Scorer, ScorerParams,
+                  SpectrumBatch, SpectrumProcessor, Tolerance, device_count, lfq, peptide_compositions, predict_rt, rescore)
 from .mzml import read_mzml_native
 
 
@@ -43,6 +43,40 @@ def search_parameters(cfg: dict) -> dict:
         chimera=bool(cfg.get("chimera", False)), wide_window=bool(cfg.get("wide_window", False)),
         score_type=cfg.get("score_type") or "SageHyperScore",
         predict_rt=True if cfg.get("predict_rt") is None else bool(cfg["predict_rt"]))  # input.rs:372
+
+
+def quant_settings(cfg: dict, log=print):
+    """QuantOptions -> QuantSettings (input.rs:87-133, 168-196): (lfq, LfqSettings).  `lfq` defaults to false; every absent
+    lfq_settings key takes LfqSettings::default (lfq.rs:56-68); spectral_angle and ppm_tolerance are taken as absolute values;
+    the strategies are the enum variant names ("Hybrid", "Sum", ...).  The warnings of input.rs:113-130 go to `log`."""
+    q = cfg.get("quant") or {}
+    on = bool(q.get("lfq")) if q.get("lfq") is not None else False
+    o = q.get("lfq_settings") or {}
+    d = LfqSettings()
+    pick = lambda k: d.__dict__[k] if o.get(k) is None else o[k]
+    st = LfqSettings(peak_scoring=pick("peak_scoring"), integration=pick("integration"),
+                     spectral_angle=abs(float(pick("spectral_angle"))), ppm_tolerance=abs(float(pick("ppm_tolerance"))),
+                     mobility_pct_tolerance=float(pick("mobility_pct_tolerance")),
+                     combine_charge_states=bool(pick("combine_charge_states")), peptide_q_value=float(pick("peptide_q_value")))
+    if st.peak_scoring not in LFQ_SCORING:
+        raise SystemExit(f"quant.lfq_settings.peak_scoring: unknown variant `{st.peak_scoring}`, expected one of "
+                         + ", ".join(f"`{v}`" for v in LFQ_SCORING))
+    if st.integration not in LFQ_INTEGRATION:
+        raise SystemExit(f"quant.lfq_settings.integration: unknown variant `{st.integration}`, expected one of "
+                         + ", ".join(f"`{v}`" for v in LFQ_INTEGRATION))
+    if st.ppm_tolerance > 20.0:
+        log("lfq_settings.ppm_tolerance is higher than expected")
+    if st.mobility_pct_tolerance > 4.0:
+        log("lfq_settings.mobility_pct_tolerance is higher than expected")
+    if st.mobility_pct_tolerance < 0.05:
+        log("lfq_settings.mobility_pct_tolerance is smaller than expected")
+    if st.spectral_angle < 0.50:
+        log("lfq_settings.spectral_angle is lower than expected")
+    if st.peptide_q_value > 0.01:
+        log("lfq_settings.peptide_q_value is higher than expected, expect increased runtime and memory usage")
+    if st.peptide_q_value < 0.01:
+        log("lfq_settings.peptide_q_value is lower than expected, not all identified peptides will have MS1 intensities extracted")
+    return on, st
 
 
 def scorer_params(sp: dict) -> ScorerParams:
@@ -223,6 +257,10 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     if device_count() <= 0:
         raise SystemExit("sage_amd.cli: no HIP device visible — libsage_hip has no CPU fallback")
     sp = search_parameters(cfg)
+    lfq_on, lfq_settings = quant_settings(cfg, log)
+    if lfq_on and not sp["predict_rt"]:  # input.rs:309-316
+        log("`predict_rt: false` and `lfq: true` are incompatible. Setting `predict_rt: true`")
+        sp["predict_rt"] = True
     dbp = DatabaseParameters.from_json(cfg["database"])
     if not dbp.fasta:
         raise SystemExit("`database.fasta` must be set. For more information try '--help'")
@@ -236,7 +274,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     t0 = time.time()
     fasta_text = read_text(dbp.fasta)
     params = scorer_params(sp)
-    processor = SpectrumProcessor(sp["max_peaks"], sp["deisotope"], 0.0)  # (no TMT reporter cut-off: quant is out of scope)
+    processor = SpectrumProcessor(sp["max_peaks"], sp["deisotope"], 0.0)  # (no TMT reporter cut-off: TMT is out of scope)
     host = None
     if dbp.prefilter:  # runner.rs:104-127
         chunk = dbp.auto_prefilter_chunk_size(fasta_text)
@@ -272,19 +310,23 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     def read_file(file_id, path):
         t0 = time.time()
         raw = read_mzml_native(path, file_id=file_id, ms_level=2, check_searchable=True)
-        return raw, (time.time() - t0) * 1000.0
+        ms1 = read_mzml_native(path, file_id=file_id, ms_level=1) if lfq_on else None  # (runner.rs:361-363: only for LFQ)
+        return raw, ms1, (time.time() - t0) * 1000.0
 
     mzml_paths = list(mzml_paths)
+    ms1_batches = []
     reader = ThreadPoolExecutor(max_workers=1)
     ahead = reader.submit(read_file, 0, mzml_paths[0]) if mzml_paths else None
     for file_id, path in enumerate(mzml_paths):
         try:
-            raw, io_ms = ahead.result()
+            raw, ms1, io_ms = ahead.result()
         except BaseException:
             reader.shutdown(wait=True)
             raise
         ahead = reader.submit(read_file, file_id + 1, mzml_paths[file_id + 1]) if file_id + 1 < len(mzml_paths) else None
         log(f"- file IO: {int(io_ms):8d} ms")
+        if ms1 is not None and ms1.n:
+            ms1_batches.append(ms1)
         if raw.n == 0:
             continue
         t0 = time.time()
@@ -357,6 +399,22 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
 
     if rescore_summary:
         log(f"- rescoring (RT / IM models, LDA, q-values, picked FDR): {int(rescore_summary['rescore_ms']):8d} ms")
+    lfq_result, lfq_summary = None, {}
+    if lfq_on and rtp is not None:  # runner.rs:562-575: only when the alignments exist
+        t0 = time.time()
+        if not ms1_batches:
+            log("no MS1 spectra found for quantification")  # lfq.rs:233
+        carbon, sulfur = peptide_compositions(host.seq_off, host.seq)
+        lfq_result = lfq(flat, post.order, rtp.aligned_rt, post.peptide_q, rtp.alignments, ms1_batches, carbon, sulfur,
+                         lfq_settings, sp["precursor_charge"], device=device)
+        log(f"discovered {lfq_result.passing} target MS1 peaks at 5% FDR")
+        lfq_ms = (time.time() - t0) * 1000.0
+        log(f"- label-free quantification: {int(lfq_ms):8d} ms")
+        lfq_summary = {"q_precursor": lfq_result.passing, "lfq_grids": len(lfq_result.peptide_idx),
+                       "lfq_windows": lfq_result.n_windows, "lfq_ms": lfq_ms, "lfq_device_ms": lfq_result.stage_ms["device_ms"],
+                       "lfq_stage_ms": lfq_result.stage_ms,
+                       "alignments": [{k: float(a[k]) if k != "file_id" else int(a[k]) for k in a.dtype.names}
+                                      for a in rtp.alignments]}
     # writers: C++ (sage_hip_write_results) — byte-identical to output.feature_row / pin_row, which tests/test_cli_io.py checks
     t_write = time.time()
     filenames = [os.path.basename(p) for p in mzml_paths]
@@ -369,15 +427,22 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         fp = os.path.join(output_directory, "matched_fragments.sage.tsv")
         output.write_fragments(fp, [r for i in order for r in frags[i]])
         paths.append(fp)
+    if lfq_result is not None:  # runner.rs:643-647
+        lp = os.path.join(output_directory, "lfq.tsv")
+        output.write_lfq_native(lp, host, lfq_result, filenames)
+        paths.append(lp)
     if write_pin:  # runner.rs:655-660
         pp = os.path.join(output_directory, "results.sage.pin")
         output.write_results_native(pp, "pin", host, flat, list(order), psm_ids, filenames, spec_ids, [rtp, post])
         paths.append(pp)
     stage_totals["write_ms"] = (time.time() - t_write) * 1e3
     log(f"- writing: {int(stage_totals['write_ms']):8d} ms")
+    if lfq_summary:
+        stage_totals["lfq_ms"] = lfq_summary["lfq_ms"]
     stage_totals["total_after_index_ms"] = (time.time() - t_run) * 1e3
     summary = {"version": "sage-hip 0.1 (search-and-score path of sage 0.15.0-beta.2)", "psms": len(flat),
-               "spectra_searched": n_searched, "search_ms": search_ms, "stages": stage_totals, "output_paths": paths, **rescore_summary}
+               "spectra_searched": n_searched, "search_ms": search_ms, "stages": stage_totals, "output_paths": paths, **rescore_summary,
+               **lfq_summary}
     with open(os.path.join(output_directory, "results.json"), "w") as fh:
         json.dump(dict(cfg, output_paths=paths, summary=summary), fh, indent=2, default=str)
     return summary

@@ -308,6 +308,41 @@ int sage_hip_predict_rt(int device, const SageRtInput* in, SageRtOutput* out) {
     return rc == SAGE_HIP_OK ? rc : fail(rc, err);
 }
 
+int sage_hip_lfq(int device, const SageLfqInput* in, SageLfqOutput* out) {
+    if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: null argument");
+    if (sage_hip_device_count() <= 0) return fail(SAGE_HIP_ERR_NO_DEVICE, "sage_hip_lfq: no HIP device (there is no CPU fallback)");
+    const SageLfqSettings& st = in->settings;
+    if (st.min_charge < 1 || st.max_charge < st.min_charge)
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: precursor charge range must be [lo >= 1, hi >= lo]");
+    if (st.peak_scoring < SAGE_LFQ_RETENTION_TIME || st.peak_scoring > SAGE_LFQ_HYBRID || (st.integration != SAGE_LFQ_APEX &&
+                                                                                           st.integration != SAGE_LFQ_SUM))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: unknown peak_scoring / integration strategy");
+    if ((in->n_features && (!in->features || !in->aligned_rt || !in->peptide_q)) || (in->n_files && !in->alignments) ||
+        (in->n_ms1 && !in->ms1) || (in->n_peptides && (!in->carbon || !in->sulfur)))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: null array");
+    if (out->cap && (!out->peptide_idx || !out->charge || !out->decoy || !out->has_peak || !out->peak_rt || !out->left ||
+                     !out->right || !out->score || !out->spectral_angle || !out->q_value || (in->n_files && !out->areas)))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: null output array");
+    for (uint32_t b = 0; b < in->n_ms1; ++b)
+        if (in->ms1[b].n_spectra && (!in->ms1[b].peak_off || !in->ms1[b].mz || !in->ms1[b].intensities))
+            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: null MS1 array");
+    std::string err;
+    const int rc = lfq_on_device(device, *in, *out, err);
+    return rc == SAGE_HIP_OK ? rc : fail(rc, err);
+}
+
+int sage_hip_write_lfq(const char* path, const SageHostDb* db, const SageLfqOutput* grids, const uint64_t* rows, uint64_t n_rows,
+                       const char* const* filenames, uint32_t n_files) {
+    if (!path || !db || !grids || (n_rows && !rows) || (n_files && !filenames))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_lfq: null argument");
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (rows[r] >= grids->n_grids || grids->peptide_idx[rows[r]] >= db->db.n_peptides())
+            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_lfq: row out of range");
+    std::string err;
+    if (!write_lfq(path, db->db, *grids, rows, n_rows, filenames, n_files, err)) return fail(SAGE_HIP_ERR_INVALID, err);
+    return SAGE_HIP_OK;
+}
+
 const char* sage_hip_last_error(void) { return g_last_error.c_str(); }
 int sage_hip_abi_version(void) { return SAGE_HIP_ABI_VERSION; }
 

@@ -273,6 +273,8 @@ int build_peptide_mass_lut(const float* d_pep_mono, uint32_t np, float top_mass,
 // rescore.hip
 int rescore_on_device(int device, const SageRescoreInput& in, SageRescoreOutput& out, std::string& err);
 int predict_rt_on_device(int device, const SageRtInput& in, SageRtOutput& out, std::string& err);
+// lfq.hip
+int lfq_on_device(int device, const SageLfqInput& in, SageLfqOutput& out, std::string& err);
 // process.hip
 // launch schedule of a batch (index_build.hip): order[k] = spectrum scored by block k, ascending neutral precursor mass
 size_t schedule_temp_bytes(uint32_t n);

@@ -93,6 +93,8 @@ bool read_mzml(const char* path, uint32_t file_id, int ms_level, MzmlRun& run, s
 bool write_results(const char* path, int format, const HostDb& db, const SageFeature* f, uint64_t n, const uint64_t* order,
                    const uint64_t* psm_id, const char* const* filenames, uint32_t n_files, const char* const* spec_ids,
                    const SagePostColumns* post, std::string& err);
+bool write_lfq(const char* path, const HostDb& db, const SageLfqOutput& g, const uint64_t* rows, uint64_t n_rows,
+               const char* const* filenames, uint32_t n_files, std::string& err);
 
 // f32 residue masses, mass.rs:64-76
 float residue_mass(uint8_t aa);

@@ -250,4 +250,42 @@ bool write_results(const char* path, int format, const HostDb& db, const SageFea
     return ok;
 }
 
+// write_lfq, runner.rs:1182-1235: target rows only (the caller's `rows`), charge -1 when charge states are combined,
+// q_value f32, score / spectral_angle / one area per file f64.
+bool write_lfq(const char* path, const HostDb& db, const SageLfqOutput& g, const uint64_t* rows, uint64_t n_rows,
+               const char* const* filenames, uint32_t n_files, std::string& err) {
+    FILE* fh = std::fopen(path, "wb");
+    if (!fh) {
+        err = std::string("cannot open ") + path;
+        return false;
+    }
+    std::string out = "peptide\tcharge\tproteins\tq_value\tscore\tspectral_angle";
+    for (uint32_t f = 0; f < n_files; ++f) {
+        out += '\t';
+        out += filenames[f];
+    }
+    out += '\n';
+    bool ok = true;
+    for (uint64_t r = 0; r < n_rows && ok; ++r) {
+        const uint64_t i = rows[r];
+        const uint64_t pep = g.peptide_idx[i];
+        str(out, db.peptide_string(pep));
+        itoa(out, g.charge[i] ? (int)g.charge[i] : -1);
+        str(out, db.peptide_proteins(pep));
+        f32(out, g.q_value[i]);
+        f64(out, g.score[i]);
+        f64(out, g.spectral_angle[i]);
+        for (uint32_t f = 0; f < n_files; ++f) f64(out, g.areas[i * n_files + f]);
+        out.back() = '\n';
+        if (out.size() >= (1 << 20)) {
+            ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+            out.clear();
+        }
+    }
+    if (ok && !out.empty()) ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+    if (std::fclose(fh) != 0) ok = false;
+    if (!ok && err.empty()) err = std::string("write to ") + path + " failed";
+    return ok;
+}
+
 }  // namespace sagehip

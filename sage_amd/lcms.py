@@ -1,0 +1,116 @@
+"""Synthetic multi-file LC-MS runs (MS1 + MS2) for label-free quantification.
+
+Each file holds the same peptides eluting as Gaussians in retention time; every file has its own RT scale and shift.  MS1
+scans carry the peptides' Poisson isotope envelopes at charges 2..4 plus uniform noise centroids; MS2 scans near each
+peptide's apex use the b/y model of synthetic.synthetic_spectra, so the search identifies them.  All randomness comes from
+numpy.random.default_rng(seed).
+"""
+import os
+from dataclasses import dataclass
+from typing import List
+
+import numpy as np
+
+from .api import IndexedDatabase, RawSpectrum
+from .synthetic import _MASS_LUT, PROTON
+
+NEUTRON = 1.00335
+
+
+@dataclass
+class LcmsFile:
+    spectra: List[RawSpectrum]  # in scan order (scan start time ascending)
+    ms_levels: List[int]
+    rt_scale: float
+    rt_shift: float
+    peptides: np.ndarray        # the peptides of the experiment
+    apex: np.ndarray            # their apex, as a fraction of the run (before the file's scale and shift)
+
+
+def _ms2(db: IndexedDatabase, pep: int, z: int, rng, noise_peaks: int, keep_prob: float, ppm_sigma: float):
+    a, b = int(db.seq_off[pep]), int(db.seq_off[pep + 1])
+    res = _MASS_LUT[db.seq[a:b]] + db.mods[a:b].astype(np.float64)
+    nterm = float(db.nterm[pep]) if not np.isnan(db.nterm[pep]) else 0.0
+    mono = float(db.pep_mono[pep])
+    bs = nterm + np.cumsum(res)[:-1]
+    frag = np.concatenate([bs, mono - bs])
+    cand = [frag + PROTON] + ([(frag + 2 * PROTON) / 2.0] if z >= 3 else [])
+    cand = np.concatenate(cand)
+    keep = rng.random(len(cand)) < keep_prob
+    mz = np.concatenate([cand[keep] * (1.0 + rng.normal(0.0, ppm_sigma, keep.sum()) * 1e-6), rng.uniform(150.0, 1800.0, noise_peaks)])
+    it = np.concatenate([rng.lognormal(8.0, 1.2, keep.sum()), rng.lognormal(6.5, 1.0, noise_peaks)])
+    ok = (mz > 100.0) & (mz < 2500.0)
+    order = np.argsort(mz[ok], kind="stable")
+    prec = (mono + z * PROTON) / z * (1.0 + rng.normal(0.0, ppm_sigma) * 1e-6)
+    return mz[ok][order].astype(np.float32), it[ok][order].astype(np.float32), prec
+
+
+def poisson_envelope(mass: float, n: int = 4) -> np.ndarray:
+    """relative isotope abundances ~ Poisson(mass / 1800)"""
+    lam = mass / 1800.0
+    k = np.arange(n)
+    p = np.exp(-lam) * lam ** k / np.array([1, 1, 2, 6, 24, 120][:n])
+    return p / p.max()
+
+
+def synthetic_lcms(db: IndexedDatabase, n_files: int = 3, n_peptides: int = 40, ms1_per_file: int = 200, seed: int = 0,
+                   run_minutes: float = 60.0, peak_width: float = 0.002, ms1_noise: int = 60, ms2_per_peptide: int = 2,
+                   charges=(2, 3, 4), ppm_sigma: float = 2.0, ms2_noise: int = 40, keep_prob: float = 0.6,
+                   peptides=None) -> List[LcmsFile]:
+    """Files of one LC-MS experiment.  peak_width: Gaussian sigma of an elution profile, as a fraction of the run.  A file's
+    retention time is `apex * rt_scale + rt_shift` (minutes).  peptides: target peptide indices (default: drawn)."""
+    rng = np.random.default_rng(seed)
+    targets = np.flatnonzero(db.decoy == 0)
+    peps = np.asarray(peptides) if peptides is not None else rng.choice(targets, size=min(n_peptides, len(targets)), replace=False)
+    apex = rng.uniform(0.12, 0.88, len(peps))               # fraction of the run
+    abundance = rng.lognormal(13.0, 1.0, len(peps))
+    zfrac = rng.dirichlet(np.ones(len(charges)), len(peps))  # charge-state distribution per peptide
+    mono = db.pep_mono[peps].astype(np.float64)
+    env = [poisson_envelope(m) for m in mono]
+    files = []
+    for f in range(n_files):
+        scale = 1.0 + rng.uniform(-0.03, 0.03) if f else 1.0
+        shift = rng.uniform(-0.01, 0.01) * run_minutes if f else 0.0
+        times = (np.arange(ms1_per_file) + 0.5) / ms1_per_file * run_minutes
+        entries = []  # (time, level, spectrum)
+        sigma = peak_width * run_minutes
+        centers = apex * run_minutes * scale + shift
+        for t in times:
+            mzs, ints = [rng.uniform(300.0, 1600.0, ms1_noise)], [rng.lognormal(7.0, 1.0, ms1_noise)]
+            near = np.flatnonzero(np.abs(t - centers) < 4.0 * sigma)
+            for p in near:
+                h = abundance[p] * np.exp(-0.5 * ((t - centers[p]) / sigma) ** 2) * rng.lognormal(0.0, 0.05)
+                for zi, z in enumerate(charges):
+                    iso = np.arange(len(env[p]))
+                    mz = (mono[p] + iso * NEUTRON) / z + PROTON
+                    mzs.append(mz * (1.0 + rng.normal(0.0, ppm_sigma, len(mz)) * 1e-6))
+                    ints.append(h * zfrac[p, zi] * env[p])
+            mz = np.concatenate(mzs)
+            it = np.concatenate(ints)
+            order = np.argsort(mz, kind="stable")
+            entries.append((t, 1, mz[order].astype(np.float32), it[order].astype(np.float32), 0.0, None))
+        for p in range(len(peps)):
+            for k in range(ms2_per_peptide):
+                t = centers[p] + rng.normal(0.0, 0.3 * sigma)
+                z = int(rng.choice(charges))
+                mz, it, prec = _ms2(db, int(peps[p]), z, rng, ms2_noise, keep_prob, ppm_sigma)
+                entries.append((t, 2, mz, it, prec, z))
+        entries.sort(key=lambda e: e[0])
+        spectra, levels = [], []
+        for i, (t, lvl, mz, it, prec, z) in enumerate(entries):
+            spectra.append(RawSpectrum(mz, it, float(np.float32(prec)), z, None, scan_start_time=float(np.float32(max(t, 0.0))),
+                                       file_id=f, id=f"scan={i + 1}"))
+            levels.append(lvl)
+        files.append(LcmsFile(spectra, levels, scale, shift, peps, apex))
+    return files
+
+
+def write_lcms(directory: str, files: List[LcmsFile], stem: str = "run") -> List[str]:
+    from .mzml import write_mzml
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for f, lf in enumerate(files):
+        path = os.path.join(directory, f"{stem}{f}.mzML")
+        write_mzml(path, lf.spectra, lf.ms_levels)
+        paths.append(path)
+    return paths

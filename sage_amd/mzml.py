@@ -181,19 +181,24 @@ def _b64(arr: np.ndarray) -> str:
     return base64.b64encode(zlib.compress(np.ascontiguousarray(arr, dtype="<f4").tobytes())).decode()
 
 
-def write_mzml(path: str, spectra: List[RawSpectrum]) -> None:
-    """Centroid MS2 spectra, 32-bit zlib arrays, selected ion m/z / charge, isolation offsets, scan start time (minutes)."""
+def write_mzml(path: str, spectra: List[RawSpectrum], ms_levels: Optional[List[int]] = None) -> None:
+    """Centroid MS2 spectra, 32-bit zlib arrays, selected ion m/z / charge, isolation offsets, scan start time (minutes).
+    ms_levels: per spectrum (default 2); an `ms level` 1 spectrum is written without a precursor list."""
     with open(path, "w") as f:
         f.write('<?xml version="1.0" encoding="utf-8"?>\n<mzML xmlns="http://psi.hupo.org/ms/mzml" version="1.1.0">\n')
         f.write(f'<run id="synthetic"><spectrumList count="{len(spectra)}">\n')
         for i, s in enumerate(spectra):
             sid = s.id or f"scan={i + 1}"
             f.write(f'<spectrum index="{i}" id="{sid}" defaultArrayLength="{len(s.mz)}">\n')
-            f.write('<cvParam cvRef="MS" accession="MS:1000511" name="ms level" value="2"/>\n')
+            level = 2 if ms_levels is None else int(ms_levels[i])
+            f.write(f'<cvParam cvRef="MS" accession="MS:1000511" name="ms level" value="{level}"/>\n')
             f.write('<cvParam cvRef="MS" accession="MS:1000127" name="centroid spectrum"/>\n')
             f.write(f'<scanList count="1"><scan><cvParam cvRef="MS" accession="MS:1000016" name="scan start time" '
                     f'value="{np.format_float_positional(np.float32(s.scan_start_time), unique=True)}" unitCvRef="UO" '
                     f'unitAccession="UO:0000031" unitName="minute"/></scan></scanList>\n')
+            if level == 1:
+                _write_arrays(f, s)
+                continue
             f.write('<precursorList count="1"><precursor>')
             if s.isolation_window is not None:
                 lo, hi = s.isolation_window
@@ -207,10 +212,14 @@ def write_mzml(path: str, spectra: List[RawSpectrum]) -> None:
             if s.precursor_charge:
                 f.write(f'<cvParam cvRef="MS" accession="MS:1000041" name="charge state" value="{int(s.precursor_charge)}"/>')
             f.write('</selectedIon></selectedIonList></precursor></precursorList>\n')
-            f.write('<binaryDataArrayList count="2">')
-            for acc, name, arr in (("MS:1000514", "m/z array", s.mz), ("MS:1000515", "intensity array", s.intensity)):
-                f.write('<binaryDataArray><cvParam cvRef="MS" accession="MS:1000521" name="32-bit float"/>'
-                        '<cvParam cvRef="MS" accession="MS:1000574" name="zlib compression"/>'
-                        f'<cvParam cvRef="MS" accession="{acc}" name="{name}"/><binary>{_b64(arr)}</binary></binaryDataArray>')
-            f.write('</binaryDataArrayList>\n</spectrum>\n')
+            _write_arrays(f, s)
         f.write('</spectrumList></run></mzML>\n')
+
+
+def _write_arrays(f, s) -> None:
+    f.write('<binaryDataArrayList count="2">')
+    for acc, name, arr in (("MS:1000514", "m/z array", s.mz), ("MS:1000515", "intensity array", s.intensity)):
+        f.write('<binaryDataArray><cvParam cvRef="MS" accession="MS:1000521" name="32-bit float"/>'
+                '<cvParam cvRef="MS" accession="MS:1000574" name="zlib compression"/>'
+                f'<cvParam cvRef="MS" accession="{acc}" name="{name}"/><binary>{_b64(arr)}</binary></binaryDataArray>')
+    f.write('</binaryDataArrayList>\n</spectrum>\n')

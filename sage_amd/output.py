@@ -202,3 +202,40 @@ def write_results_native(path: str, fmt: str, db, features, order, psm_ids, file
     L.check(L.load().sage_hip_write_results(path.encode(), {"tsv": 0, "pin": 1}[fmt], db._h, f.ctypes.data, n,
                                             None if order_a is None else L.as_ptr(order_a, C.c_uint64), L.as_ptr(ids, C.c_uint64),
                                             names, len(filenames), specs, C.byref(cols)))
+
+
+LFQ_HEADERS = ["peptide", "charge", "proteins", "q_value", "score", "spectral_angle"]
+
+
+def lfq_rows(db, result, rows) -> List[List[str]]:
+    """write_lfq (runner.rs:1182-1235) for the grids `rows` of an LfqResult: charge -1 when charge states are combined,
+    q_value f32, score / spectral_angle / areas f64."""
+    out = []
+    for i in rows:
+        i = int(i)
+        pep = int(result.peptide_idx[i])
+        z = int(result.charge[i])
+        out.append([db.peptide_string(pep), str(z if z else -1), db.peptide_proteins(pep), ryu_f32(result.q_value[i]),
+                    ryu_f64(result.score[i]), ryu_f64(result.spectral_angle[i])] + [ryu_f64(a) for a in result.areas[i]])
+    return out
+
+
+def write_lfq(path: str, filenames: Sequence[str], rows: Sequence[List[str]]) -> None:
+    with open(path, "w", newline="") as fh:
+        fh.write("\t".join(LFQ_HEADERS + list(filenames)) + "\n")
+        for r in rows:
+            fh.write("\t".join(r) + "\n")
+
+
+def write_lfq_native(path: str, db, result, filenames: Sequence[str], rows=None) -> None:
+    """lfq.tsv through the C++ writer (sage_hip_write_lfq): the bytes of lfq_rows + write_lfq.  rows: grid indices, default
+    the target grids with a peak in grid order (ascending peptide index, then charge)."""
+    import ctypes as C
+
+    from . import _lib as L
+    rows = np.ascontiguousarray(result.target_rows() if rows is None else rows, dtype=np.uint64)
+    keep = []
+    cout = result.to_c(keep)
+    names = (C.c_char_p * max(len(filenames), 1))(*[s.encode() for s in filenames])
+    L.check(L.load().sage_hip_write_lfq(path.encode(), db._h, C.byref(cout), L.as_ptr(rows, C.c_uint64), len(rows), names,
+                                        len(filenames)))
