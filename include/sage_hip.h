@@ -426,6 +426,13 @@ int sage_hip_mzml_check_searchable(const SageMzml* run);
 int sage_hip_mzml_view(const SageMzml* run, SageRawBatch* out);
 const char* sage_hip_mzml_spectrum_id(const SageMzml* run, uint64_t i);
 void sage_hip_mzml_free(SageMzml* run);
+/* sage_hip_mzml_read with MzMLReader::set_signal_to_noise(Some(sn_level)) (mzml.rs:371-381): every kept spectrum of MS level
+ * sn_level that carries a noise array (MS:1002744) gets intensity[i] /= noise[i], i below the shorter length.  Only a
+ * spectrum's own noise array divides it.  sn_level < 0: sage_hip_mzml_read. */
+int sage_hip_mzml_read_sn(const char* path, uint32_t file_id, int ms_level, int sn_level, SageMzml** out);
+/* RawSpectrum.ion_injection_time (MS:1000927; 0 when absent) and precursors.first().spectrum_ref ("" when absent) */
+float sage_hip_mzml_ion_injection_time(const SageMzml* run, uint64_t i);
+const char* sage_hip_mzml_precursor_ref(const SageMzml* run, uint64_t i);
 
 /* ---- writers (host): results.sage.tsv / results.sage.pin, byte for byte as sage-cli/src/runner.rs:687-780, :830-905,
  * :938-1135 format them (itoa integers, ryu floats).  Arrays of SagePostColumns may be NULL: the Feature defaults of
@@ -520,6 +527,44 @@ int sage_hip_lfq(int device, const SageLfqInput* in, SageLfqOutput* out);
 
 /* lfq.tsv (sage-cli runner.rs:1182-1235): target grids with a peak, in the order given (rows: indices into the arrays). */
 int sage_hip_write_lfq(const char* path, const SageHostDb* db, const SageLfqOutput* grids, const uint64_t* rows, uint64_t n_rows,
+                       const char* const* filenames, uint32_t n_files);
+
+/* ---- TMT reporter-ion quantification (sage-cli runner.rs:334-359: tmt::quantify, tmt.rs:193-214, 314-352).  For every
+ * spectrum of the batches (the spectra of the quant level, in output order) and every label: the peak
+ * select_most_intense_peak(masses, intensities, label, tolerance, Some(-PROTON)) picks (spectrum.rs:134-159).
+ *   level 2   SpectrumProcessor::new(take_top_n, deisotope, min_deisotope_mz).process() on the device first — the code of
+ *             sage_hip_batch_process_upload with min_peaks 0 — then the extraction over the resident processed peaks
+ *   other     mass = mz - PROTON for every peak, extraction over the raw peaks without sorting them (tmt.hip: the selection
+ *             is the maximum of a total-order key)
+ * intensity[i * n_labels + k]: the picked peak's intensity, 0.0 without one; peak_index (may be NULL): its position in the
+ * processed spectrum (level 2) or in the raw spectrum as given (other levels), -1 without one. */
+typedef struct SageTmtInput {
+    uint32_t n_batches;
+    const SageRawBatch* batches;   /* peak_off, mz, intensities (+ precursor_charge at level 2) are read */
+    int32_t level;
+    uint32_t n_labels;
+    const float* labels;           /* reporter m/z, any order, duplicates allowed */
+    SageTolerance tolerance;       /* the CLI passes Ppm(-20, 20) */
+    uint64_t take_top_n;           /* level 2 only */
+    int32_t deisotope;
+    float min_deisotope_mz;
+} SageTmtInput;
+
+typedef struct SageTmtOutput {
+    float* intensity;              /* [n_spectra * n_labels], n_spectra summed over the batches */
+    int32_t* peak_index;           /* [n_spectra * n_labels] or NULL */
+    /* filled by the call: HIP-event times summed over the batches.  upload_ms: raw peaks to the device (levels != 2);
+     * process_ms: upload + process_kernel + compaction (level 2); extract_ms: the extraction kernel; device_ms: the whole
+     * call, downloads included */
+    float upload_ms, process_ms, extract_ms, device_ms;
+} SageTmtOutput;
+
+int sage_hip_tmt(int device, const SageTmtInput* in, SageTmtOutput* out);
+
+/* tmt.tsv (sage-cli runner.rs:1140-1180): filename, scannr (spec_ids as given), ion_injection_time, then one column per header;
+ * ryu f32.  file_id indexes filenames. */
+int sage_hip_write_tmt(const char* path, const char* const* headers, uint32_t n_labels, uint64_t n_rows, const uint32_t* file_id,
+                       const char* const* spec_ids, const float* ion_injection_time, const float* intensity,
                        const char* const* filenames, uint32_t n_files);
 
 /* The competition keys of SageRescoreInput for `n` PSMs given their peptide indices (host work: string keys). */

@@ -226,6 +226,17 @@ class SageLfqOutput(C.Structure):
                 ("ms1_ms", C.c_float), ("trace_ms", C.c_float), ("integrate_ms", C.c_float), ("device_ms", C.c_float)]
 
 
+class SageTmtInput(C.Structure):
+    _fields_ = [("n_batches", C.c_uint32), ("batches", C.POINTER(SageRawBatch)), ("level", C.c_int32), ("n_labels", C.c_uint32),
+                ("labels", c_float_p), ("tolerance", SageTolerance), ("take_top_n", C.c_uint64), ("deisotope", C.c_int32),
+                ("min_deisotope_mz", C.c_float)]
+
+
+class SageTmtOutput(C.Structure):
+    _fields_ = [("intensity", c_float_p), ("peak_index", C.POINTER(C.c_int32)), ("upload_ms", C.c_float), ("process_ms", C.c_float),
+                ("extract_ms", C.c_float), ("device_ms", C.c_float)]
+
+
 class SagePostColumns(C.Structure):
     _fields_ = [(k, c_float_p) for k in ("discriminant_score", "posterior_error", "spectrum_q", "peptide_q", "protein_q",
                                          "aligned_rt", "predicted_rt", "delta_rt_model", "predicted_ims", "delta_ims_model")]
@@ -293,6 +304,12 @@ def load():
         "sage_hip_mzml_check_searchable": (C.c_int, [vp]),
         "sage_hip_mzml_spectrum_id": (C.c_char_p, [vp, C.c_uint64]),
         "sage_hip_mzml_free": (None, [vp]),
+        "sage_hip_mzml_read_sn": (C.c_int, [C.c_char_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(vp)]),
+        "sage_hip_mzml_ion_injection_time": (C.c_float, [vp, C.c_uint64]),
+        "sage_hip_mzml_precursor_ref": (C.c_char_p, [vp, C.c_uint64]),
+        "sage_hip_tmt": (C.c_int, [C.c_int, C.POINTER(SageTmtInput), C.POINTER(SageTmtOutput)]),
+        "sage_hip_write_tmt": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, c_u32_p, C.POINTER(C.c_char_p),
+                                         c_float_p, c_float_p, C.POINTER(C.c_char_p), C.c_uint32]),
         "sage_hip_write_results": (C.c_int, [C.c_char_p, C.c_int, vp, vp, C.c_uint64, c_u64_p, c_u64_p, C.POINTER(C.c_char_p),
                                              C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(SagePostColumns)]),
         "sage_hip_lfq": (C.c_int, [C.c_int, C.POINTER(SageLfqInput), C.POINTER(SageLfqOutput)]),
@@ -322,7 +339,8 @@ EXPORTED_SYMBOLS = [
     "sage_hip_rescore", "sage_hip_hostdb_competition_keys", "sage_hip_fasta_num_targets", "sage_hip_prefilter_chunk_size",
     "sage_hip_hostdb_build_chunk", "sage_hip_hostdb_merge_kept", "sage_hip_predict_rt", "sage_hip_hostdb_feature_peptides",
     "sage_hip_write_results", "sage_hip_mzml_read", "sage_hip_mzml_view", "sage_hip_mzml_check_searchable", "sage_hip_mzml_spectrum_id", "sage_hip_mzml_free",
-    "sage_hip_lfq", "sage_hip_write_lfq",
+    "sage_hip_lfq", "sage_hip_write_lfq", "sage_hip_mzml_read_sn", "sage_hip_mzml_ion_injection_time", "sage_hip_mzml_precursor_ref",
+    "sage_hip_tmt", "sage_hip_write_tmt",
 ]
 
 

@@ -307,6 +307,8 @@ class RawSpectrum:  # spectrum.rs:81-106 (MS2, centroided)
     inverse_ion_mobility: Optional[float] = None
     file_id: int = 0
     id: str = ""
+    ion_injection_time: float = 0.0  # MS:1000927
+    precursor_ref: str = ""          # precursors.first().spectrum_ref ("" == None)
 
 
 @dataclass
@@ -499,11 +501,14 @@ class RawBatch:
         self.scan_start_time = f32([s.scan_start_time for s in spectra])
         self.inverse_ion_mobility = f32([nan if s.inverse_ion_mobility is None else s.inverse_ion_mobility for s in spectra])
         self.file_id = np.ascontiguousarray([s.file_id for s in spectra], dtype=np.uint32)
+        self.ion_injection_time = f32([s.ion_injection_time for s in spectra])
+        self.precursor_ref = [s.precursor_ref for s in spectra]
 
     @classmethod
     def from_arrays(cls, ids, peak_off, mz, intensities, precursor_mz, precursor_charge, isolation_lo, isolation_hi,
-                    scan_start_time, inverse_ion_mobility, file_id) -> "RawBatch":
-        """Adopt SoA arrays (NaN == None for the optional floats, 0 == unknown charge): what the C++ mzML reader returns."""
+                    scan_start_time, inverse_ion_mobility, file_id, ion_injection_time=None, precursor_ref=None) -> "RawBatch":
+        """Adopt SoA arrays (NaN == None for the optional floats, 0 == unknown charge): what the C++ mzML reader returns.
+        ion_injection_time / precursor_ref default to 0.0 / ""."""
         b = cls.__new__(cls)
         b.n = len(precursor_mz)
         b.ids = list(ids)
@@ -515,6 +520,8 @@ class RawBatch:
         b.isolation_lo, b.isolation_hi = f32(isolation_lo), f32(isolation_hi)
         b.scan_start_time, b.inverse_ion_mobility = f32(scan_start_time), f32(inverse_ion_mobility)
         b.file_id = np.ascontiguousarray(file_id, dtype=np.uint32)
+        b.ion_injection_time = np.zeros(b.n, np.float32) if ion_injection_time is None else f32(ion_injection_time)
+        b.precursor_ref = [""] * b.n if precursor_ref is None else list(precursor_ref)
         assert len(b.peak_off) == b.n + 1 and len(b.mz) == len(b.intensities) == int(b.peak_off[-1])
         return b
 
@@ -524,7 +531,8 @@ class RawBatch:
         return RawBatch.from_arrays(self.ids[begin:end], self.peak_off[begin:end + 1] - np.uint64(a), self.mz[a:b], self.intensities[a:b],
                                     self.precursor_mz[begin:end], self.precursor_charge[begin:end], self.isolation_lo[begin:end],
                                     self.isolation_hi[begin:end], self.scan_start_time[begin:end],
-                                    self.inverse_ion_mobility[begin:end], self.file_id[begin:end])
+                                    self.inverse_ion_mobility[begin:end], self.file_id[begin:end],
+                                    self.ion_injection_time[begin:end], self.precursor_ref[begin:end])
 
     def subset(self, idx) -> "RawBatch":
         """The spectra at positions `idx` as a batch of their own (a shard that is not contiguous in the file: sharding.plan_mass_shards)."""
@@ -536,7 +544,8 @@ class RawBatch:
         gather = (np.repeat(starts - off[:-1].astype(np.int64), lens) + np.arange(int(off[-1]))) if len(idx) else np.zeros(0, np.int64)
         return RawBatch.from_arrays([self.ids[i] for i in idx], off, self.mz[gather], self.intensities[gather], self.precursor_mz[idx],
                                     self.precursor_charge[idx], self.isolation_lo[idx], self.isolation_hi[idx], self.scan_start_time[idx],
-                                    self.inverse_ion_mobility[idx], self.file_id[idx])
+                                    self.inverse_ion_mobility[idx], self.file_id[idx], self.ion_injection_time[idx],
+                                    [self.precursor_ref[i] for i in idx])
 
     def spectrum(self, i: int) -> RawSpectrum:
         lo, hi = int(self.peak_off[i]), int(self.peak_off[i + 1])
@@ -544,7 +553,7 @@ class RawBatch:
         ims = None if np.isnan(self.inverse_ion_mobility[i]) else float(self.inverse_ion_mobility[i])
         return RawSpectrum(self.mz[lo:hi], self.intensities[lo:hi], float(self.precursor_mz[i]),
                            int(self.precursor_charge[i]) or None, iso, float(self.scan_start_time[i]), ims, int(self.file_id[i]),
-                           self.ids[i])
+                           self.ids[i], float(self.ion_injection_time[i]), self.precursor_ref[i])
 
     def to_c(self):
         b = L.SageRawBatch()
@@ -949,4 +958,94 @@ def lfq(features: np.ndarray, order, aligned_rt, peptide_q, alignments: np.ndarr
     r.n_windows, r.n_contributions, r.passing = int(cout.n_windows), int(cout.n_contributions), int(cout.passing)
     r.stage_ms = {"build_ms": float(cout.build_ms), "ms1_ms": float(cout.ms1_ms), "trace_ms": float(cout.trace_ms),
                   "integrate_ms": float(cout.integrate_ms), "device_ms": float(cout.device_ms)}
+    return r
+
+
+# ---- TMT reporter-ion quantification (sage_hip_tmt) ----------------------------------------------------------------------------
+# tmt.rs:216-231, as f32
+TMT6PLEX = np.array([126.127726, 127.124761, 128.134436, 129.131471, 130.141145, 131.138180], dtype=np.float32)
+TMT11PLEX = np.array([126.127726, 127.124761, 127.131081, 128.128116, 128.134436, 129.131471, 129.137790, 130.134825,
+                      130.141145, 131.138180, 131.144499], dtype=np.float32)
+TMT18PLEX = np.array([126.127726, 127.124761, 127.131081, 128.128116, 128.134436, 129.131471, 129.137790, 130.134825,
+                      130.141145, 131.138180, 131.144500, 132.141535, 132.147855, 133.144890, 133.151210, 134.148245,
+                      134.154565, 135.15160], dtype=np.float32)
+ISOBARIC_VARIANTS = ("Tmt6", "Tmt10", "Tmt11", "Tmt16", "Tmt18", "User")
+
+
+@dataclass(frozen=True)
+class Isobaric:  # tmt.rs:13-61
+    kind: str                 # one of ISOBARIC_VARIANTS
+    user: Tuple[float, ...] = ()
+
+    def __post_init__(self):
+        if self.kind not in ISOBARIC_VARIANTS:
+            raise ValueError(f"unknown variant `{self.kind}`, expected one of " + ", ".join(f"`{v}`" for v in ISOBARIC_VARIANTS))
+
+    @staticmethod
+    def from_json(obj) -> "Isobaric":
+        """serde's externally tagged enum: "Tmt16" or {"User": [f32, ...]}."""
+        if isinstance(obj, str) and obj != "User":
+            return Isobaric(obj)
+        if isinstance(obj, dict) and len(obj) == 1:
+            (k, v), = obj.items()
+            if k == "User":
+                return Isobaric("User", tuple(float(np.float32(x)) for x in v))
+            return Isobaric(k)  # (raises, naming the variant)
+        raise ValueError(f"unknown variant `{json_text(obj)}`, expected one of " + ", ".join(f"`{v}`" for v in ISOBARIC_VARIANTS))
+
+    def reporter_masses(self) -> np.ndarray:
+        return {"Tmt6": TMT6PLEX, "Tmt10": TMT11PLEX[:10], "Tmt11": TMT11PLEX, "Tmt16": TMT18PLEX[:16], "Tmt18": TMT18PLEX,
+                "User": np.array(self.user, dtype=np.float32)}[self.kind].copy()
+
+    def modification_mass(self) -> Optional[float]:
+        return {"Tmt6": 229.162932, "Tmt10": 229.162932, "Tmt11": 229.162932, "Tmt16": 304.2071, "Tmt18": 304.2135,
+                "User": None}[self.kind]
+
+    def headers(self) -> List[str]:
+        stem = "user" if self.kind == "User" else "tmt"
+        return [f"{stem}_{i + 1}" for i in range(len(self.reporter_masses()))]
+
+    def min_deisotope_mz(self) -> float:
+        """runner.rs:398-403 at level 2: reporter_masses().last() * (1.0 + 20E-6) in f32 (last, not max); 0.0 without labels"""
+        m = self.reporter_masses()
+        return float(m[-1] * (np.float32(1.0) + np.float32(20e-6))) if len(m) else 0.0
+
+
+def json_text(obj) -> str:
+    import json
+    return obj if isinstance(obj, str) else json.dumps(obj)
+
+
+@dataclass
+class TmtSettings:  # input.rs:136-160 (TmtSettings::default)
+    level: int = 3
+    sn: bool = False
+
+
+@dataclass
+class TmtResult:
+    """intensity / peak_index: [n_spectra, n_labels], spectra in the order of the batches; peak_index -1 == None."""
+    intensity: np.ndarray
+    peak_index: np.ndarray
+    stage_ms: dict
+
+
+def tmt(batches: Sequence[RawBatch], isobaric, level: int, take_top_n: int = 150, deisotope: bool = True,
+        min_deisotope_mz: float = 0.0, tolerance: Optional[Tolerance] = None, device: int = 0) -> TmtResult:
+    """tmt::quantify's reporter intensities (tmt.rs:314-352) on the device for the spectra of `batches` (the spectra of MS level
+    `level`; at level 2 they are first processed with SpectrumProcessor(take_top_n, deisotope, min_deisotope_mz), min_peaks 0).
+    isobaric: an Isobaric or the label m/z themselves.  tolerance: default Ppm(-20, 20), as the CLI (runner.rs:350)."""
+    labels = np.ascontiguousarray(isobaric.reporter_masses() if isinstance(isobaric, Isobaric) else isobaric, dtype=np.float32)
+    tol = tolerance or Tolerance("ppm", -20.0, 20.0)
+    n = sum(b.n for b in batches)
+    nl = len(labels)
+    r = TmtResult(np.zeros((n, nl), np.float32), np.full((n, nl), -1, np.int32), {})
+    cb = [b.to_c() for b in batches]
+    arr = (L.SageRawBatch * max(len(cb), 1))(*cb)
+    cin = L.SageTmtInput(len(cb), arr, int(level), nl, L.as_ptr(labels, C.c_float), tol.to_c(), int(take_top_n), int(bool(deisotope)),
+                         float(min_deisotope_mz))
+    cout = L.SageTmtOutput(L.as_ptr(r.intensity, C.c_float), L.as_ptr(r.peak_index, C.c_int32))
+    L.check(L.load().sage_hip_tmt(device, C.byref(cin), C.byref(cout)))
+    r.stage_ms = {"upload_ms": float(cout.upload_ms), "process_ms": float(cout.process_ms), "extract_ms": float(cout.extract_ms),
+                  "device_ms": float(cout.device_ms)}
     return r

@@ -7,9 +7,10 @@ crates/sage-cli/src/input.rs (Input -> Search, :298-385; `database` = sage-core 
 flow of runner.rs (read mzML -> SpectrumProcessor::process -> keep MS2 with >= min_peaks peaks -> Scorer::score,
 :311-325, :398-461) and the `results.sage.tsv` / `matched_fragments.sage.tsv` writers (:687-935).  Everything downstream
 of Scorer::score is limited to the LDA rescoring, q-values and picked peptide / protein FDR (runner.rs:536-541, on the
-device: rescore.hip), label-free MS1 quantification when `quant.lfq` is true (runner.rs:562-575, lfq.hip: `lfq.tsv`) and the
-optional percolator .pin file; protein grouping, TMT, parquet, cloud IO are out of scope and their columns carry the defaults a Feature is born with (scoring.rs:576-592).  The search itself runs on the GPU through
-libsage_hip.so; there is no CPU fallback.
+device: rescore.hip), label-free MS1 quantification when `quant.lfq` is true (runner.rs:562-575, lfq.hip: `lfq.tsv`),
+isobaric-tag (TMT) reporter-ion quantification when `quant.tmt` is set (runner.rs:334-359, 398-410, tmt.hip: `tmt.tsv`) and
+the optional percolator .pin file; protein grouping, parquet, cloud IO are out of scope and their columns carry the defaults a
+Feature is born with (scoring.rs:576-592).  The search itself runs on the GPU through libsage_hip.so; there is no CPU fallback.
 """
 import argparse
 import json
@@ -21,8 +22,9 @@ import numpy as np
 
 from . import output
 from ._lib import FEATURE_DTYPE as L_FEATURE_DTYPE
-from .api import (LFQ_INTEGRATION, LFQ_SCORING, DatabaseParameters, DeviceDatabase, LfqSettings, RawBatch, Scorer, ScorerParams,
-                  SpectrumBatch, SpectrumProcessor, Tolerance, device_count, lfq, peptide_compositions, predict_rt, rescore)
+from .api import (LFQ_INTEGRATION, LFQ_SCORING, DatabaseParameters, DeviceDatabase, Isobaric, LfqSettings, RawBatch, Scorer,
+                  ScorerParams, SpectrumBatch, SpectrumProcessor, TmtSettings, Tolerance, device_count, lfq, peptide_compositions,
+                  predict_rt, rescore, tmt)
 from .mzml import read_mzml_native
 
 
@@ -79,6 +81,25 @@ def quant_settings(cfg: dict, log=print):
     return on, st
 
 
+def tmt_settings(cfg: dict, log=print):
+    """quant.tmt / quant.tmt_settings (input.rs:136-196): (Isobaric or None, TmtSettings).  `tmt` is the externally tagged
+    enum ("Tmt6" | "Tmt10" | "Tmt11" | "Tmt16" | "Tmt18" | {"User": [..]}); level defaults to 3, sn to false.  The level
+    warning of runner.rs:347-349 goes to `log`."""
+    q = cfg.get("quant") or {}
+    o = q.get("tmt_settings") or {}
+    d = TmtSettings()
+    st = TmtSettings(level=d.level if o.get("level") is None else int(o["level"]), sn=d.sn if o.get("sn") is None else bool(o["sn"]))
+    if q.get("tmt") is None:
+        return None, st
+    try:
+        iso = Isobaric.from_json(q["tmt"])
+    except ValueError as e:
+        raise SystemExit(f"quant.tmt: {e}")
+    if st.level not in (2, 3):
+        log(f"TMT quant level set at {st.level}, is this correct?")
+    return iso, st
+
+
 def scorer_params(sp: dict) -> ScorerParams:
     """The Scorer struct literal of runner.rs:492-508."""
     return ScorerParams(precursor_tol=sp["precursor_tol"], fragment_tol=sp["fragment_tol"],
@@ -101,15 +122,16 @@ def _upload(scorer, processor, raw, sp, host_preprocess, positions=False):
         out = scorer.upload(SpectrumBatch.from_spectra([p for _, p in processed])), [p.id for _, p in processed]
         return out + (np.array([i for i, _ in processed], dtype=np.int64),) if positions else out
     # ... or on the device: raw peaks in, PSMs out; spectra below min_peaks stay in the batch with zero peaks
-    dbatch, _ = scorer.process_upload(raw, sp["max_peaks"], sp["deisotope"], 0.0, sp["min_peaks"])
+    dbatch, _ = scorer.process_upload(raw, sp["max_peaks"], sp["deisotope"], processor.min_deisotope_mz, sp["min_peaks"])
     return (dbatch, list(raw.ids), np.arange(raw.n, dtype=np.int64)) if positions else (dbatch, list(raw.ids))
 
 
-def prefilter_peptides(dbp, fasta_text, chunk, n_targets, sp, mzml_paths, processor, device, host_preprocess, log):
+def prefilter_peptides(dbp, fasta_text, chunk, n_targets, sp, mzml_paths, processor, device, host_preprocess, log, sn_level=None):
     """Runner::prefilter_peptides (runner.rs:143-238): search every spectrum against the FASTA one chunk of target proteins
     at a time with Scorer::quick_score, keep the peptides some spectrum picked, merge the survivors (reorder_peptides) and
-    leave build_from_peptides to the device.  The scorer of this pass reports one PSM more than the final one (runner.rs:190)."""
-    raws = [read_mzml_native(path, file_id=file_id, ms_level=2) for file_id, path in enumerate(mzml_paths)]
+    leave build_from_peptides to the device.  The scorer of this pass reports one PSM more than the final one (runner.rs:190).
+    sn_level: the MS2 intensities are divided by their noise (TMT `sn` at level 2; the pass reads as the search does)."""
+    raws = [read_mzml_native(path, file_id=file_id, ms_level=2, sn_level=sn_level) for file_id, path in enumerate(mzml_paths)]
     pass_params = scorer_params(dict(sp, report_psms=sp["report_psms"] + 1))
     chunks, keeps = [], []
     for chunk_id, first in enumerate(range(0, n_targets, chunk)):
@@ -258,6 +280,11 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         raise SystemExit("sage_amd.cli: no HIP device visible — libsage_hip has no CPU fallback")
     sp = search_parameters(cfg)
     lfq_on, lfq_settings = quant_settings(cfg, log)
+    isobaric, tmt_st = tmt_settings(cfg, log)
+    # runner.rs:391-410: S/N division at the quant level; at level 2 the reporter region is kept out of deisotoping
+    sn_level = tmt_st.level if (isobaric is not None and tmt_st.sn) else None
+    ms2_sn = sn_level if sn_level == 2 else None
+    cutoff = isobaric.min_deisotope_mz() if (isobaric is not None and tmt_st.level == 2) else 0.0
     if lfq_on and not sp["predict_rt"]:  # input.rs:309-316
         log("`predict_rt: false` and `lfq: true` are incompatible. Setting `predict_rt: true`")
         sp["predict_rt"] = True
@@ -274,14 +301,15 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     t0 = time.time()
     fasta_text = read_text(dbp.fasta)
     params = scorer_params(sp)
-    processor = SpectrumProcessor(sp["max_peaks"], sp["deisotope"], 0.0)  # (no TMT reporter cut-off: TMT is out of scope)
+    processor = SpectrumProcessor(sp["max_peaks"], sp["deisotope"], cutoff)
     host = None
     if dbp.prefilter:  # runner.rs:104-127
         chunk = dbp.auto_prefilter_chunk_size(fasta_text)
         n_targets = dbp.num_targets(fasta_text)
         if chunk < n_targets:
             log(f"using {(n_targets + chunk - 1) // chunk} db chunks of size {chunk}")
-            host = prefilter_peptides(dbp, fasta_text, chunk, n_targets, sp, mzml_paths, processor, device, host_preprocess, log)
+            host = prefilter_peptides(dbp, fasta_text, chunk, n_targets, sp, mzml_paths, processor, device, host_preprocess, log,
+                                      sn_level=ms2_sn)
     if host is None:
         host = dbp.build(fasta_text, peptides_only=True)  # digest / modify / sort / dedup on the host ...
     # ... build_from_peptides on the device (index_build.hip): the index is replicated on every device that searches
@@ -309,17 +337,21 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
 
     def read_file(file_id, path):
         t0 = time.time()
-        raw = read_mzml_native(path, file_id=file_id, ms_level=2, check_searchable=True)
+        raw = read_mzml_native(path, file_id=file_id, ms_level=2, check_searchable=True, sn_level=ms2_sn)
         ms1 = read_mzml_native(path, file_id=file_id, ms_level=1) if lfq_on else None  # (runner.rs:361-363: only for LFQ)
-        return raw, ms1, (time.time() - t0) * 1000.0
+        # TMT at a level other than 2 (SPS-MS3): that level's spectra (level 1 quantifies nothing: tmt.rs:330)
+        msn = (read_mzml_native(path, file_id=file_id, ms_level=tmt_st.level, sn_level=sn_level)
+               if isobaric is not None and tmt_st.level not in (1, 2) else None)
+        return raw, ms1, msn, (time.time() - t0) * 1000.0
 
     mzml_paths = list(mzml_paths)
     ms1_batches = []
+    tmt_parts, tmt_ms = [], 0.0  # per file: (file_id, spectrum ids, ion injection times, intensities[n, labels])
     reader = ThreadPoolExecutor(max_workers=1)
     ahead = reader.submit(read_file, 0, mzml_paths[0]) if mzml_paths else None
     for file_id, path in enumerate(mzml_paths):
         try:
-            raw, ms1, io_ms = ahead.result()
+            raw, ms1, msn, io_ms = ahead.result()
         except BaseException:
             reader.shutdown(wait=True)
             raise
@@ -327,6 +359,14 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         log(f"- file IO: {int(io_ms):8d} ms")
         if ms1 is not None and ms1.n:
             ms1_batches.append(ms1)
+        if isobaric is not None and tmt_st.level != 1:  # tmt::quantify per file, on the first device (runner.rs:334-359)
+            t0 = time.time()
+            q = raw if tmt_st.level == 2 else msn
+            if q.n:
+                res = tmt([q], isobaric, tmt_st.level, sp["max_peaks"], sp["deisotope"], cutoff, device=device)
+                tmt_parts.append((file_id, list(q.ids) if tmt_st.level == 2 else list(q.precursor_ref), q.ion_injection_time,
+                                  res.intensity))
+            tmt_ms += (time.time() - t0) * 1000.0
         if raw.n == 0:
             continue
         t0 = time.time()
@@ -427,6 +467,12 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         fp = os.path.join(output_directory, "matched_fragments.sage.tsv")
         output.write_fragments(fp, [r for i in order for r in frags[i]])
         paths.append(fp)
+    if tmt_parts:  # runner.rs:638-641: only when some spectrum was quantified
+        tp = os.path.join(output_directory, "tmt.tsv")
+        output.write_tmt_native(tp, isobaric.headers(), filenames, np.concatenate([np.full(len(p[1]), p[0], np.uint32) for p in tmt_parts]),
+                                [s for p in tmt_parts for s in p[1]], np.concatenate([p[2] for p in tmt_parts]),
+                                np.concatenate([p[3] for p in tmt_parts]))
+        paths.append(tp)
     if lfq_result is not None:  # runner.rs:643-647
         lp = os.path.join(output_directory, "lfq.tsv")
         output.write_lfq_native(lp, host, lfq_result, filenames)
@@ -439,10 +485,14 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     log(f"- writing: {int(stage_totals['write_ms']):8d} ms")
     if lfq_summary:
         stage_totals["lfq_ms"] = lfq_summary["lfq_ms"]
+    tmt_summary = {}
+    if isobaric is not None:
+        log(f"- TMT quantification: {int(tmt_ms):8d} ms")
+        tmt_summary = {"tmt_rows": sum(len(p[1]) for p in tmt_parts), "tmt_ms": tmt_ms}
     stage_totals["total_after_index_ms"] = (time.time() - t_run) * 1e3
     summary = {"version": "sage-hip 0.1 (search-and-score path of sage 0.15.0-beta.2)", "psms": len(flat),
                "spectra_searched": n_searched, "search_ms": search_ms, "stages": stage_totals, "output_paths": paths, **rescore_summary,
-               **lfq_summary}
+               **lfq_summary, **tmt_summary}
     with open(os.path.join(output_directory, "results.json"), "w") as fh:
         json.dump(dict(cfg, output_paths=paths, summary=summary), fh, indent=2, default=str)
     return summary

@@ -344,6 +344,19 @@ int sage_hip_write_lfq(const char* path, const SageHostDb* db, const SageLfqOutp
 }
 
 const char* sage_hip_last_error(void) { return g_last_error.c_str(); }
+int sage_hip_write_tmt(const char* path, const char* const* headers, uint32_t n_labels, uint64_t n_rows, const uint32_t* file_id,
+                       const char* const* spec_ids, const float* ion_injection_time, const float* intensity,
+                       const char* const* filenames, uint32_t n_files) {
+    if (!path || (n_labels && !headers) || (n_rows && (!file_id || !spec_ids || !ion_injection_time || (n_labels && !intensity))) ||
+        (n_files && !filenames))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_tmt: null argument");
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (file_id[r] >= n_files || !spec_ids[r]) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_tmt: file id out of range or null id");
+    std::string err;
+    if (!write_tmt(path, headers, n_labels, n_rows, file_id, spec_ids, ion_injection_time, intensity, filenames, n_files, err))
+        return fail(SAGE_HIP_ERR_INVALID, err);
+    return SAGE_HIP_OK;
+}
 int sage_hip_abi_version(void) { return SAGE_HIP_ABI_VERSION; }
 
 // ---------------------------------------------------------------------------------------------
@@ -429,11 +442,14 @@ struct SageMzml {
     MzmlRun run;
 };
 int sage_hip_mzml_read(const char* path, uint32_t file_id, int ms_level, SageMzml** out) {
+    return sage_hip_mzml_read_sn(path, file_id, ms_level, -1, out);
+}
+int sage_hip_mzml_read_sn(const char* path, uint32_t file_id, int ms_level, int sn_level, SageMzml** out) {
     if (!path || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mzml_read: null argument");
     auto h = std::make_unique<SageMzml>();
     std::string err;
     try {
-        if (!read_mzml(path, file_id, ms_level, h->run, err)) return fail(SAGE_HIP_ERR_INVALID, err);
+        if (!read_mzml(path, file_id, ms_level, sn_level, h->run, err)) return fail(SAGE_HIP_ERR_INVALID, err);
     } catch (const std::exception& e) {
         return fail(SAGE_HIP_ERR_INVALID, e.what());
     }
@@ -473,6 +489,14 @@ int sage_hip_mzml_view(const SageMzml* run, SageRawBatch* out) {
 const char* sage_hip_mzml_spectrum_id(const SageMzml* run, uint64_t i) {
     if (!run || i >= run->run.n()) return nullptr;
     return run->run.ids.data() + run->run.id_off[i];
+}
+float sage_hip_mzml_ion_injection_time(const SageMzml* run, uint64_t i) {
+    if (!run || i >= run->run.n()) return NAN;
+    return run->run.ion_injection_time[i];
+}
+const char* sage_hip_mzml_precursor_ref(const SageMzml* run, uint64_t i) {
+    if (!run || i >= run->run.n()) return nullptr;
+    return run->run.precursor_refs.data() + run->run.ref_off[i];
 }
 void sage_hip_mzml_free(SageMzml* run) { delete run; }
 int sage_hip_write_results(const char* path, int format, const SageHostDb* db, const SageFeature* features, uint64_t n,
@@ -1305,18 +1329,24 @@ int sage_hip_batch_upload(SageScorer* s, const SageSpectrumBatch* b, SageDeviceB
     return SAGE_HIP_OK;
 }
 
-int sage_hip_batch_process_upload(SageScorer* s, const SageRawBatch* raw, uint64_t take_top_n, int deisotope,
-                                  float min_deisotope_mz, uint32_t min_peaks, SageDeviceBatch** out, uint32_t* out_npeaks) {
-    if (!s || !raw || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+// SpectrumProcessor::process (spectrum.rs:279-412) of every spectrum of `raw` on the device: process_kernel (the LDS instance up
+// to 2 048 raw peaks, the global-workspace instance beyond) and the compaction into ProcessedSpectrum arrays, enqueued on
+// `stream`.  Spectra that keep fewer than min_peaks peaks are left with zero.  counts: the peaks each spectrum kept before
+// that filter; off: the offsets of peak_off.  `w` holds the inputs and intermediates until the caller's stream is done with
+// them.  What sage_hip_batch_process_upload and sage_hip_tmt share.
+struct ProcessScratch {
+    DevBuf<uint64_t> raw_off;
+    DevBuf<float> raw_mz, raw_int, sm, si;
+    DevBuf<uint8_t> zbuf;
+    DevBuf<uint32_t> cnt, big_list;
+    DevBuf<unsigned char> big_ws;
+};
+static int process_raw_on_device(const SageRawBatch* raw, uint64_t take_top_n, int deisotope, float min_deisotope_mz,
+                                 uint32_t min_peaks, hipStream_t stream, ProcessScratch& w, DevBuf<uint64_t>& peak_off,
+                                 DevBuf<float>& masses, DevBuf<float>& intensities, DevBuf<float>& tic,
+                                 std::vector<uint32_t>& counts, std::vector<uint64_t>& off) {
     const uint32_t n = raw->n_spectra;
-    if (n && (!raw->peak_off || !raw->precursor_mz || !raw->precursor_charge))
-        return fail(SAGE_HIP_ERR_INVALID, "missing required spectrum arrays");
     if (take_top_n == 0 || take_top_n > 0xFFFFu) return fail(SAGE_HIP_ERR_INVALID, "take_top_n must be in [1, 65535]");
-    std::lock_guard<std::mutex> lock(s->mu);
-    HIP_TRY(hipSetDevice(s->db->device));
-    auto d = std::make_unique<SageDeviceBatch>();
-    d->device = s->db->device;
-    HIP_TRY(d->up_done.create(false));
     const uint64_t total = n ? raw->peak_off[n] : 0;
     uint32_t rcap = 1;
     for (uint32_t i = 0; i < n; i++) {
@@ -1338,23 +1368,17 @@ int sage_hip_batch_process_upload(SageScorer* s, const SageRawBatch* raw, uint64
     while (rpow2 < rcap) rpow2 <<= 1;
     HIP_TRY((hipError_t)process_kernel_prepare(160 * 1024));
     const uint32_t stride = (uint32_t)std::min<uint64_t>(take_top_n, big_cap);
-    DevBuf<uint64_t> raw_off;
-    DevBuf<float> raw_mz, raw_int, sm, si;
-    DevBuf<uint8_t> zbuf;
-    DevBuf<uint32_t> cnt;
-    HIP_TRY(raw_off.upload(raw->peak_off, n ? (size_t)n + 1 : 0));
-    HIP_TRY(raw_mz.upload(raw->mz, total));
-    HIP_TRY(raw_int.upload(raw->intensities, total));
-    HIP_TRY(zbuf.upload(raw->precursor_charge, n));
-    HIP_TRY(sm.alloc((size_t)n * stride));
-    HIP_TRY(si.alloc((size_t)n * stride));
-    HIP_TRY(cnt.alloc(n));
-    HIP_TRY(d->tic.alloc(n));
-    launch_process(n, raw_off.p, raw_mz.p, raw_int.p, zbuf.p, (uint32_t)take_top_n, deisotope != 0, min_deisotope_mz, rcap, rpow2,
-                   stride, sm.p, si.p, d->tic.p, cnt.p, s->stream);
+    HIP_TRY(w.raw_off.upload(raw->peak_off, n ? (size_t)n + 1 : 0));
+    HIP_TRY(w.raw_mz.upload(raw->mz, total));
+    HIP_TRY(w.raw_int.upload(raw->intensities, total));
+    HIP_TRY(w.zbuf.upload(raw->precursor_charge, n));
+    HIP_TRY(w.sm.alloc((size_t)n * stride));
+    HIP_TRY(w.si.alloc((size_t)n * stride));
+    HIP_TRY(w.cnt.alloc(n));
+    HIP_TRY(tic.alloc(n));
+    launch_process(n, w.raw_off.p, w.raw_mz.p, w.raw_int.p, w.zbuf.p, (uint32_t)take_top_n, deisotope != 0, min_deisotope_mz, rcap, rpow2,
+                   stride, w.sm.p, w.si.p, tic.p, w.cnt.p, stream);
     HIP_TRY(hipGetLastError());
-    DevBuf<uint32_t> big_list;
-    DevBuf<unsigned char> big_ws;
     if (!big.empty()) {
         // Groups of similar size, each with slices sized for ITS largest spectrum, launched one after the other over one
         // workspace of bounded size (stream order makes the reuse safe): a batch with one 50 000-peak outlier among thousands of
@@ -1391,38 +1415,59 @@ int sage_hip_batch_process_upload(SageScorer* s, const SageRawBatch* raw, uint64
         }
         size_t ws_bytes = 0;
         for (const Group& g : groups) ws_bytes = std::max(ws_bytes, g.count * g.slice);
-        HIP_TRY(big_list.upload(big.data(), big.size()));
-        if (hipError_t e = big_ws.alloc(ws_bytes); e != hipSuccess) {
+        HIP_TRY(w.big_list.upload(big.data(), big.size()));
+        if (hipError_t e = w.big_ws.alloc(ws_bytes); e != hipSuccess) {
             (void)hipGetLastError();
             return fail(e == hipErrorOutOfMemory ? SAGE_HIP_ERR_OOM : SAGE_HIP_ERR_HIP,
                         "preprocessing workspace of " + std::to_string(ws_bytes >> 20) + " MiB for a spectrum of " + std::to_string(big_cap) +
                             " raw peaks: " + hipGetErrorString(e) + " (sage_hip_process_ms2 preprocesses a spectrum on the host)");
         }
         for (const Group& g : groups) {
-            launch_process_big((uint32_t)g.count, big_list.p + g.first, big_ws.p, raw_off.p, raw_mz.p, raw_int.p, zbuf.p, (uint32_t)take_top_n,
-                               deisotope != 0, min_deisotope_mz, g.cap, g.pow2, stride, sm.p, si.p, d->tic.p, cnt.p, s->stream);
+            launch_process_big((uint32_t)g.count, w.big_list.p + g.first, w.big_ws.p, w.raw_off.p, w.raw_mz.p, w.raw_int.p, w.zbuf.p, (uint32_t)take_top_n,
+                               deisotope != 0, min_deisotope_mz, g.cap, g.pow2, stride, w.sm.p, w.si.p, tic.p, w.cnt.p, stream);
             HIP_TRY(hipGetLastError());
         }
     }
-    std::vector<uint32_t> counts(n);
-    HIP_TRY(hipMemcpyAsync(counts.data(), cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    counts.assign(n, 0);
+    HIP_TRY(hipMemcpyAsync(counts.data(), w.cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    off.assign((size_t)n + 1, 0);
+    for (uint32_t i = 0; i < n; i++) off[i + 1] = off[i] + (counts[i] >= min_peaks ? counts[i] : 0);  // runner.rs:313
+    HIP_TRY(peak_off.upload(off.data(), n ? (size_t)n + 1 : 0));
+    HIP_TRY(masses.alloc(off[n]));
+    HIP_TRY(intensities.alloc(off[n]));
+    launch_compact(n, peak_off.p, stride, w.sm.p, w.si.p, masses.p, intensities.p, stream);
+    HIP_TRY(hipGetLastError());
+    return SAGE_HIP_OK;
+}
+
+int sage_hip_batch_process_upload(SageScorer* s, const SageRawBatch* raw, uint64_t take_top_n, int deisotope,
+                                  float min_deisotope_mz, uint32_t min_peaks, SageDeviceBatch** out, uint32_t* out_npeaks) {
+    if (!s || !raw || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+    const uint32_t n = raw->n_spectra;
+    if (n && (!raw->peak_off || !raw->precursor_mz || !raw->precursor_charge))
+        return fail(SAGE_HIP_ERR_INVALID, "missing required spectrum arrays");
+    if (take_top_n == 0 || take_top_n > 0xFFFFu) return fail(SAGE_HIP_ERR_INVALID, "take_top_n must be in [1, 65535]");
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->db->device));
+    auto d = std::make_unique<SageDeviceBatch>();
+    d->device = s->db->device;
+    HIP_TRY(d->up_done.create(false));
+    ProcessScratch w;
+    std::vector<uint32_t> counts;
+    std::vector<uint64_t> off;
+    if (int rc = process_raw_on_device(raw, take_top_n, deisotope, min_deisotope_mz, min_peaks, s->stream, w, d->peak_off, d->masses,
+                                       d->intensities, d->tic, counts, off);
+        rc != SAGE_HIP_OK)
+        return rc;
     if (out_npeaks) std::copy(counts.begin(), counts.end(), out_npeaks);
-    std::vector<uint64_t> off((size_t)n + 1, 0);
     uint32_t pcap = 1, zmax = 0;
     bool any_unknown = false;
     for (uint32_t i = 0; i < n; i++) {
-        const uint32_t c = counts[i] >= min_peaks ? counts[i] : 0;  // runner.rs:313: too few peaks -> not searched
-        off[i + 1] = off[i] + c;
-        pcap = std::max(pcap, c);
+        pcap = std::max(pcap, (uint32_t)(off[i + 1] - off[i]));
         zmax = std::max<uint32_t>(zmax, raw->precursor_charge[i]);
         any_unknown = any_unknown || raw->precursor_charge[i] == 0;
     }
-    HIP_TRY(d->peak_off.upload(off.data(), n ? (size_t)n + 1 : 0));
-    HIP_TRY(d->masses.alloc(off[n]));
-    HIP_TRY(d->intensities.alloc(off[n]));
-    launch_compact(n, d->peak_off.p, stride, sm.p, si.p, d->masses.p, d->intensities.p, s->stream);
-    HIP_TRY(hipGetLastError());
     // precursor-side arrays and the launch schedule
     d->n = n;
     HIP_TRY(d->precursor_mz.upload(raw->precursor_mz, n));
@@ -1486,6 +1531,106 @@ int sage_hip_batch_download(SageDeviceBatch* b, uint64_t* peak_off, float* masse
     if (masses && total) HIP_TRY(hipMemcpy(masses, b->view.masses, total * 4, hipMemcpyDeviceToHost));
     if (intensities && total) HIP_TRY(hipMemcpy(intensities, b->view.intensities, total * 4, hipMemcpyDeviceToHost));
     if (tic && b->n) HIP_TRY(hipMemcpy(tic, b->view.tic, (size_t)b->n * 4, hipMemcpyDeviceToHost));
+    return SAGE_HIP_OK;
+}
+
+// ---- TMT reporter ions (sage tmt.rs:314-352 quantify, minus the host-side row fields) ----------------------------------------
+int sage_hip_tmt(int device, const SageTmtInput* in, SageTmtOutput* out) {
+    if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null argument");
+    if (sage_hip_device_count() <= 0) return fail(SAGE_HIP_ERR_NO_DEVICE, "sage_hip_tmt: no HIP device (there is no CPU fallback)");
+    if ((in->n_batches && !in->batches) || (in->n_labels && !in->labels))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null array");
+    if (in->tolerance.kind < 0 || in->tolerance.kind > 2) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: unknown tolerance kind");
+    const bool ms2 = in->level == 2;
+    const uint32_t L = in->n_labels;
+    uint64_t n_total = 0;
+    for (uint32_t b = 0; b < in->n_batches; ++b) {
+        const SageRawBatch& r = in->batches[b];
+        if (!r.n_spectra) continue;
+        if (!r.peak_off || (ms2 && !r.precursor_charge)) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null spectrum array");
+        for (uint32_t i = 0; i < r.n_spectra; ++i) {
+            if (r.peak_off[i + 1] < r.peak_off[i]) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: peak_off is not monotone");
+            if (r.peak_off[i + 1] - r.peak_off[i] > (uint64_t)INT32_MAX)
+                return fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_tmt: a spectrum of more than 2^31 - 1 peaks (peak_index is i32)");
+        }
+        if (r.peak_off[r.n_spectra] && (!r.mz || !r.intensities)) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: missing peak arrays");
+        n_total += r.n_spectra;
+    }
+    if (n_total && L && !out->intensity) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null output array");
+    out->upload_ms = out->process_ms = out->extract_ms = out->device_ms = 0.0f;
+    if (!n_total || !L) return SAGE_HIP_OK;
+    // each label's window in f32 on the host: Tolerance::bounds, then + offset (-PROTON); the region is their union's hull
+    const sagecore::Tol tol{in->tolerance.kind, in->tolerance.lo, in->tolerance.hi};
+    std::vector<float> lo(L), hi(L);
+    float region_lo = INFINITY, region_hi = -INFINITY;
+    for (uint32_t k = 0; k < L; ++k) {
+        sagecore::offset_bounds(tol, in->labels[k], -sagecore::PROTON, lo[k], hi[k]);
+        if (lo[k] < region_lo) region_lo = lo[k];
+        if (hi[k] > region_hi) region_hi = hi[k];
+    }
+    HIP_TRY(hipSetDevice(device));
+    struct Stream {
+        hipStream_t s = nullptr;
+        hipEvent_t e[4] = {};
+        ~Stream() {
+            for (hipEvent_t x : e)
+                if (x) (void)hipEventDestroy(x);
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } cx;
+    HIP_TRY(hipStreamCreateWithFlags(&cx.s, hipStreamNonBlocking));
+    for (auto& e : cx.e) HIP_TRY(hipEventCreate(&e));
+    DevBuf<float> dlo, dhi, dint;
+    DevBuf<int32_t> didx;
+    HIP_TRY(dlo.upload(lo.data(), L));
+    HIP_TRY(dhi.upload(hi.data(), L));
+    uint64_t row = 0;
+    for (uint32_t b = 0; b < in->n_batches; ++b) {
+        const SageRawBatch& r = in->batches[b];
+        const uint32_t n = r.n_spectra;
+        if (!n) continue;
+        const uint64_t total = r.peak_off[n], cells = (uint64_t)n * L;
+        HIP_TRY(dint.reserve(cells));
+        if (out->peak_index) HIP_TRY(didx.reserve(cells));
+        HIP_TRY(hipEventRecord(cx.e[0], cx.s));
+        ProcessScratch w;
+        DevBuf<uint64_t> poff;
+        DevBuf<float> pm, pi, tic;
+        if (ms2) {  // the search's own preprocessing (min_peaks 0: every spectrum is quantified, runner.rs:334-359)
+            std::vector<uint32_t> counts;
+            std::vector<uint64_t> off;
+            if (int rc = process_raw_on_device(&r, in->take_top_n, in->deisotope, in->min_deisotope_mz, 0, cx.s, w, poff, pm, pi, tic,
+                                               counts, off);
+                rc != SAGE_HIP_OK)
+                return rc;
+        } else {    // mass = mz - PROTON in the kernel; the raw peaks as given
+            HIP_TRY(poff.alloc((size_t)n + 1));
+            HIP_TRY(pm.alloc(total));
+            HIP_TRY(pi.alloc(total));
+            HIP_TRY(hipMemcpyAsync(poff.p, r.peak_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, cx.s));
+            if (total) {
+                HIP_TRY(hipMemcpyAsync(pm.p, r.mz, total * 4, hipMemcpyHostToDevice, cx.s));
+                HIP_TRY(hipMemcpyAsync(pi.p, r.intensities, total * 4, hipMemcpyHostToDevice, cx.s));
+            }
+        }
+        HIP_TRY(hipEventRecord(cx.e[1], cx.s));
+        launch_tmt_extract(n, poff.p, pm.p, pi.p, !ms2, dlo.p, dhi.p, L, region_lo, region_hi, dint.p,
+                           out->peak_index ? didx.p : nullptr, cx.s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(cx.e[2], cx.s));
+        HIP_TRY(hipMemcpyAsync(out->intensity + row * L, dint.p, cells * 4, hipMemcpyDeviceToHost, cx.s));
+        if (out->peak_index) HIP_TRY(hipMemcpyAsync(out->peak_index + row * L, didx.p, cells * 4, hipMemcpyDeviceToHost, cx.s));
+        HIP_TRY(hipEventRecord(cx.e[3], cx.s));
+        HIP_TRY(hipStreamSynchronize(cx.s));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, cx.e[0], cx.e[1]));
+        (ms2 ? out->process_ms : out->upload_ms) += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, cx.e[1], cx.e[2]));
+        out->extract_ms += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, cx.e[0], cx.e[3]));
+        out->device_ms += ms;
+        row += n;
+    }
     return SAGE_HIP_OK;
 }
 

@@ -315,6 +315,42 @@ SAGE_HD int select_most_intense_peak(const float* masses, const float* intensiti
     return best;
 }
 
+// ---- select_most_intense_peak with Some(offset) (spectrum.rs:134-159): the bounds of `tol` around `center`, then the offset
+// added to each (f32), then the same search.  find_reporter_ions (tmt.rs:193-214) calls it with offset -PROTON; the
+// order-free device form is tmt.hip's.
+SAGE_HD void offset_bounds(const Tol& tol, float center, float offset, float& lo, float& hi) {
+    tol_bounds(tol, center, lo, hi);
+    lo = lo + offset;
+    hi = hi + offset;
+}
+SAGE_HD int select_most_intense_peak_offset(const float* masses, const float* intensities, uint32_t n, float center,
+                                            const Tol& tol, float offset) {
+    float lo, hi;
+    offset_bounds(tol, center, offset, lo, hi);
+    const int32_t klo = order_key(lo), khi = order_key(hi);
+    uint32_t a = 0, b = n;
+    while (a < b) {
+        uint32_t mid = (a + b) >> 1;
+        if (order_key(masses[mid]) < klo) a = mid + 1; else b = mid;
+    }
+    const uint32_t left = a ? a - 1 : 0;
+    a = left; b = n;
+    while (a < b) {
+        uint32_t mid = (a + b) >> 1;
+        if (order_key(masses[mid]) <= khi) a = mid + 1; else b = mid;
+    }
+    int best = -1;
+    float max_int = 0.0f;
+    for (uint32_t idx = left; idx < a; idx++) {
+        const float m = masses[idx];
+        if (m >= lo && m <= hi && intensities[idx] >= max_int) {
+            max_int = intensities[idx];
+            best = (int)idx;
+        }
+    }
+    return best;
+}
+
 // Same result as select_most_intense_peak, with the two partition points found in lock step
 // (`top` = pow2_floor(n)).  right = left + partition_point(slice[left..], <= hi) == max(left, #{m <= hi}).
 SAGE_HD int select_most_intense_peak_lockstep(const float* masses, const float* intensities, uint32_t n, uint32_t top,

@@ -275,6 +275,11 @@ int rescore_on_device(int device, const SageRescoreInput& in, SageRescoreOutput&
 int predict_rt_on_device(int device, const SageRtInput& in, SageRtOutput& out, std::string& err);
 // lfq.hip
 int lfq_on_device(int device, const SageLfqInput& in, SageLfqOutput& out, std::string& err);
+// tmt.hip: reporter-ion extraction, one wavefront per spectrum (peaks [off[i], off[i+1]); subtract_proton: the array holds raw
+// m/z); lo / hi: each label's window with the offset applied; region: [min lo, max hi].  out_*: [n * n_labels]
+void launch_tmt_extract(uint32_t n, const uint64_t* off, const float* mass_or_mz, const float* inten, bool subtract_proton,
+                        const float* lo, const float* hi, uint32_t n_labels, float region_lo, float region_hi, float* out_int,
+                        int32_t* out_idx, void* stream);
 // process.hip
 // launch schedule of a batch (index_build.hip): order[k] = spectrum scored by block k, ascending neutral precursor mass
 size_t schedule_temp_bytes(uint32_t n);

@@ -85,9 +85,12 @@ struct MzmlRun {
     std::vector<uint32_t> file_id;
     std::string ids;                 // NUL-separated spectrum ids
     std::vector<uint64_t> id_off;    // [n + 1] into ids
+    std::vector<float> ion_injection_time;  // MS:1000927, 0 when absent
+    std::string precursor_refs;      // NUL-separated spectrumRef of each kept precursor ("" when absent)
+    std::vector<uint64_t> ref_off{0};  // [n + 1] into precursor_refs
     uint64_t n() const { return precursor_mz.size(); }
 };
-bool read_mzml(const char* path, uint32_t file_id, int ms_level, MzmlRun& run, std::string& err);
+bool read_mzml(const char* path, uint32_t file_id, int ms_level, int sn_level, MzmlRun& run, std::string& err);
 
 // writers.cpp
 bool write_results(const char* path, int format, const HostDb& db, const SageFeature* f, uint64_t n, const uint64_t* order,
@@ -95,6 +98,9 @@ bool write_results(const char* path, int format, const HostDb& db, const SageFea
                    const SagePostColumns* post, std::string& err);
 bool write_lfq(const char* path, const HostDb& db, const SageLfqOutput& g, const uint64_t* rows, uint64_t n_rows,
                const char* const* filenames, uint32_t n_files, std::string& err);
+bool write_tmt(const char* path, const char* const* headers, uint32_t n_labels, uint64_t n_rows, const uint32_t* file_id,
+               const char* const* spec_ids, const float* ion_injection_time, const float* intensity, const char* const* filenames,
+               uint32_t n_files, std::string& err);
 
 // f32 residue masses, mass.rs:64-76
 float residue_mass(uint8_t aa);

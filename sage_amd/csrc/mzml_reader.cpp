@@ -10,7 +10,11 @@
 //     (MS:1000827, :221-229); isolation_window = Da(-lower, +upper) when both offsets are present (:354-357); a precursor is
 //     kept only if its m/z != 0 (:353); the path reads precursors.first();
 //   * scan start time in minutes (seconds / 60 in f32, :262-272); inverse reduced ion mobility (MS:1002815);
-//   * a spectrum whose total ion current cvParam is 0 is dropped (:205-213); the ms-level filter drops other levels.
+//   * a spectrum whose total ion current cvParam is 0 is dropped (:205-213); the ms-level filter drops other levels;
+//   * ion injection time (MS:1000927 under <scan>, :273) and the spectrumRef attribute of the kept precursor (:167-172);
+//   * signal-to-noise (sn_level >= 0, :371-381): at that MS level, intensity[i] /= noise[i] (MS:1002744) over the shorter of
+//     the two arrays.  Only the spectrum's OWN noise array divides it: the reference keeps an unused noise array across
+//     spectra and would divide a later spectrum that has none; a spectrum without one keeps its intensities.
 // No XML library: mzML's spectrum blocks are flat enough for a tag scanner (attributes in single or double quotes, the five
 // predefined entities in attribute values, namespace prefixes stripped).
 #include <zlib.h>
@@ -191,12 +195,14 @@ bool inflate_all(const std::vector<uint8_t>& in, std::vector<uint8_t>& out) {
 struct SpectrumOut {
     std::string id;
     std::vector<float> mz, inten;
-    float scan_start = 0.0f, prec_mz = 0.0f, prec_ims = NAN, iso_lo = NAN, iso_hi = NAN;
+    std::string precursor_ref;  // spectrumRef of the kept precursor ("" when absent)
+    float scan_start = 0.0f, prec_mz = 0.0f, prec_ims = NAN, iso_lo = NAN, iso_hi = NAN, ion_injection_time = 0.0f;
     uint8_t prec_charge = 0;
     bool have_precursor = false, have_lo = false, have_hi = false, centroid = false, keep = false;
     int level = 0;
 };
-bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, SpectrumOut& o, std::string& err, bool& unterminated) {
+bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, int sn_level, SpectrumOut& o, std::string& err,
+                    bool& unterminated) {
     std::vector<uint8_t> raw, plain;
     unterminated = false;
     std::string_view idv;
@@ -205,19 +211,21 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, Spectrum
     bool centroid = false;  // Representation::default() is Profile (spectrum.rs:119-124); MS:1000127 / MS:1000128 set it
     int level = 0, depth = 1;
     std::vector<float> mz, inten;
-    float scan_start = 0.0f, prec_mz = 0.0f, prec_ims = NAN, iso_lo = NAN, iso_hi = NAN;
+    float scan_start = 0.0f, prec_mz = 0.0f, prec_ims = NAN, iso_lo = NAN, iso_hi = NAN, ion_injection_time = 0.0f;
     uint8_t prec_charge = 0;
+    std::string prec_ref, p_ref;
     float p_mz = 0.0f, p_lo = NAN, p_hi = NAN;  // the precursor being read
     bool p_has_lo = false, p_has_hi = false, have_lo = false, have_hi = false;
     uint8_t p_z = 0;
     int precursor_depth = 0, scan_depth = 0, bda_depth = 0;
     bool bda_f32 = false, bda_zlib = false;
-    int bda_kind = 0;  // 1 m/z, 2 intensity
+    int bda_kind = 0;  // 1 m/z, 2 intensity, 3 noise
     std::string_view bda_text;
     struct Pending {
         std::string_view text;
         bool f32, zlib, set;
-    } pending[2] = {{std::string_view(), false, false, false}, {std::string_view(), false, false, false}};
+    } pending[3] = {{std::string_view(), false, false, false}, {std::string_view(), false, false, false},
+                    {std::string_view(), false, false, false}};
     bool closed = t.self_closing;
     while (!closed && next_tag(p, e, t)) {
         if (t.closing) {
@@ -233,6 +241,7 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, Spectrum
                     prec_charge = p_z;
                     iso_lo = p_lo;
                     iso_hi = p_hi;
+                    prec_ref.swap(p_ref);
                     have_lo = p_has_lo;
                     have_hi = p_has_hi;
                 }
@@ -281,12 +290,15 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, Spectrum
                             return false;
                         }
                         scan_start = v;
+                    } else if (acc == "MS:1000927") {
+                        ion_injection_time = parse_f32(val);
                     } else if (acc == "MS:1002815") {
                         prec_ims = parse_f32(val);
                     }
                 } else if (in_bda && child_depth == bda_depth + 1) {
                     if (acc == "MS:1000514") bda_kind = 1;
                     else if (acc == "MS:1000515" && bda_kind != 1) bda_kind = 2;
+                    else if (acc == "MS:1002744" && bda_kind == 0) bda_kind = 3;  // (noise only when neither of the above)
                     else if (acc == "MS:1000574") bda_zlib = true;
                     else if (acc == "MS:1000521") bda_f32 = true;
                 } else if (child_depth == 2) {  // direct children of <spectrum>
@@ -315,6 +327,8 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, Spectrum
                 p_z = 0;
                 p_lo = p_hi = NAN;
                 p_has_lo = p_has_hi = false;
+                std::string_view ref;
+                p_ref = attr(t.attrs, "spectrumRef", ref) ? unescape(ref) : std::string();
             }
         } else if (t.name == "binaryDataArray" && !in_bda) {
             if (!t.self_closing) {
@@ -342,7 +356,9 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, Spectrum
     o.keep = !(tic_zero || (ms_level >= 0 && (!have_level || level != ms_level)));
     o.id.swap(id);
     if (o.keep) {
-        for (int k = 0; k < 2; ++k) {
+        std::vector<float> noise;
+        const bool sn = sn_level >= 0 && have_level && level == sn_level;
+        for (int k = 0; k < (sn ? 3 : 2); ++k) {
             if (!pending[k].set) continue;
             base64_decode(pending[k].text, raw);
             const std::vector<uint8_t>* bytes = &raw;
@@ -353,7 +369,7 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, Spectrum
                 }
                 bytes = &plain;
             }
-            std::vector<float>& dst = k == 0 ? mz : inten;
+            std::vector<float>& dst = k == 0 ? mz : k == 1 ? inten : noise;
             if (pending[k].f32) {
                 dst.resize(bytes->size() / 4);
                 std::memcpy(dst.data(), bytes->data(), dst.size() * 4);
@@ -366,11 +382,15 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, Spectrum
                 }
             }
         }
+        const size_t n_sn = std::min(inten.size(), noise.size());  // (zipped: the shorter array decides)
+        for (size_t i = 0; i < n_sn; ++i) inten[i] /= noise[i];
         inten.resize(mz.size(), 0.0f);  // (a spectrum with arrays of different lengths is malformed; keep the peak table rectangular)
         o.mz.swap(mz);
         o.inten.swap(inten);
     }
     o.scan_start = scan_start;
+    o.ion_injection_time = ion_injection_time;
+    o.precursor_ref.swap(prec_ref);
     o.prec_mz = prec_mz;
     o.prec_ims = prec_ims;
     o.iso_lo = iso_lo;
@@ -386,8 +406,9 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, Spectrum
 
 }  // namespace
 
-// MzMLReader::with_file_id_and_level_filter(file_id, ms_level).parse(..): ms_level < 0 keeps every level
-bool read_mzml(const char* path, uint32_t file_id, int ms_level, MzmlRun& run, std::string& err) {
+// MzMLReader::with_file_id_and_level_filter(file_id, ms_level).set_signal_to_noise(sn_level).parse(..): ms_level < 0 keeps
+// every level, sn_level < 0 divides nothing
+bool read_mzml(const char* path, uint32_t file_id, int ms_level, int sn_level, MzmlRun& run, std::string& err) {
     FILE* fh = std::fopen(path, "rb");
     if (!fh) {
         err = std::string("cannot open ") + path;
@@ -522,7 +543,7 @@ bool read_mzml(const char* path, uint32_t file_id, int ms_level, MzmlRun& run, s
             const char* q = spans[i].begin;
             Tag t;
             bool unterminated = false;
-            if (!next_tag(q, spans[i].end, t) || !parse_spectrum(t, q, spans[i].end, ms_level, outs[i], errs[i], unterminated)) {
+            if (!next_tag(q, spans[i].end, t) || !parse_spectrum(t, q, spans[i].end, ms_level, sn_level, outs[i], errs[i], unterminated)) {
                 failed[i] = 1;
                 if (errs[i].empty()) errs[i] = "malformed mzML: unterminated <spectrum>";
             }
@@ -551,6 +572,7 @@ bool read_mzml(const char* path, uint32_t file_id, int ms_level, MzmlRun& run, s
     run.isolation_lo.resize(n_keep);
     run.isolation_hi.resize(n_keep);
     run.scan_start_time.resize(n_keep);
+    run.ion_injection_time.resize(n_keep);
     run.inverse_ion_mobility.resize(n_keep);
     run.file_id.assign(n_keep, file_id);
     run.centroid.resize(n_keep);
@@ -570,6 +592,7 @@ bool read_mzml(const char* path, uint32_t file_id, int ms_level, MzmlRun& run, s
             run.isolation_lo[j] = iso ? -o.iso_lo : NAN;
             run.isolation_hi[j] = iso ? o.iso_hi : NAN;
             run.scan_start_time[j] = o.scan_start;
+            run.ion_injection_time[j] = o.ion_injection_time;
             run.inverse_ion_mobility[j] = o.prec_ims;
             run.centroid[j] = o.centroid ? 1 : 0;
             run.has_precursor[j] = o.have_precursor ? 1 : 0;
@@ -580,10 +603,14 @@ bool read_mzml(const char* path, uint32_t file_id, int ms_level, MzmlRun& run, s
     });
     run.ids.reserve(id_bytes);
     run.id_off.reserve(n_keep + 1);
+    run.ref_off.reserve(n_keep + 1);
     for (size_t j = 0; j < n_keep; j++) {
         run.ids += outs[kept[j]].id;
         run.ids += '\0';
         run.id_off.push_back(run.ids.size());
+        run.precursor_refs += outs[kept[j]].precursor_ref;
+        run.precursor_refs += '\0';
+        run.ref_off.push_back(run.precursor_refs.size());
     }
     return true;
 }

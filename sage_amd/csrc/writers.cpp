@@ -288,4 +288,39 @@ bool write_lfq(const char* path, const HostDb& db, const SageLfqOutput& g, const
     return ok;
 }
 
+// write_tmt, runner.rs:1140-1180: one row per quantified spectrum in the order given; the spectrum id as written to
+// results.sage.tsv's scannr (as is), ion_injection_time and the reporter intensities as ryu f32.
+bool write_tmt(const char* path, const char* const* headers, uint32_t n_labels, uint64_t n_rows, const uint32_t* file_id,
+               const char* const* spec_ids, const float* ion_injection_time, const float* intensity, const char* const* filenames,
+               uint32_t n_files, std::string& err) {
+    (void)n_files;
+    FILE* fh = std::fopen(path, "wb");
+    if (!fh) {
+        err = std::string("cannot open ") + path;
+        return false;
+    }
+    std::string out = "filename\tscannr\tion_injection_time";
+    for (uint32_t k = 0; k < n_labels; ++k) {
+        out += '\t';
+        out += headers[k];
+    }
+    out += '\n';
+    bool ok = true;
+    for (uint64_t r = 0; r < n_rows && ok; ++r) {
+        str(out, filenames[file_id[r]]);
+        str(out, spec_ids[r]);
+        f32(out, ion_injection_time[r]);
+        for (uint32_t k = 0; k < n_labels; ++k) f32(out, intensity[r * n_labels + k]);
+        out.back() = '\n';
+        if (out.size() >= (1 << 20)) {
+            ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+            out.clear();
+        }
+    }
+    if (ok && !out.empty()) ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+    if (std::fclose(fh) != 0) ok = false;
+    if (!ok && err.empty()) err = std::string("write to ") + path + " failed";
+    return ok;
+}
+
 }  // namespace sagehip

@@ -1,4 +1,4 @@
-"""Synthetic multi-file LC-MS runs (MS1 + MS2) for label-free quantification.
+"""Synthetic multi-file LC-MS runs (MS1 + MS2) for label-free quantification, and SPS-MS3 runs for TMT quantification.
 
 Each file holds the same peptides eluting as Gaussians in retention time; every file has its own RT scale and shift.  MS1
 scans carry the peptides' Poisson isotope envelopes at charges 2..4 plus uniform noise centroids; MS2 scans near each
@@ -112,5 +112,73 @@ def write_lcms(directory: str, files: List[LcmsFile], stem: str = "run") -> List
     for f, lf in enumerate(files):
         path = os.path.join(directory, f"{stem}{f}.mzML")
         write_mzml(path, lf.spectra, lf.ms_levels)
+        paths.append(path)
+    return paths
+
+
+@dataclass
+class SpsFile:
+    spectra: List[RawSpectrum]  # in scan order: MS1, then per precursor an MS2 and its MS3
+    ms_levels: List[int]
+    noise: list                 # per spectrum: noise array or None
+    extra_precursors: list      # per spectrum: further SPS precursor m/z or None
+
+
+def synthetic_sps_ms3(db: IndexedDatabase, labels, n_files: int = 2, ms2_per_file: int = 60, seed: int = 0, ms1_every: int = 10,
+                      ms3_noise: int = 30, ms2_noise: int = 40, reporter_ppm: float = 4.0, noise_prob: float = 0.8,
+                      run_minutes: float = 30.0) -> List[SpsFile]:
+    """SPS-MS3 runs: every MS2 (b/y model of _ms2, searchable) is followed by an MS3 whose precursors are several of the MS2's
+    fragments (spectrumRef = the MS2's id).  The MS3 holds a cluster of reporter peaks near `labels` (some labels missing, some
+    with a close neighbour inside +-20 ppm), random noise peaks and, with probability noise_prob, a noise array (MS:1002744);
+    every MSn spectrum has an ion injection time.  An MS1 scan every ms1_every precursors.  All randomness: default_rng(seed)."""
+    rng = np.random.default_rng(seed)
+    labels = np.asarray(labels, dtype=np.float64)
+    targets = np.flatnonzero(db.decoy == 0)
+    files = []
+    for f in range(n_files):
+        spectra, levels, noise, extra = [], [], [], []
+        t = 0.0
+        peps = rng.choice(targets, size=ms2_per_file, replace=len(targets) < ms2_per_file)
+        for k, pep in enumerate(peps):
+            if k % ms1_every == 0:
+                mz = np.sort(rng.uniform(350.0, 1500.0, 50)).astype(np.float32)
+                spectra.append(RawSpectrum(mz, rng.lognormal(8.0, 1.0, 50).astype(np.float32), 0.0, None,
+                                           scan_start_time=float(np.float32(t)), file_id=f, id=f"scan={len(spectra) + 1}"))
+                levels.append(1), noise.append(None), extra.append(None)
+            t += run_minutes / (ms2_per_file * 2.2)
+            z = int(rng.choice([2, 3]))
+            mz, it, prec = _ms2(db, int(pep), z, rng, ms2_noise, 0.6, 2.0)
+            ms2_id = f"controllerType=0 controllerNumber=1 scan={len(spectra) + 1}"
+            iit2 = float(np.float32(rng.uniform(5.0, 50.0)))
+            spectra.append(RawSpectrum(mz, it, float(np.float32(prec)), z, None, scan_start_time=float(np.float32(t)), file_id=f,
+                                       id=ms2_id, ion_injection_time=iit2))
+            levels.append(2), noise.append(None), extra.append(None)
+            # the MS3: reporters (+ near neighbours) and noise, m/z ascending
+            present = rng.random(len(labels)) < 0.9
+            rep = labels[present] * (1.0 + rng.normal(0.0, reporter_ppm, present.sum()) * 1e-6)
+            near = labels[rng.random(len(labels)) < 0.2] * (1.0 + rng.uniform(-15.0, 15.0) * 1e-6)
+            rmz = np.concatenate([rep, near, rng.uniform(100.0, 1200.0, ms3_noise)])
+            rit = np.concatenate([rng.lognormal(9.0, 1.0, len(rep)), rng.lognormal(6.0, 1.0, len(near)),
+                                  rng.lognormal(6.5, 1.0, ms3_noise)])
+            o = np.argsort(rmz, kind="stable")
+            rmz, rit = rmz[o].astype(np.float32), rit[o].astype(np.float32)
+            sps = mz[rng.choice(len(mz), size=min(len(mz), 5), replace=False)] if len(mz) else np.zeros(0, np.float32)
+            spectra.append(RawSpectrum(rmz, rit, float(sps[0]) if len(sps) else float(np.float32(prec)), None, None,
+                                       scan_start_time=float(np.float32(t)), file_id=f, id=f"scan={len(spectra) + 1}",
+                                       ion_injection_time=float(np.float32(rng.uniform(20.0, 120.0))), precursor_ref=ms2_id))
+            levels.append(3)
+            noise.append(rng.uniform(50.0, 500.0, len(rmz)).astype(np.float32) if rng.random() < noise_prob else None)
+            extra.append([float(x) for x in sps[1:]])
+        files.append(SpsFile(spectra, levels, noise, extra))
+    return files
+
+
+def write_sps(directory: str, files: List[SpsFile], stem: str = "sps") -> List[str]:
+    from .mzml import write_mzml
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for f, sf in enumerate(files):
+        path = os.path.join(directory, f"{stem}{f}.mzML")
+        write_mzml(path, sf.spectra, sf.ms_levels, sf.noise, sf.extra_precursors)
         paths.append(path)
     return paths

@@ -8,7 +8,11 @@
     the fallback precursor m/z (MS:1000827, :221-229); isolation_window = Da(-lower, +upper) when both offsets are present
     (:354-357); a precursor is kept only if its m/z != 0 (:353);
   * scan start time in minutes (seconds are divided by 60 in f32, :262-272); inverse reduced ion mobility (MS:1002815);
-  * a spectrum whose total ion current cvParam is 0 is dropped (:205-213); an ms-level filter drops other levels.
+  * a spectrum whose total ion current cvParam is 0 is dropped (:205-213); an ms-level filter drops other levels;
+  * ion injection time (MS:1000927 under <scan>, :273); the spectrumRef attribute of the kept precursor (:167-172);
+  * signal-to-noise (`sn_level`, :371-381): at that MS level intensity[i] /= noise[i] (noise array MS:1002744, recognised
+    only when the array is neither m/z nor intensity) over the shorter of the two arrays, in f32.  Only the spectrum's own
+    noise array divides it; the reference would reuse an earlier spectrum's unused one.
 `write_mzml` is ours (the reference has no writer): centroid MS2 spectra with 32-bit zlib arrays like the reference's
 test fixture (tests/LQSRPAAPPAPGPGQLTLR.mzML:117-126), used to feed synthetic workloads through the CLI.
 """
@@ -16,6 +20,7 @@ import base64
 import struct
 import zlib
 import xml.etree.ElementTree as ET
+from xml.sax.saxutils import escape
 from decimal import Decimal, InvalidOperation
 from fractions import Fraction
 from typing import List, Optional
@@ -53,8 +58,9 @@ def _f32(text: str) -> float:
     return float(best)
 
 
-def read_mzml(path: str, file_id: int = 0, ms_level: Optional[int] = 2) -> List[RawSpectrum]:
-    """MzMLReader::with_file_id_and_level_filter(file_id, ms_level).parse(..) for the MSn spectra of one file."""
+def read_mzml(path: str, file_id: int = 0, ms_level: Optional[int] = 2, sn_level: Optional[int] = None) -> List[RawSpectrum]:
+    """MzMLReader::with_file_id_and_level_filter(file_id, ms_level).set_signal_to_noise(sn_level).parse(..) for the MSn
+    spectra of one file."""
     out: List[RawSpectrum] = []
     for _, el in ET.iterparse(path, events=("end",)):
         if _local(el.tag) != "spectrum":
@@ -73,7 +79,8 @@ def read_mzml(path: str, file_id: int = 0, ms_level: Optional[int] = 2) -> List[
             continue
         mz = np.zeros(0, _F32)
         inten = np.zeros(0, _F32)
-        scan_start = 0.0
+        noise = None
+        scan_start, iit, prec_ref = 0.0, 0.0, ""
         prec_mz, prec_charge, prec_ims = 0.0, None, None
         iso_lo = iso_hi = None
         have_precursor = False
@@ -92,10 +99,13 @@ def read_mzml(path: str, file_id: int = 0, ms_level: Optional[int] = 2) -> List[
                         elif unit != "UO:0000031":
                             raise ValueError("malformed mzML: scan start time unit")
                         scan_start = float(v)
+                    elif acc == "MS:1000927":
+                        iit = _f32(cv.attrib["value"])
                     elif acc == "MS:1002815":
                         prec_ims = _f32(cv.attrib["value"])
             elif t == "precursor" and not have_precursor:  # the path reads precursors.first()
                 p_mz, p_z, p_lo, p_hi = 0.0, None, None, None
+                p_ref = sub.attrib.get("spectrumRef", "")
                 for cv in sub.iter():
                     if _local(cv.tag) != "cvParam":
                         continue
@@ -119,11 +129,13 @@ def read_mzml(path: str, file_id: int = 0, ms_level: Optional[int] = 2) -> List[
                     have_precursor = True
                     prec_mz, prec_charge = p_mz, p_z
                     iso_lo, iso_hi = p_lo, p_hi
+                    prec_ref = p_ref
             elif t == "binaryDataArray":
                 accs = [cv.attrib.get("accession") for cv in sub if _local(cv.tag) == "cvParam"]
                 text = next((b.text for b in sub if _local(b.tag) == "binary"), None) or ""
-                kind = "mz" if "MS:1000514" in accs else "intensity" if "MS:1000515" in accs else None
-                if not text or kind is None:
+                kind = ("mz" if "MS:1000514" in accs else "intensity" if "MS:1000515" in accs else
+                        "noise" if "MS:1002744" in accs else None)
+                if not text or kind is None or (kind == "noise" and (sn_level is None or level != sn_level)):
                     continue
                 raw = base64.b64decode(text)
                 if "MS:1000574" in accs:
@@ -134,25 +146,39 @@ def read_mzml(path: str, file_id: int = 0, ms_level: Optional[int] = 2) -> List[
                     arr = np.frombuffer(raw[:len(raw) // 8 * 8], dtype="<f8").astype(_F32)
                 if kind == "mz":
                     mz = arr
-                else:
+                elif kind == "intensity":
                     inten = arr
+                else:
+                    noise = arr
+        if noise is not None and len(noise):
+            k = min(len(inten), len(noise))
+            inten = inten.copy()
+            with np.errstate(divide="ignore", invalid="ignore"):
+                inten[:k] = inten[:k] / noise[:k]
         iso = (-iso_lo, iso_hi) if (iso_lo is not None and iso_hi is not None) else None
-        out.append(RawSpectrum(mz, inten, prec_mz, prec_charge, iso, scan_start, prec_ims, file_id, el.attrib.get("id", "")))
+        out.append(RawSpectrum(mz, inten, prec_mz, prec_charge, iso, scan_start, prec_ims, file_id, el.attrib.get("id", ""), iit,
+                               prec_ref))
         el.clear()
     return out
 
 
-def read_mzml_native(path: str, file_id: int = 0, ms_level: Optional[int] = 2, check_searchable: bool = False):
+def read_mzml_native(path: str, file_id: int = 0, ms_level: Optional[int] = 2, check_searchable: bool = False,
+                     sn_level: Optional[int] = None):
     """The same reader in C++ (csrc/mzml_reader.cpp, sage_hip_mzml_read): one call per file, arrays straight into a RawBatch
     for Scorer.process_upload — no Python object per spectrum.  gzip-compressed files are inflated on the way in.
-    check_searchable: refuse what the reference refuses to search (profile-mode MS2 spectra, MS2 spectra without precursor)."""
+    check_searchable: refuse what the reference refuses to search (profile-mode MS2 spectra, MS2 spectra without precursor).
+    sn_level: divide the intensities of that MS level by their noise array (sage_hip_mzml_read_sn)."""
     import ctypes as C
 
     from . import _lib as L
     from .api import RawBatch
     lib = L.load()
     h = C.c_void_p()
-    L.check(lib.sage_hip_mzml_read(path.encode(), file_id, -1 if ms_level is None else int(ms_level), C.byref(h)))
+    level = -1 if ms_level is None else int(ms_level)
+    if sn_level is None:
+        L.check(lib.sage_hip_mzml_read(path.encode(), file_id, level, C.byref(h)))
+    else:
+        L.check(lib.sage_hip_mzml_read_sn(path.encode(), file_id, level, int(sn_level), C.byref(h)))
     try:
         if check_searchable:
             L.check(lib.sage_hip_mzml_check_searchable(h))
@@ -172,7 +198,9 @@ def read_mzml_native(path: str, file_id: int = 0, ms_level: Optional[int] = 2, c
                                     arr(v.precursor_mz, n, np.float32), arr(v.precursor_charge, n, np.uint8),
                                     arr(v.isolation_lo, n, np.float32), arr(v.isolation_hi, n, np.float32),
                                     arr(v.scan_start_time, n, np.float32), arr(v.inverse_ion_mobility, n, np.float32),
-                                    arr(v.file_id, n, np.uint32))
+                                    arr(v.file_id, n, np.uint32),
+                                    np.array([lib.sage_hip_mzml_ion_injection_time(h, i) for i in range(n)], dtype=np.float32),
+                                    [lib.sage_hip_mzml_precursor_ref(h, i).decode() for i in range(n)])
     finally:
         lib.sage_hip_mzml_free(h)
 
@@ -181,9 +209,12 @@ def _b64(arr: np.ndarray) -> str:
     return base64.b64encode(zlib.compress(np.ascontiguousarray(arr, dtype="<f4").tobytes())).decode()
 
 
-def write_mzml(path: str, spectra: List[RawSpectrum], ms_levels: Optional[List[int]] = None) -> None:
+def write_mzml(path: str, spectra: List[RawSpectrum], ms_levels: Optional[List[int]] = None, noise=None,
+               extra_precursors=None) -> None:
     """Centroid MS2 spectra, 32-bit zlib arrays, selected ion m/z / charge, isolation offsets, scan start time (minutes).
-    ms_levels: per spectrum (default 2); an `ms level` 1 spectrum is written without a precursor list."""
+    ms_levels: per spectrum (default 2); an `ms level` 1 spectrum is written without a precursor list.  A non-zero
+    ion_injection_time and a non-empty precursor_ref (spectrumRef) are written when set.  noise: per spectrum, a noise array
+    (MS:1002744) or None; extra_precursors: per spectrum, further precursor m/z (SPS-MS3) after the first, or None."""
     with open(path, "w") as f:
         f.write('<?xml version="1.0" encoding="utf-8"?>\n<mzML xmlns="http://psi.hupo.org/ms/mzml" version="1.1.0">\n')
         f.write(f'<run id="synthetic"><spectrumList count="{len(spectra)}">\n')
@@ -193,13 +224,20 @@ def write_mzml(path: str, spectra: List[RawSpectrum], ms_levels: Optional[List[i
             level = 2 if ms_levels is None else int(ms_levels[i])
             f.write(f'<cvParam cvRef="MS" accession="MS:1000511" name="ms level" value="{level}"/>\n')
             f.write('<cvParam cvRef="MS" accession="MS:1000127" name="centroid spectrum"/>\n')
+            iit = getattr(s, "ion_injection_time", 0.0)
+            iit_cv = (f'<cvParam cvRef="MS" accession="MS:1000927" name="ion injection time" '
+                      f'value="{np.format_float_positional(np.float32(iit), unique=True)}"/>' if iit else "")
             f.write(f'<scanList count="1"><scan><cvParam cvRef="MS" accession="MS:1000016" name="scan start time" '
                     f'value="{np.format_float_positional(np.float32(s.scan_start_time), unique=True)}" unitCvRef="UO" '
-                    f'unitAccession="UO:0000031" unitName="minute"/></scan></scanList>\n')
+                    f'unitAccession="UO:0000031" unitName="minute"/>{iit_cv}</scan></scanList>\n')
+            nz = None if noise is None else noise[i]
             if level == 1:
-                _write_arrays(f, s)
+                _write_arrays(f, s, nz)
                 continue
-            f.write('<precursorList count="1"><precursor>')
+            ref = getattr(s, "precursor_ref", "")
+            extra = [] if extra_precursors is None or extra_precursors[i] is None else list(extra_precursors[i])
+            ref_attr = f' spectrumRef="{escape(ref, {chr(34): "&quot;"})}"' if ref else ""
+            f.write(f'<precursorList count="{1 + len(extra)}"><precursor{ref_attr}>')
             if s.isolation_window is not None:
                 lo, hi = s.isolation_window
                 f.write('<isolationWindow>'
@@ -211,14 +249,22 @@ def write_mzml(path: str, spectra: List[RawSpectrum], ms_levels: Optional[List[i
                     f'<cvParam cvRef="MS" accession="MS:1000744" name="selected ion m/z" value="{np.format_float_positional(np.float32(s.precursor_mz), unique=True)}"/>')
             if s.precursor_charge:
                 f.write(f'<cvParam cvRef="MS" accession="MS:1000041" name="charge state" value="{int(s.precursor_charge)}"/>')
-            f.write('</selectedIon></selectedIonList></precursor></precursorList>\n')
-            _write_arrays(f, s)
+            f.write('</selectedIon></selectedIonList></precursor>')
+            for x in extra:
+                f.write(f'<precursor{ref_attr}><selectedIonList count="1"><selectedIon><cvParam cvRef="MS" accession="MS:1000744" '
+                        f'name="selected ion m/z" value="{np.format_float_positional(np.float32(x), unique=True)}"/>'
+                        '</selectedIon></selectedIonList></precursor>')
+            f.write('</precursorList>\n')
+            _write_arrays(f, s, nz)
         f.write('</spectrumList></run></mzML>\n')
 
 
-def _write_arrays(f, s) -> None:
-    f.write('<binaryDataArrayList count="2">')
-    for acc, name, arr in (("MS:1000514", "m/z array", s.mz), ("MS:1000515", "intensity array", s.intensity)):
+def _write_arrays(f, s, noise=None) -> None:
+    arrays = [("MS:1000514", "m/z array", s.mz), ("MS:1000515", "intensity array", s.intensity)]
+    if noise is not None:
+        arrays.append(("MS:1002744", "sampled noise intensity array", noise))
+    f.write(f'<binaryDataArrayList count="{len(arrays)}">')
+    for acc, name, arr in arrays:
         f.write('<binaryDataArray><cvParam cvRef="MS" accession="MS:1000521" name="32-bit float"/>'
                 '<cvParam cvRef="MS" accession="MS:1000574" name="zlib compression"/>'
                 f'<cvParam cvRef="MS" accession="{acc}" name="{name}"/><binary>{_b64(arr)}</binary></binaryDataArray>')

@@ -239,3 +239,38 @@ def write_lfq_native(path: str, db, result, filenames: Sequence[str], rows=None)
     names = (C.c_char_p * max(len(filenames), 1))(*[s.encode() for s in filenames])
     L.check(L.load().sage_hip_write_lfq(path.encode(), db._h, C.byref(cout), L.as_ptr(rows, C.c_uint64), len(rows), names,
                                         len(filenames)))
+
+
+TMT_HEADERS = ["filename", "scannr", "ion_injection_time"]
+
+
+def tmt_rows(filenames: Sequence[str], file_id, spec_ids, ion_injection_time, intensity) -> List[List[str]]:
+    """write_tmt (runner.rs:1140-1180): one row per quantified spectrum, in the order given; ryu f32 values."""
+    inten = np.asarray(intensity, dtype=np.float32).reshape(len(spec_ids), -1) if len(spec_ids) else []
+    return [[filenames[int(f)], s, ryu_f32(t)] + [ryu_f32(x) for x in row]
+            for f, s, t, row in zip(file_id, spec_ids, np.asarray(ion_injection_time, dtype=np.float32), inten)]
+
+
+def write_tmt(path: str, headers: Sequence[str], rows: Sequence[List[str]]) -> None:
+    with open(path, "w", newline="") as fh:
+        fh.write("\t".join(TMT_HEADERS + list(headers)) + "\n")
+        for r in rows:
+            fh.write("\t".join(r) + "\n")
+
+
+def write_tmt_native(path: str, headers: Sequence[str], filenames: Sequence[str], file_id, spec_ids, ion_injection_time,
+                     intensity) -> None:
+    """tmt.tsv through the C++ writer (sage_hip_write_tmt): the bytes of tmt_rows + write_tmt."""
+    import ctypes as C
+
+    from . import _lib as L
+    n = len(spec_ids)
+    fid = np.ascontiguousarray(file_id, dtype=np.uint32)
+    iit = np.ascontiguousarray(ion_injection_time, dtype=np.float32)
+    inten = np.ascontiguousarray(intensity, dtype=np.float32).reshape(-1)
+    assert len(fid) == n and len(iit) == n and len(inten) == n * len(headers)
+    hs = (C.c_char_p * max(len(headers), 1))(*[h.encode() for h in headers])
+    ids = (C.c_char_p * max(n, 1))(*[s.encode() for s in spec_ids])
+    names = (C.c_char_p * max(len(filenames), 1))(*[s.encode() for s in filenames])
+    L.check(L.load().sage_hip_write_tmt(path.encode(), hs, len(headers), n, L.as_ptr(fid, C.c_uint32), ids, L.as_ptr(iit, C.c_float),
+                                        L.as_ptr(inten, C.c_float), names, len(filenames)))
