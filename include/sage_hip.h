@@ -236,7 +236,8 @@ void sage_hip_batch_free(SageDeviceBatch* batch);
 int sage_hip_score_resident(SageScorer* scorer, SageDeviceBatch* batch, SageFeature* out, uint32_t* out_count);
 
 /* Raw centroided MS2 spectra (spectrum.rs:81-106 RawSpectrum + precursors[0]), SoA — the input of
- * SpectrumProcessor::process.  Same conventions as SageSpectrumBatch; mz ascending inside each spectrum. */
+ * SpectrumProcessor::process.  Same conventions as SageSpectrumBatch; peaks in any order (MGF keeps the file's order): like the
+ * reference (spectrum.rs:179-227, 279-335), preprocessing uses them as given, without sorting first. */
 typedef struct SageRawBatch {
     uint32_t n_spectra;
     const uint64_t* peak_off;          /* [n + 1] */
@@ -433,6 +434,41 @@ int sage_hip_mzml_read_sn(const char* path, uint32_t file_id, int ms_level, int 
 /* RawSpectrum.ion_injection_time (MS:1000927; 0 when absent) and precursors.first().spectrum_ref ("" when absent) */
 float sage_hip_mzml_ion_injection_time(const SageMzml* run, uint64_t i);
 const char* sage_hip_mzml_precursor_ref(const SageMzml* run, uint64_t i);
+
+/* ---- MGF input (host; sage-cloudpath/src/mgf.rs:325-369 MgfReader::with_file_id(file_id).parse, util.rs:107-118 read_mgf):
+ * every spectrum of a .mgf / .mgf.gz file as a SageMzml run (MS2, centroided, no ion mobility, injection time 0, no spectrumRef),
+ * read through sage_hip_mzml_view / _spectrum_id / _free.  The reference's rules, quirks included:
+ *   - the file-level TOL= / TOLU= / CHARGE= (before the first BEGIN IONS, :333-352) apply from the SECOND spectrum on: only the
+ *     init() at END IONS copies them in (:55-70, :316); state is reset only at END IONS, so lines between END IONS and the next
+ *     BEGIN IONS belong to the next spectrum (:185-196);
+ *   - peak lines (:276-299): unparsable m/z adds nothing, a missing intensity is 1.0, an unparsable one drops the spectrum;
+ *   - PEPMASS= (:198-221): first token the m/z (no token: 0; unparsable: no precursor); CHARGE= (:223-236): one charge per ASCII
+ *     digit; precursors[0] is the first PEPMASS with the first charge (:86-104);
+ *   - isolation window Da(-|TOL|, |TOL|) or Ppm(-|TOL|, |TOL|) for TOLU exactly `Da` / `ppm`, else None (:72-83) — the kind
+ *     is sage_hip_mzml_isolation_kinds; RTINSECONDS / 60 (:238-247); TITLE= is the spectrum id (:249-255);
+ *     TOL=NaN gives the bounds (+inf, -inf): an empty window, as the reference's NaN bounds match nothing, where NaN would read as None;
+ *   - check_spectrum (:115-128) drops spectra with an empty id, no precursor, no peaks or peak arrays of different lengths
+ *     (a message on stderr; the rest of the file is read);
+ *   - a file without BEGIN IONS (the reference panics), a missing file or text that is not UTF-8: SAGE_HIP_ERR_INVALID.
+ * Parsed in parallel pieces cut behind END IONS lines (SAGE_HIP_MGF_PIECE_KB, default 4096); spectra in file order. */
+int sage_hip_mgf_read(const char* path, uint32_t file_id, SageMzml** out);
+/* out[n]: the SAGE_TOL_* kind of each spectrum's isolation_lo / hi (mzML runs: SAGE_TOL_DA throughout) */
+int sage_hip_mzml_isolation_kinds(const SageMzml* run, uint8_t* out);
+/* out[n]: 1 where precursors[0].charge is Some(0) (MGF `CHARGE=0`), which SageRawBatch.precursor_charge == 0 cannot tell from
+ * None.  The reference then searches around mass 0 in a narrow search and reports no PSM (scoring.rs:439-443). */
+int sage_hip_mzml_charge_zero(const SageMzml* run, uint8_t* out);
+/* The upload and score entry points with the KIND of every spectrum's isolation window (mgf.rs:72-83: `TOLU=ppm` gives
+ * Tolerance::Ppm), which the isolation_lo / isolation_hi of SageSpectrumBatch / SageRawBatch do not carry: iso_kind[n] holds
+ * SAGE_TOL_PPM, SAGE_TOL_PCT or SAGE_TOL_DA (NULL: every window Da — exactly the entry points without `_kinds`).  Only the
+ * wide-window search reads the windows: `isolation_window * charge` (scoring.rs:427-431, mass.rs:47-57) for every kind. */
+int sage_hip_batch_upload_kinds(SageScorer* scorer, const SageSpectrumBatch* batch, const uint8_t* iso_kind, SageDeviceBatch** out);
+int sage_hip_batch_process_upload_kinds(SageScorer* scorer, const SageRawBatch* raw, const uint8_t* iso_kind, uint64_t take_top_n,
+                                        int deisotope, float min_deisotope_mz, uint32_t min_peaks, SageDeviceBatch** out,
+                                        uint32_t* out_npeaks);
+int sage_hip_score_batch_kinds(SageScorer* scorer, const SageSpectrumBatch* batch, const uint8_t* iso_kind, SageFeature* out,
+                               uint32_t* out_count);
+/* str::parse::<f32>() as the MGF reader applies it to `len` bytes at `token`: SAGE_HIP_OK and *out, or SAGE_HIP_ERR_INVALID */
+int sage_hip_parse_f32(const char* token, uint64_t len, float* out);
 
 /* ---- writers (host): results.sage.tsv / results.sage.pin, byte for byte as sage-cli/src/runner.rs:687-780, :830-905,
  * :938-1135 format them (itoa integers, ryu floats).  Arrays of SagePostColumns may be NULL: the Feature defaults of

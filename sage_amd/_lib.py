@@ -286,6 +286,10 @@ def load():
         "sage_hip_batch_process_upload": (C.c_int, [vp, C.POINTER(SageRawBatch), C.c_uint64, C.c_int, C.c_float, C.c_uint32,
                                                     C.POINTER(vp), c_u32_p]),
         "sage_hip_batch_download": (C.c_int, [vp, c_u64_p, c_float_p, c_float_p, c_float_p]),
+        "sage_hip_batch_upload_kinds": (C.c_int, [vp, C.POINTER(SageSpectrumBatch), c_u8_p, C.POINTER(vp)]),
+        "sage_hip_batch_process_upload_kinds": (C.c_int, [vp, C.POINTER(SageRawBatch), c_u8_p, C.c_uint64, C.c_int, C.c_float,
+                                                          C.c_uint32, C.POINTER(vp), c_u32_p]),
+        "sage_hip_score_batch_kinds": (C.c_int, [vp, C.POINTER(SageSpectrumBatch), c_u8_p, vp, c_u32_p]),
         "sage_hip_score_resident": (C.c_int, [vp, vp, vp, c_u32_p]),
         "sage_hip_initial_hits": (C.c_int, [vp, vp, c_u64_p, C.c_uint32, c_u32_p, c_u64_p, c_u64_p]),
         "sage_hip_last_timing": (C.c_int, [vp, C.POINTER(SageTiming)]),
@@ -307,6 +311,10 @@ def load():
         "sage_hip_mzml_read_sn": (C.c_int, [C.c_char_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(vp)]),
         "sage_hip_mzml_ion_injection_time": (C.c_float, [vp, C.c_uint64]),
         "sage_hip_mzml_precursor_ref": (C.c_char_p, [vp, C.c_uint64]),
+        "sage_hip_mgf_read": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(vp)]),
+        "sage_hip_mzml_isolation_kinds": (C.c_int, [vp, c_u8_p]),
+        "sage_hip_mzml_charge_zero": (C.c_int, [vp, c_u8_p]),
+        "sage_hip_parse_f32": (C.c_int, [C.c_char_p, C.c_uint64, c_float_p]),
         "sage_hip_tmt": (C.c_int, [C.c_int, C.POINTER(SageTmtInput), C.POINTER(SageTmtOutput)]),
         "sage_hip_write_tmt": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, c_u32_p, C.POINTER(C.c_char_p),
                                          c_float_p, c_float_p, C.POINTER(C.c_char_p), C.c_uint32]),
@@ -340,7 +348,8 @@ EXPORTED_SYMBOLS = [
     "sage_hip_hostdb_build_chunk", "sage_hip_hostdb_merge_kept", "sage_hip_predict_rt", "sage_hip_hostdb_feature_peptides",
     "sage_hip_write_results", "sage_hip_mzml_read", "sage_hip_mzml_view", "sage_hip_mzml_check_searchable", "sage_hip_mzml_spectrum_id", "sage_hip_mzml_free",
     "sage_hip_lfq", "sage_hip_write_lfq", "sage_hip_mzml_read_sn", "sage_hip_mzml_ion_injection_time", "sage_hip_mzml_precursor_ref",
-    "sage_hip_tmt", "sage_hip_write_tmt",
+    "sage_hip_tmt", "sage_hip_write_tmt", "sage_hip_mgf_read", "sage_hip_mzml_isolation_kinds", "sage_hip_mzml_charge_zero",
+    "sage_hip_parse_f32", "sage_hip_batch_upload_kinds", "sage_hip_batch_process_upload_kinds", "sage_hip_score_batch_kinds",
 ]
 
 

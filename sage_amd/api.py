@@ -571,8 +571,15 @@ class RawBatch:
         return b
 
 
+def _kinds(iso_kind, n: int) -> np.ndarray:
+    k = np.ascontiguousarray(iso_kind, dtype=np.uint8)
+    if len(k) != n or (k > 2).any():
+        raise ValueError("iso_kind: one Tolerance kind (0 ppm, 1 pct, 2 Da) per spectrum")
+    return k if n else np.zeros(1, np.uint8)
+
+
 class DeviceBatch:
-    def __init__(self, scorer: "Scorer", batch: Optional[SpectrumBatch], handle=None, n: int = 0):
+    def __init__(self, scorer: "Scorer", batch: Optional[SpectrumBatch], handle=None, n: int = 0, iso_kind=None):
         lib = L.load()
         self._keep = batch
         if handle is not None:  # adopted (Scorer.process_upload)
@@ -581,7 +588,11 @@ class DeviceBatch:
         self.n = batch.n
         self._h = C.c_void_p()
         cb = batch.to_c()
-        L.check(lib.sage_hip_batch_upload(scorer._h, C.byref(cb), C.byref(self._h)))
+        if iso_kind is None:
+            L.check(lib.sage_hip_batch_upload(scorer._h, C.byref(cb), C.byref(self._h)))
+        else:
+            kinds = _kinds(iso_kind, batch.n)
+            L.check(lib.sage_hip_batch_upload_kinds(scorer._h, C.byref(cb), L.as_ptr(kinds, C.c_uint8), C.byref(self._h)))
 
     def download(self):
         """(peak_off[n+1], masses, intensities, total_ion_current[n]) of the resident ProcessedSpectrum arrays."""
@@ -625,19 +636,28 @@ class Scorer:
         L.check(L.load().sage_hip_scorer_clone(self._h, C.byref(other._h)))
         return other
 
-    def upload(self, batch: SpectrumBatch) -> DeviceBatch:
-        return DeviceBatch(self, batch)
+    def upload(self, batch: SpectrumBatch, iso_kind=None) -> DeviceBatch:
+        """iso_kind: per-spectrum Tolerance kind of the isolation windows (0 ppm, 1 pct, 2 Da; None: all Da —
+        sage_hip_batch_upload_kinds)"""
+        return DeviceBatch(self, batch, iso_kind=iso_kind)
 
     def process_upload(self, raw: "RawBatch", take_top_n: int = 150, deisotope: bool = True, min_deisotope_mz: float = 0.0,
-                       min_peaks: int = 15):
+                       min_peaks: int = 15, iso_kind=None):
         """SpectrumProcessor::process (spectrum.rs:279-412) + the min_peaks filter of runner.rs:313 on the device; the
-        processed batch stays resident.  Returns (DeviceBatch, peaks kept per spectrum before the filter)."""
+        processed batch stays resident.  Returns (DeviceBatch, peaks kept per spectrum before the filter).
+        iso_kind: as for upload (sage_hip_batch_process_upload_kinds)."""
         lib = L.load()
         h = C.c_void_p()
         npk = np.zeros(max(raw.n, 1), dtype=np.uint32)
         cb = raw.to_c()
-        L.check(lib.sage_hip_batch_process_upload(self._h, C.byref(cb), take_top_n, int(deisotope), min_deisotope_mz, min_peaks,
-                                                  C.byref(h), L.as_ptr(npk, C.c_uint32)))
+        if iso_kind is None:
+            L.check(lib.sage_hip_batch_process_upload(self._h, C.byref(cb), take_top_n, int(deisotope), min_deisotope_mz, min_peaks,
+                                                      C.byref(h), L.as_ptr(npk, C.c_uint32)))
+        else:
+            kinds = _kinds(iso_kind, raw.n)
+            L.check(lib.sage_hip_batch_process_upload_kinds(self._h, C.byref(cb), L.as_ptr(kinds, C.c_uint8), take_top_n,
+                                                            int(deisotope), min_deisotope_mz, min_peaks, C.byref(h),
+                                                            L.as_ptr(npk, C.c_uint32)))
         return DeviceBatch(self, None, handle=h, n=raw.n), npk[:raw.n]
 
     def _alloc_out(self, n):
@@ -675,9 +695,10 @@ class Scorer:
                                             L.as_ptr(counts, C.c_uint32)))
         return feats.reshape(dbatch.n, self.params.report_psms), counts
 
-    def score(self, batch: SpectrumBatch, pinned_out: bool = True):
+    def score(self, batch: SpectrumBatch, pinned_out: bool = True, iso_kind=None):
         """Vec<Feature> per spectrum: returns (features[n, report_psms], counts[n]).  Host arrays in, host arrays out, through
-        the upload / score / download pipeline of sage_hip_score_batch.  pinned_out=False: plain (pageable) result arrays."""
+        the upload / score / download pipeline of sage_hip_score_batch.  pinned_out=False: plain (pageable) result arrays.
+        iso_kind: as for upload (sage_hip_score_batch_kinds)."""
         lib = L.load()
         if pinned_out:
             feats, counts = self._alloc_out(batch.n)
@@ -685,8 +706,13 @@ class Scorer:
             feats = np.zeros(batch.n * self.params.report_psms, dtype=L.FEATURE_DTYPE)
             counts = np.zeros(batch.n, dtype=np.uint32)
         cb = batch.to_c()
-        L.check(lib.sage_hip_score_batch(self._h, C.byref(cb), feats.ctypes.data_as(C.c_void_p),
-                                         L.as_ptr(counts, C.c_uint32)))
+        if iso_kind is None:
+            L.check(lib.sage_hip_score_batch(self._h, C.byref(cb), feats.ctypes.data_as(C.c_void_p),
+                                             L.as_ptr(counts, C.c_uint32)))
+        else:
+            kinds = _kinds(iso_kind, batch.n)
+            L.check(lib.sage_hip_score_batch_kinds(self._h, C.byref(cb), L.as_ptr(kinds, C.c_uint8), feats.ctypes.data_as(C.c_void_p),
+                                                   L.as_ptr(counts, C.c_uint32)))
         return feats.reshape(batch.n, self.params.report_psms), counts
 
     def annotate(self, dbatch: DeviceBatch, feats: np.ndarray, counts: np.ndarray):

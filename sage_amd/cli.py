@@ -25,7 +25,7 @@ from ._lib import FEATURE_DTYPE as L_FEATURE_DTYPE
 from .api import (LFQ_INTEGRATION, LFQ_SCORING, DatabaseParameters, DeviceDatabase, Isobaric, LfqSettings, RawBatch, Scorer,
                   ScorerParams, SpectrumBatch, SpectrumProcessor, TmtSettings, Tolerance, device_count, lfq, peptide_compositions,
                   predict_rt, rescore, tmt)
-from .mzml import read_mzml_native
+from .mgf import TOL_DA, is_mgf, read_mgf_native, read_spectra
 
 
 def search_parameters(cfg: dict) -> dict:
@@ -114,16 +114,54 @@ def scorer_params(sp: dict) -> ScorerParams:
 def _upload(scorer, processor, raw, sp, host_preprocess, positions=False):
     """spectra of one file (RawBatch) -> resident ProcessedSpectrum batch (+ spectrum ids); None when nothing is left to search.
     positions=True: also the positions in `raw` of the spectra the batch holds."""
+    kinds = getattr(raw, "iso_kind", None)  # (searchable: the window kinds of an MGF file with ppm windows; None: all Da)
     if host_preprocess:  # SpectrumProcessor::process on the host (C++), spectra below min_peaks dropped (runner.rs:313)
         processed = [(i, processor.process(raw.spectrum(i))) for i in range(raw.n)]
         processed = [(i, p) for i, p in processed if len(p.masses) >= sp["min_peaks"]]
         if not processed:
             return (None, [], np.zeros(0, np.int64)) if positions else (None, [])
-        out = scorer.upload(SpectrumBatch.from_spectra([p for _, p in processed])), [p.id for _, p in processed]
-        return out + (np.array([i for i, _ in processed], dtype=np.int64),) if positions else out
+        pos = np.array([i for i, _ in processed], dtype=np.int64)
+        out = (scorer.upload(SpectrumBatch.from_spectra([p for _, p in processed]), iso_kind=None if kinds is None else kinds[pos]),
+               [p.id for _, p in processed])
+        return out + (pos,) if positions else out
     # ... or on the device: raw peaks in, PSMs out; spectra below min_peaks stay in the batch with zero peaks
-    dbatch, _ = scorer.process_upload(raw, sp["max_peaks"], sp["deisotope"], processor.min_deisotope_mz, sp["min_peaks"])
+    dbatch, _ = scorer.process_upload(raw, sp["max_peaks"], sp["deisotope"], processor.min_deisotope_mz, sp["min_peaks"], iso_kind=kinds)
     return (dbatch, list(raw.ids), np.arange(raw.n, dtype=np.int64)) if positions else (dbatch, list(raw.ids))
+
+
+def searchable(raw, kinds, charge_zero, sp, path, quantified=False):
+    """The spectra of one file (read_spectra) that the search scores.  MGF input carries two things an mzML run never does:
+    * the kind of each isolation window (`TOLU=ppm`), which only the wide-window search reads (scoring.rs:427-431): kept as
+      `raw.iso_kind` when some window is not in Da, for the `_kinds` upload entry points;
+    * charge 0 annotated on precursors[0] (`CHARGE=0`): the reference searches around mass 0 in a narrow search and reports no
+      PSM (scoring.rs:439-443), so those spectra are left out.  Where the charge is ignored (wide window, override) they are
+      searched, but deisotoping would use a maximum charge of 0 (spectrum.rs:289-293), which this build does not do: refused
+      (check_inputs, before any work).
+    quantified: the spectra are also TMT-quantified at level 2 (their deisotoping counts there too)."""
+    if raw.n == 0:
+        return raw
+    zero = charge_zero.astype(bool)
+    if zero.any():
+        narrow = not sp["wide_window"] and not sp["override_precursor_charge"]
+        if sp["deisotope"] and (not narrow or quantified):
+            raise SystemExit(f"{path}: precursor charge 0 with deisotoping is not supported by this build")
+        if narrow:
+            keep = np.flatnonzero(~zero)
+            raw, kinds = raw.subset(keep), kinds[keep]
+    if (kinds != TOL_DA).any():
+        raw.iso_kind = np.ascontiguousarray(kinds, dtype=np.uint8)
+    return raw
+
+
+def check_inputs(paths, sp, quantified):
+    """Refuse up front, before any device work, what searchable() would refuse in a later file: precursor charge 0 of an MGF
+    spectrum where deisotoping would use it."""
+    narrow = not sp["wide_window"] and not sp["override_precursor_charge"]
+    if not sp["deisotope"] or (narrow and not quantified):
+        return
+    for path in paths:
+        if is_mgf(path) and read_mgf_native(path)[2].any():
+            raise SystemExit(f"{path}: precursor charge 0 with deisotoping is not supported by this build")
 
 
 def prefilter_peptides(dbp, fasta_text, chunk, n_targets, sp, mzml_paths, processor, device, host_preprocess, log, sn_level=None):
@@ -131,7 +169,8 @@ def prefilter_peptides(dbp, fasta_text, chunk, n_targets, sp, mzml_paths, proces
     at a time with Scorer::quick_score, keep the peptides some spectrum picked, merge the survivors (reorder_peptides) and
     leave build_from_peptides to the device.  The scorer of this pass reports one PSM more than the final one (runner.rs:190).
     sn_level: the MS2 intensities are divided by their noise (TMT `sn` at level 2; the pass reads as the search does)."""
-    raws = [read_mzml_native(path, file_id=file_id, ms_level=2, sn_level=sn_level) for file_id, path in enumerate(mzml_paths)]
+    raws = [searchable(*read_spectra(path, file_id=file_id, ms_level=2, sn_level=sn_level), sp, path)
+            for file_id, path in enumerate(mzml_paths)]
     pass_params = scorer_params(dict(sp, report_psms=sp["report_psms"] + 1))
     chunks, keeps = [], []
     for chunk_id, first in enumerate(range(0, n_targets, chunk)):
@@ -209,7 +248,13 @@ def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono
         else:
             # eight blocks of the mass axis per device, every len(workers)-th block each: the window sizes of an open search span
             # orders of magnitude ALONG the mass axis, so within a block the estimate's weights still matter
-            weights = estimate_work(raw.peak_off, raw.precursor_mz, raw.precursor_charge, params, pep_mono, raw.isolation_lo, raw.isolation_hi)
+            iso_lo, iso_hi = raw.isolation_lo, raw.isolation_hi
+            if getattr(raw, "iso_kind", None) is not None or np.isinf(iso_lo).any():  # (MGF; weights only: ppm windows as Da
+                ppm = raw.iso_kind != TOL_DA if getattr(raw, "iso_kind", None) is not None else np.zeros(raw.n, bool)  # around m/z,
+                iso_lo = np.where(ppm, iso_lo * raw.precursor_mz * np.float32(1e-6), iso_lo)  # the empty windows of TOL=NaN as 0)
+                iso_hi = np.where(ppm, iso_hi * raw.precursor_mz * np.float32(1e-6), iso_hi)
+                iso_lo, iso_hi = np.where(np.isinf(iso_lo), 0, iso_lo), np.where(np.isinf(iso_hi), 0, iso_hi)
+            weights = estimate_work(raw.peak_off, raw.precursor_mz, raw.precursor_charge, params, pep_mono, iso_lo, iso_hi)
             narrow = not params.wide_window and params.precursor_tol.kind != "da"
             shards = plan_mass_shards(precursor_sort_mass(raw.precursor_mz, raw.precursor_charge, params), len(workers),
                                       None if narrow else weights)
@@ -222,6 +267,8 @@ def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono
             idx = shards[k]
             scorer = workers[k][1]
             part = raw if len(idx) == raw.n else raw.subset(idx)
+            if part is not raw and getattr(raw, "iso_kind", None) is not None:
+                part.iso_kind = raw.iso_kind[idx]
             if part.n == 0:
                 return
             t0 = time.time()
@@ -299,6 +346,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     devices = list(devices) if devices else [device]
     device = devices[0]
     t0 = time.time()
+    check_inputs(list(mzml_paths), sp, isobaric is not None and tmt_st.level == 2)
     fasta_text = read_text(dbp.fasta)
     params = scorer_params(sp)
     processor = SpectrumProcessor(sp["max_peaks"], sp["deisotope"], cutoff)
@@ -337,12 +385,14 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
 
     def read_file(file_id, path):
         t0 = time.time()
-        raw = read_mzml_native(path, file_id=file_id, ms_level=2, check_searchable=True, sn_level=ms2_sn)
-        ms1 = read_mzml_native(path, file_id=file_id, ms_level=1) if lfq_on else None  # (runner.rs:361-363: only for LFQ)
+        # (read_spectra: .mgf / .mgf.gz to the MGF reader, which has MS2 only and no S/N option; anything else as mzML)
+        raw = read_spectra(path, file_id=file_id, ms_level=2, check_searchable=True, sn_level=ms2_sn)
+        ms1 = read_spectra(path, file_id=file_id, ms_level=1)[0] if lfq_on else None  # (runner.rs:361-363: only for LFQ)
         # TMT at a level other than 2 (SPS-MS3): that level's spectra (level 1 quantifies nothing: tmt.rs:330)
-        msn = (read_mzml_native(path, file_id=file_id, ms_level=tmt_st.level, sn_level=sn_level)
+        msn = (read_spectra(path, file_id=file_id, ms_level=tmt_st.level, sn_level=sn_level)[0]
                if isobaric is not None and tmt_st.level not in (1, 2) else None)
-        return raw, ms1, msn, (time.time() - t0) * 1000.0
+        search = searchable(*raw, sp, path, quantified=isobaric is not None and tmt_st.level == 2)
+        return raw[0], search, ms1, msn, (time.time() - t0) * 1000.0
 
     mzml_paths = list(mzml_paths)
     ms1_batches = []
@@ -351,7 +401,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     ahead = reader.submit(read_file, 0, mzml_paths[0]) if mzml_paths else None
     for file_id, path in enumerate(mzml_paths):
         try:
-            raw, ms1, msn, io_ms = ahead.result()
+            raw, search_raw, ms1, msn, io_ms = ahead.result()
         except BaseException:
             reader.shutdown(wait=True)
             raise
@@ -367,10 +417,10 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
                 tmt_parts.append((file_id, list(q.ids) if tmt_st.level == 2 else list(q.precursor_ref), q.ion_injection_time,
                                   res.intensity))
             tmt_ms += (time.time() - t0) * 1000.0
-        if raw.n == 0:
+        if search_raw.n == 0:
             continue
         t0 = time.time()
-        found = search_file(workers, processor, raw, sp, host_preprocess, sp["annotate_matches"], host.pep_mono)
+        found = search_file(workers, processor, search_raw, sp, host_preprocess, sp["annotate_matches"], host.pep_mono)
         if found is None:
             continue
         feats, counts, ids, ann = found

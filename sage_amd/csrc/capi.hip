@@ -185,7 +185,7 @@ struct SageDeviceBatch {
     uint32_t n = 0;
     DevBuf<uint64_t> peak_off;
     DevBuf<float> masses, intensities, precursor_mz, iso_lo, iso_hi, tic, rt, ims;
-    DevBuf<uint8_t> charge;
+    DevBuf<uint8_t> charge, iso_kind;
     DevBuf<uint32_t> file_id, order, sort_a, sort_b, sort_idx;
     DevBuf<uint8_t> sort_tmp;
     DevBuf<uint4> sched;     // DevBatchView::sched (SAGE_HIP_NO_SCHED=1: not built — the kernels go through `order`)
@@ -205,6 +205,7 @@ struct SageScorer {
     SageScorerParams params{};
     DevScorer dev{};
     std::mutex mu;                   // entry points taking this handle serialise on it (clone the scorer for concurrency)
+    const uint8_t* iso_kind = nullptr;  // the call in progress (under `mu`): SAGE_TOL_* of each spectrum's isolation window, null = Da
     hipStream_t stream = nullptr;    // compute (and, for resident batches, the result download)
     hipStream_t up_stream = nullptr, down_stream = nullptr;  // streaming pipeline: H2D of batch c + 1, D2H of batch c - 1
     hipStream_t side_stream = nullptr;  // kernels of one batch that may run next to each other (the two heap-replay kernels); also the
@@ -499,6 +500,34 @@ const char* sage_hip_mzml_precursor_ref(const SageMzml* run, uint64_t i) {
     return run->run.precursor_refs.data() + run->run.ref_off[i];
 }
 void sage_hip_mzml_free(SageMzml* run) { delete run; }
+int sage_hip_mgf_read(const char* path, uint32_t file_id, SageMzml** out) {
+    if (!path || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mgf_read: null argument");
+    auto h = std::make_unique<SageMzml>();
+    std::string err;
+    try {
+        if (!read_mgf(path, file_id, h->run, err)) return fail(SAGE_HIP_ERR_INVALID, err);
+    } catch (const std::exception& e) {
+        return fail(SAGE_HIP_ERR_INVALID, e.what());
+    }
+    *out = h.release();
+    return SAGE_HIP_OK;
+}
+int sage_hip_mzml_isolation_kinds(const SageMzml* run, uint8_t* out) {
+    if (!run || (!out && run->run.n())) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mzml_isolation_kinds: null argument");
+    const MzmlRun& r = run->run;
+    for (uint64_t i = 0; i < r.n(); ++i) out[i] = r.iso_kind.empty() ? (uint8_t)SAGE_TOL_DA : r.iso_kind[i];
+    return SAGE_HIP_OK;
+}
+int sage_hip_mzml_charge_zero(const SageMzml* run, uint8_t* out) {
+    if (!run || (!out && run->run.n())) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mzml_charge_zero: null argument");
+    const MzmlRun& r = run->run;
+    for (uint64_t i = 0; i < r.n(); ++i) out[i] = r.charge_zero.empty() ? 0 : r.charge_zero[i];
+    return SAGE_HIP_OK;
+}
+int sage_hip_parse_f32(const char* token, uint64_t len, float* out) {
+    if ((!token && len) || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_parse_f32: null argument");
+    return parse_f32_rust(token, token + len, *out) ? SAGE_HIP_OK : fail(SAGE_HIP_ERR_INVALID, "invalid float literal");
+}
 int sage_hip_write_results(const char* path, int format, const SageHostDb* db, const SageFeature* features, uint64_t n,
                            const uint64_t* order, const uint64_t* psm_id, const char* const* filenames, uint32_t n_files,
                            const char* const* spec_ids, const SagePostColumns* post) {
@@ -1068,12 +1097,19 @@ static bool is_page_locked(const void* p) {
 
 // What a batch looks like to the narrow kernel, from (a sample of) its spectra: the mean candidate-window size picks the
 // matching variant, the largest one says whether the large-window kernels have to be launched at all.
+// The per-spectrum isolation-window kinds of the entry point in progress (sage_hip_*_kinds), for the upload paths and the window
+// estimate below it; set and cleared under the scorer's mutex.
+struct KindScope {
+    SageScorer* s;
+    KindScope(SageScorer* s_, const uint8_t* kinds) : s(s_) { s->iso_kind = kinds; }
+    ~KindScope() { s->iso_kind = nullptr; }
+};
 struct WindowEstimate {
     uint32_t probe;       // narrow kernel variant (DevBatchView::probe)
     bool maybe_wide;      // some window may exceed DevScorer::wcap (a sample cannot rule it out: callers re-run on a wrong "no")
 };
 static WindowEstimate choose_probe(const SageScorer* s, uint32_t n, const float* precursor_mz, const uint8_t* precursor_charge,
-                                   const float* isolation_lo, const float* isolation_hi) {
+                                   const float* isolation_lo, const float* isolation_hi, const uint8_t* iso_kind) {
     const SageScorerParams& p = s->params;
     const std::vector<float>& pm = s->db->h_pep_mono;
     const uint32_t step = std::max<uint32_t>(1, n / 1024);  // (each sample costs two searches over the whole peptide list: ~0.2 us)
@@ -1088,11 +1124,13 @@ static WindowEstimate choose_probe(const SageScorer* s, uint32_t n, const float*
             sagecore::Tol tol{p.precursor_tol.kind, p.precursor_tol.lo, p.precursor_tol.hi};
             if (p.wide_window) {
                 float lo = -2.4f, hi = 2.4f;
+                int kind = 2;
                 if (isolation_lo && isolation_hi && isolation_lo[i] == isolation_lo[i] && isolation_hi[i] == isolation_hi[i]) {
                     lo = isolation_lo[i];
                     hi = isolation_hi[i];
+                    kind = iso_kind ? iso_kind[i] : 2;
                 }
-                tol = sagecore::Tol{2, lo * (float)z, hi * (float)z};
+                tol = sagecore::Tol{kind, lo * (float)z, hi * (float)z};
             }
             float lo, hi;
             sagecore::tol_bounds(tol, center, lo, hi);
@@ -1177,7 +1215,8 @@ static int stage_and_upload(SageScorer* s, SageDeviceBatch* d, const SageSpectru
     HIP_TRY(d->sort_tmp.reserve(sort_bytes));
     const bool use_sched = !getenv("SAGE_HIP_NO_SCHED");
     if (use_sched) { HIP_TRY(d->sched.reserve(2 * (size_t)n)); }
-    const size_t small = ((size_t)n + 1) * 8 + (size_t)n * (4 * 7 + 1) + 64 * 12;
+    const bool has_kind = has_iso && s->iso_kind != nullptr;
+    const size_t small = ((size_t)n + 1) * 8 + (size_t)n * (4 * 7 + 1 + (has_kind ? 1 : 0)) + 64 * 13;
     HIP_TRY(d->stage.reserve(small + (peaks_locked ? 0 : total * 8 + 128)));
     HIP_TRY(d->meta.reserve(small));
     unsigned char* cur = d->stage.p;
@@ -1190,6 +1229,7 @@ static int stage_and_upload(SageScorer* s, SageDeviceBatch* d, const SageSpectru
     float* h_rt = has_rt ? carve<float>(cur, n) : nullptr;
     float* h_ims = has_ims ? carve<float>(cur, n) : nullptr;
     uint32_t* h_fid = has_fid ? carve<uint32_t>(cur, n) : nullptr;
+    uint8_t* h_kind = has_kind ? carve<uint8_t>(cur, n) : nullptr;
     uint32_t pcap = 1, zmax = 0;
     bool any_unknown = false;
     h_off[0] = 0;
@@ -1220,6 +1260,7 @@ static int stage_and_upload(SageScorer* s, SageDeviceBatch* d, const SageSpectru
         if (has_rt) std::memcpy(h_rt, b->scan_start_time + c0, (size_t)n * 4);
         if (has_ims) std::memcpy(h_ims, b->inverse_ion_mobility + c0, (size_t)n * 4);
         if (has_fid) std::memcpy(h_fid, b->file_id + c0, (size_t)n * 4);
+        if (has_kind) std::memcpy(h_kind, s->iso_kind + c0, n);
     }
     const size_t meta_bytes = (size_t)(cur - d->stage.p);
     auto image = [&](const void* h) { return h ? d->meta.p + ((const unsigned char*)h - d->stage.p) : nullptr; };
@@ -1248,7 +1289,8 @@ static int stage_and_upload(SageScorer* s, SageDeviceBatch* d, const SageSpectru
                                                d->sort_a.p, d->sort_b.p, d->sort_idx.p, d->order.p, d->sort_tmp.p, sort_bytes, s->side_stream));
         if (use_sched)
             schedule_records_on_device(n, d->order.p, (const uint64_t*)image(h_off), (const float*)image(h_mz), (const uint8_t*)image(h_z),
-                                       (const float*)image(h_lo), (const float*)image(h_hi), d->sched.p, s->side_stream);
+                                       (const float*)image(h_lo), (const float*)image(h_hi), (const uint8_t*)image(h_kind), d->sched.p,
+                                       s->side_stream);
         HIP_TRY(hipEventRecord(d->sort_done.e, s->side_stream));
         if (total && !peaks_first) {
             HIP_TRY(hipMemcpyAsync(d->masses.p, src_m, total * 4, hipMemcpyHostToDevice, up));
@@ -1269,6 +1311,7 @@ static int stage_and_upload(SageScorer* s, SageDeviceBatch* d, const SageSpectru
     v.precursor_charge = (const uint8_t*)image(h_z);
     v.isolation_lo = (const float*)image(h_lo);
     v.isolation_hi = (const float*)image(h_hi);
+    v.iso_kind = (const uint8_t*)image(h_kind);
     v.tic = (const float*)image(h_tic);
     v.rt = (const float*)image(h_rt);
     v.ims = (const float*)image(h_ims);
@@ -1309,17 +1352,18 @@ static int exact_window_check(SageScorer* s, SageDeviceBatch* d, hipStream_t st)
     return SAGE_HIP_OK;
 }
 
-int sage_hip_batch_upload(SageScorer* s, const SageSpectrumBatch* b, SageDeviceBatch** out) {
+static int batch_upload(SageScorer* s, const SageSpectrumBatch* b, const uint8_t* iso_kind, SageDeviceBatch** out) {
     if (!s || !b || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
     int rc = check_batch_args(b);
     if (rc != SAGE_HIP_OK) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
+    KindScope kinds(s, iso_kind);
     HIP_TRY(hipSetDevice(s->db->device));
     auto d = std::make_unique<SageDeviceBatch>();
     d->device = s->db->device;
     HIP_TRY(d->up_done.create(false));
     const uint32_t n = b->n_spectra;
-    const WindowEstimate est = choose_probe(s, n, b->precursor_mz, b->precursor_charge, b->isolation_lo, b->isolation_hi);
+    const WindowEstimate est = choose_probe(s, n, b->precursor_mz, b->precursor_charge, b->isolation_lo, b->isolation_hi, s->iso_kind);
     rc = stage_and_upload(s, d.get(), b, 0, n, is_page_locked(b->masses) && is_page_locked(b->intensities), est, s->up_stream);
     if (rc != SAGE_HIP_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s->up_stream));
@@ -1441,14 +1485,15 @@ static int process_raw_on_device(const SageRawBatch* raw, uint64_t take_top_n, i
     return SAGE_HIP_OK;
 }
 
-int sage_hip_batch_process_upload(SageScorer* s, const SageRawBatch* raw, uint64_t take_top_n, int deisotope,
-                                  float min_deisotope_mz, uint32_t min_peaks, SageDeviceBatch** out, uint32_t* out_npeaks) {
+static int batch_process_upload(SageScorer* s, const SageRawBatch* raw, const uint8_t* iso_kind, uint64_t take_top_n, int deisotope,
+                                float min_deisotope_mz, uint32_t min_peaks, SageDeviceBatch** out, uint32_t* out_npeaks) {
     if (!s || !raw || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
     const uint32_t n = raw->n_spectra;
     if (n && (!raw->peak_off || !raw->precursor_mz || !raw->precursor_charge))
         return fail(SAGE_HIP_ERR_INVALID, "missing required spectrum arrays");
     if (take_top_n == 0 || take_top_n > 0xFFFFu) return fail(SAGE_HIP_ERR_INVALID, "take_top_n must be in [1, 65535]");
     std::lock_guard<std::mutex> lock(s->mu);
+    KindScope kinds(s, iso_kind);
     HIP_TRY(hipSetDevice(s->db->device));
     auto d = std::make_unique<SageDeviceBatch>();
     d->device = s->db->device;
@@ -1477,6 +1522,8 @@ int sage_hip_batch_process_upload(SageScorer* s, const SageRawBatch* raw, uint64
         HIP_TRY(d->iso_lo.upload(raw->isolation_lo, n));
         HIP_TRY(d->iso_hi.upload(raw->isolation_hi, n));
     }
+    const bool has_kind = has_iso && s->iso_kind != nullptr;
+    if (has_kind) HIP_TRY(d->iso_kind.upload(s->iso_kind, n));
     if (raw->scan_start_time) HIP_TRY(d->rt.upload(raw->scan_start_time, n));
     if (raw->inverse_ion_mobility) HIP_TRY(d->ims.upload(raw->inverse_ion_mobility, n));
     if (raw->file_id) HIP_TRY(d->file_id.upload(raw->file_id, n));
@@ -1492,7 +1539,7 @@ int sage_hip_batch_process_upload(SageScorer* s, const SageRawBatch* raw, uint64
     if (use_sched) {
         HIP_TRY(d->sched.alloc(2 * (size_t)n));
         schedule_records_on_device(n, d->order.p, d->peak_off.p, d->precursor_mz.p, d->charge.p, has_iso ? d->iso_lo.p : nullptr,
-                                   has_iso ? d->iso_hi.p : nullptr, d->sched.p, s->stream);
+                                   has_iso ? d->iso_hi.p : nullptr, has_kind ? d->iso_kind.p : nullptr, d->sched.p, s->stream);
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     DevBatchView& v = d->view;
@@ -1505,13 +1552,14 @@ int sage_hip_batch_process_upload(SageScorer* s, const SageRawBatch* raw, uint64
     v.precursor_charge = d->charge.p;
     v.isolation_lo = has_iso ? d->iso_lo.p : nullptr;
     v.isolation_hi = has_iso ? d->iso_hi.p : nullptr;
+    v.iso_kind = has_kind ? d->iso_kind.p : nullptr;
     v.tic = d->tic.p;
     v.rt = raw->scan_start_time ? d->rt.p : nullptr;
     v.ims = raw->inverse_ion_mobility ? d->ims.p : nullptr;
     v.file_id = raw->file_id ? d->file_id.p : nullptr;
     v.order = d->order.p;
     v.sched = use_sched && n ? d->sched.p : nullptr;
-    const WindowEstimate est = choose_probe(s, n, raw->precursor_mz, raw->precursor_charge, raw->isolation_lo, raw->isolation_hi);
+    const WindowEstimate est = choose_probe(s, n, raw->precursor_mz, raw->precursor_charge, raw->isolation_lo, raw->isolation_hi, s->iso_kind);
     v.probe = est.probe;
     d->maybe_wide = est.maybe_wide;
     v.pcap = pcap;
@@ -2364,11 +2412,12 @@ static int score_range(SageScorer* s, const SageSpectrumBatch* b, uint32_t r0, u
     return SAGE_HIP_OK;
 }
 
-int sage_hip_score_batch(SageScorer* s, const SageSpectrumBatch* b, SageFeature* out, uint32_t* out_count) {
+static int score_batch(SageScorer* s, const SageSpectrumBatch* b, const uint8_t* iso_kind, SageFeature* out, uint32_t* out_count) {
     if (!s || !b || (b->n_spectra && (!out || !out_count))) return fail(SAGE_HIP_ERR_INVALID, "null argument");
     int rc = check_batch_args(b);
     if (rc != SAGE_HIP_OK) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
+    KindScope kinds(s, iso_kind);
     HIP_TRY(hipSetDevice(s->db->device));
     reset_timing(s);
     const uint32_t n = b->n_spectra;
@@ -2379,7 +2428,7 @@ int sage_hip_score_batch(SageScorer* s, const SageSpectrumBatch* b, SageFeature*
     // peptide list) runs on a helper thread while this one stages the first chunk and enqueues its upload, which need neither
     // of its answers; score_range joins it before the chunk's first launch.
     std::future<WindowEstimate> pending = std::async(std::launch::async, [s, n, b]() {
-        return choose_probe(s, n, b->precursor_mz, b->precursor_charge, b->isolation_lo, b->isolation_hi);
+        return choose_probe(s, n, b->precursor_mz, b->precursor_charge, b->isolation_lo, b->isolation_hi, s->iso_kind);
     });
     WindowEstimate est{};
     est.probe = 1;
@@ -2567,4 +2616,25 @@ int sage_hip_last_timing(const SageScorer* s, SageTiming* out) {
     return SAGE_HIP_OK;
 }
 
+// Entry points with and without the per-spectrum isolation-window kinds (include/sage_hip.h)
+int sage_hip_batch_upload(SageScorer* s, const SageSpectrumBatch* b, SageDeviceBatch** out) { return batch_upload(s, b, nullptr, out); }
+int sage_hip_batch_upload_kinds(SageScorer* s, const SageSpectrumBatch* b, const uint8_t* iso_kind, SageDeviceBatch** out) {
+    return batch_upload(s, b, iso_kind, out);
+}
+int sage_hip_batch_process_upload(SageScorer* s, const SageRawBatch* raw, uint64_t take_top_n, int deisotope, float min_deisotope_mz,
+                                  uint32_t min_peaks, SageDeviceBatch** out, uint32_t* out_npeaks) {
+    return batch_process_upload(s, raw, nullptr, take_top_n, deisotope, min_deisotope_mz, min_peaks, out, out_npeaks);
+}
+int sage_hip_batch_process_upload_kinds(SageScorer* s, const SageRawBatch* raw, const uint8_t* iso_kind, uint64_t take_top_n,
+                                        int deisotope, float min_deisotope_mz, uint32_t min_peaks, SageDeviceBatch** out,
+                                        uint32_t* out_npeaks) {
+    return batch_process_upload(s, raw, iso_kind, take_top_n, deisotope, min_deisotope_mz, min_peaks, out, out_npeaks);
+}
+int sage_hip_score_batch(SageScorer* s, const SageSpectrumBatch* b, SageFeature* out, uint32_t* out_count) {
+    return score_batch(s, b, nullptr, out, out_count);
+}
+int sage_hip_score_batch_kinds(SageScorer* s, const SageSpectrumBatch* b, const uint8_t* iso_kind, SageFeature* out,
+                               uint32_t* out_count) {
+    return score_batch(s, b, iso_kind, out, out_count);
+}
 }  // extern "C"

@@ -132,7 +132,9 @@ struct DevBatchView {
     uint32_t fzcap;             // max (max_fragment_charge - 1) over the charges this batch can use
     const uint4* sched;         // may be null.  [2 n] what a block needs of the spectrum it scores, IN SCHEDULE ORDER: record b =
                                 //     {order[b], peaks, peak_off lo, hi}, {charge, precursor m/z, isolation lo, hi (NaN: none)} — one
-                                //     trip to a line its neighbours share instead of order[b] and then five random reads
+                                //     trip to a line its neighbours share instead of order[b] and then five random reads.  The
+                                //     charge word carries (SAGE_TOL_* of the isolation window) ^ SAGE_TOL_DA in bits 8-15: 0 for Da
+    const uint8_t* iso_kind;    // may be null (every window Da): SAGE_TOL_* of isolation_lo / hi (MGF `TOLU=ppm`)
 };
 
 struct DevWork {  // per-spectrum outputs of the preliminary pass
@@ -286,7 +288,8 @@ size_t schedule_temp_bytes(uint32_t n);
 int schedule_on_device(uint32_t n, const float* d_precursor_mz, const uint8_t* d_charge, uint32_t min_charge, uint32_t* d_keys_a,
                        uint32_t* d_keys_b, uint32_t* d_idx, uint32_t* d_order, void* d_temp, size_t temp_bytes, void* stream);
 void schedule_records_on_device(uint32_t n, const uint32_t* d_order, const uint64_t* d_peak_off, const float* d_precursor_mz,
-                                const uint8_t* d_charge, const float* d_iso_lo, const float* d_iso_hi, uint4* d_sched, void* stream);
+                                const uint8_t* d_charge, const float* d_iso_lo, const float* d_iso_hi, const uint8_t* d_iso_kind,
+                                uint4* d_sched, void* stream);
 size_t process_lds_bytes(uint32_t rcap, uint32_t rpow2);
 int process_kernel_prepare(size_t max_lds_bytes);
 void launch_process(uint32_t n, const uint64_t* raw_off, const float* raw_mz, const float* raw_int, const uint8_t* charge,

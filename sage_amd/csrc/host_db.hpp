@@ -88,9 +88,16 @@ struct MzmlRun {
     std::vector<float> ion_injection_time;  // MS:1000927, 0 when absent
     std::string precursor_refs;      // NUL-separated spectrumRef of each kept precursor ("" when absent)
     std::vector<uint64_t> ref_off{0};  // [n + 1] into precursor_refs
+    std::vector<uint8_t> iso_kind;     // SAGE_TOL_* of isolation_lo / hi; empty == all SAGE_TOL_DA (mzML)
+    std::vector<uint8_t> charge_zero;  // precursors[0].charge == Some(0) (MGF `CHARGE=0`); empty == none
     uint64_t n() const { return precursor_mz.size(); }
 };
 bool read_mzml(const char* path, uint32_t file_id, int ms_level, int sn_level, MzmlRun& run, std::string& err);
+bool load_text(const char* path, std::string& text, std::string& err);
+// mgf_reader.cpp: sage-cloudpath mgf.rs MgfReader::with_file_id(file_id).parse(..)
+bool read_mgf(const char* path, uint32_t file_id, MzmlRun& run, std::string& err);
+// str::parse::<f32>() (Rust core dec2flt): grammar and correctly rounded value; false when the token is rejected
+bool parse_f32_rust(const char* b, const char* e, float& out);
 
 // writers.cpp
 bool write_results(const char* path, int format, const HostDb& db, const SageFeature* f, uint64_t n, const uint64_t* order,

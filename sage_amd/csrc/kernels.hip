@@ -592,7 +592,11 @@ __device__ __forceinline__ SpecInfo load_spec(const DevScorer& sc, const DevBatc
     s.iso_tol.hi = 2.4f;  // scoring.rs:430
     if (b.isolation_lo && b.isolation_hi) {
         const float a = unif(b.isolation_lo[spec]), c = unif(b.isolation_hi[spec]);
-        if (a == a && c == c) { s.iso_tol.lo = a; s.iso_tol.hi = c; }
+        if (a == a && c == c) {
+            s.iso_tol.lo = a;
+            s.iso_tol.hi = c;
+            if (b.iso_kind) s.iso_tol.kind = (int32_t)uni(b.iso_kind[spec]);  // (Tolerance::Ppm / Pct of an MGF `TOLU`)
+        }
     }
     return s;
 }
@@ -605,7 +609,7 @@ __device__ __forceinline__ SpecInfo load_spec_sched(const DevScorer& sc, const D
     SpecInfo s;
     s.p0 = ((uint64_t)uni(r0.w) << 32) | uni(r0.z);
     s.P = uni(r0.y);
-    const uint32_t zraw = uni(r1.x);
+    const uint32_t zraw = uni(r1.x) & 0xFFu;
     if (sc.wide_window || zraw == 0 || sc.override_precursor_charge) {  // scoring.rs:423, 437, 442
         s.z0 = sc.min_precursor_charge;
         s.z1 = sc.max_precursor_charge;
@@ -623,7 +627,11 @@ __device__ __forceinline__ SpecInfo load_spec_sched(const DevScorer& sc, const D
     s.iso_tol.lo = -2.4f;
     s.iso_tol.hi = 2.4f;  // scoring.rs:430
     const float a = unif(__uint_as_float(r1.z)), c = unif(__uint_as_float(r1.w));  // (NaN bits where the batch has no isolation windows)
-    if (a == a && c == c) { s.iso_tol.lo = a; s.iso_tol.hi = c; }
+    if (a == a && c == c) {
+        s.iso_tol.lo = a;
+        s.iso_tol.hi = c;
+        s.iso_tol.kind = (int32_t)(((uni(r1.x) >> 8) & 0xFFu) ^ 2u);  // (bits 8-15: kind ^ SAGE_TOL_DA)
+    }
     return s;
 }
 
@@ -4587,7 +4595,11 @@ __global__ __launch_bounds__(256) void window_max_kernel(DevScorer sc, DevBatchV
         Tol iso_tol{2, -2.4f, 2.4f};
         if (b.isolation_lo && b.isolation_hi) {
             const float a = b.isolation_lo[spec], c = b.isolation_hi[spec];
-            if (a == a && c == c) { iso_tol.lo = a; iso_tol.hi = c; }
+            if (a == a && c == c) {
+                iso_tol.lo = a;
+                iso_tol.hi = c;
+                if (b.iso_kind) iso_tol.kind = (int32_t)b.iso_kind[spec];
+            }
         }
         const bool fold = sc.min_isotope_err != sc.max_isotope_err;
         const int isoA = fold ? sc.min_isotope_err : 0, isoB = fold ? sc.max_isotope_err : 0;

@@ -406,9 +406,8 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, int sn_l
 
 }  // namespace
 
-// MzMLReader::with_file_id_and_level_filter(file_id, ms_level).set_signal_to_noise(sn_level).parse(..): ms_level < 0 keeps
-// every level, sn_level < 0 divides nothing
-bool read_mzml(const char* path, uint32_t file_id, int ms_level, int sn_level, MzmlRun& run, std::string& err) {
+// The whole file as text, gunzipped when it starts with the gzip magic (shared with mgf_reader.cpp)
+bool load_text(const char* path, std::string& text, std::string& err) {
     FILE* fh = std::fopen(path, "rb");
     if (!fh) {
         err = std::string("cannot open ") + path;
@@ -417,7 +416,7 @@ bool read_mzml(const char* path, uint32_t file_id, int ms_level, int sn_level, M
     std::fseek(fh, 0, SEEK_END);
     const long size = std::ftell(fh);
     std::fseek(fh, 0, SEEK_SET);
-    std::string text((size_t)std::max<long>(size, 0), '\0');
+    text.assign((size_t)std::max<long>(size, 0), '\0');
     const size_t got = size > 0 ? std::fread(&text[0], 1, (size_t)size, fh) : 0;
     std::fclose(fh);
     if ((long)got != size) {
@@ -472,6 +471,14 @@ bool read_mzml(const char* path, uint32_t file_id, int ms_level, int sn_level, M
         plain_text.resize(have);
         text.swap(plain_text);
     }
+    return true;
+}
+
+// MzMLReader::with_file_id_and_level_filter(file_id, ms_level).set_signal_to_noise(sn_level).parse(..): ms_level < 0 keeps
+// every level, sn_level < 0 divides nothing
+bool read_mzml(const char* path, uint32_t file_id, int ms_level, int sn_level, MzmlRun& run, std::string& err) {
+    std::string text;
+    if (!load_text(path, text, err)) return false;
     run = MzmlRun{};
     run.peak_off.push_back(0);
     run.id_off.push_back(0);

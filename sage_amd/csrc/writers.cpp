@@ -88,8 +88,22 @@ inline void itoa(std::string& o, I x) {
     o += std::to_string(x);
     o += '\t';
 }
+// a text field as the csv crate writes it with QuoteStyle::Necessary (the reference's writers: runner.rs:837-839, 907-909): in
+// double quotes, inner quotes doubled, when it contains a quote, the tab delimiter, CR or LF; verbatim otherwise
+inline void field(std::string& o, const std::string& s) {
+    if (s.find_first_of("\"\t\r\n") == std::string::npos) {
+        o += s;
+        return;
+    }
+    o += '"';
+    for (char c : s) {
+        if (c == '"') o += '"';
+        o += c;
+    }
+    o += '"';
+}
 inline void str(std::string& o, const std::string& s) {
-    o += s;
+    field(o, s);
     o += '\t';
 }
 inline float col(const float* p, uint64_t i, float dflt) { return p ? p[i] : dflt; }
@@ -262,7 +276,7 @@ bool write_lfq(const char* path, const HostDb& db, const SageLfqOutput& g, const
     std::string out = "peptide\tcharge\tproteins\tq_value\tscore\tspectral_angle";
     for (uint32_t f = 0; f < n_files; ++f) {
         out += '\t';
-        out += filenames[f];
+        field(out, filenames[f]);
     }
     out += '\n';
     bool ok = true;

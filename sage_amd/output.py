@@ -94,12 +94,24 @@ def feature_row(psm_id: int, f, db, filename: str, scannr: str, post: Optional[d
     ]
 
 
+def csv_field(s: str) -> str:
+    """a field as the csv crate writes it with QuoteStyle::Necessary (runner.rs:837-839, 907-909): quoted, inner quotes
+    doubled, when it contains a quote, tab, CR or LF"""
+    if any(c in s for c in '"\t\r\n'):
+        return '"' + s.replace('"', '""') + '"'
+    return s
+
+
+def _record(fields) -> str:
+    return "\t".join(csv_field(f) for f in fields)
+
+
 def write_features(path: str, rows: Sequence[List[str]]) -> None:
     """write_features (runner.rs:830-905): tab-separated, header first."""
     with open(path, "w", newline="") as fh:
-        fh.write("\t".join(HEADERS) + "\n")
+        fh.write(_record(HEADERS) + "\n")
         for r in rows:
-            fh.write("\t".join(r) + "\n")
+            fh.write(_record(r) + "\n")
 
 
 def fragment_rows(psm_id: int, lo: int, hi: int, arr) -> List[List[str]]:
@@ -111,9 +123,9 @@ def fragment_rows(psm_id: int, lo: int, hi: int, arr) -> List[List[str]]:
 
 def write_fragments(path: str, rows: Sequence[List[str]]) -> None:
     with open(path, "w", newline="") as fh:
-        fh.write("\t".join(FRAGMENT_HEADERS) + "\n")
+        fh.write(_record(FRAGMENT_HEADERS) + "\n")
         for r in rows:
-            fh.write("\t".join(r) + "\n")
+            fh.write(_record(r) + "\n")
 
 
 PIN_HEADERS = ["SpecId", "Label", "ScanNr", "ExpMass", "CalcMass", "FileName", "retentiontime", "ion_mobility", "rank", "z=2",
@@ -169,9 +181,9 @@ def pin_row(psm_id: int, f, db, filename: str, spec_id: str, post: Optional[dict
 def write_pin(path: str, rows: Sequence[List[str]]) -> None:
     """write_pin (runner.rs:1086-1135)."""
     with open(path, "w", newline="") as fh:
-        fh.write("\t".join(PIN_HEADERS) + "\n")
+        fh.write(_record(PIN_HEADERS) + "\n")
         for r in rows:
-            fh.write("\t".join(r) + "\n")
+            fh.write(_record(r) + "\n")
 
 
 def write_results_native(path: str, fmt: str, db, features, order, psm_ids, filenames, spec_ids, post=None) -> None:
@@ -222,9 +234,9 @@ def lfq_rows(db, result, rows) -> List[List[str]]:
 
 def write_lfq(path: str, filenames: Sequence[str], rows: Sequence[List[str]]) -> None:
     with open(path, "w", newline="") as fh:
-        fh.write("\t".join(LFQ_HEADERS + list(filenames)) + "\n")
+        fh.write(_record(LFQ_HEADERS + list(filenames)) + "\n")
         for r in rows:
-            fh.write("\t".join(r) + "\n")
+            fh.write(_record(r) + "\n")
 
 
 def write_lfq_native(path: str, db, result, filenames: Sequence[str], rows=None) -> None:
@@ -253,9 +265,9 @@ def tmt_rows(filenames: Sequence[str], file_id, spec_ids, ion_injection_time, in
 
 def write_tmt(path: str, headers: Sequence[str], rows: Sequence[List[str]]) -> None:
     with open(path, "w", newline="") as fh:
-        fh.write("\t".join(TMT_HEADERS + list(headers)) + "\n")
+        fh.write(_record(TMT_HEADERS + list(headers)) + "\n")
         for r in rows:
-            fh.write("\t".join(r) + "\n")
+            fh.write(_record(r) + "\n")
 
 
 def write_tmt_native(path: str, headers: Sequence[str], filenames: Sequence[str], file_id, spec_ids, ion_injection_time,
