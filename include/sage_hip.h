@@ -434,6 +434,16 @@ int sage_hip_mzml_read_sn(const char* path, uint32_t file_id, int ms_level, int 
 /* RawSpectrum.ion_injection_time (MS:1000927; 0 when absent) and precursors.first().spectrum_ref ("" when absent) */
 float sage_hip_mzml_ion_injection_time(const SageMzml* run, uint64_t i);
 const char* sage_hip_mzml_precursor_ref(const SageMzml* run, uint64_t i);
+/* RawSpectrum.mobility of the MS1 spectra of a run: the per-peak ion-mobility array that converters of timsTOF data write as a
+ * third binaryDataArray.  An ADDITION over the reference's mzML reader, which ignores the array (its MS1 mobilities come from the
+ * Bruker reader only).  An array is the mobility array when it carries MS:1002893, MS:1002816, MS:1003006, MS:1003007 or
+ * MS:1003008 and is neither m/z, intensity nor noise (MS:1002744); 32/64-bit, zlib or not, stored as f32.  It is kept for spectra
+ * whose ms level is 1 only (spectrum.rs:344); a length other than the m/z array's fails the read (SAGE_HIP_ERR_INVALID).
+ *   _mobility       the column, indexed like SageRawBatch.mz ([peak_off[n]]; 0 inside spectra without the array), or NULL when no
+ *                   kept spectrum has one (always NULL for MGF runs); owned by the handle
+ *   _has_mobility   out[n]: 1 where RawSpectrum.mobility is Some */
+const float* sage_hip_mzml_mobility(const SageMzml* run);
+int sage_hip_mzml_has_mobility(const SageMzml* run, uint8_t* out);
 
 /* ---- MGF input (host; sage-cloudpath/src/mgf.rs:325-369 MgfReader::with_file_id(file_id).parse, util.rs:107-118 read_mgf):
  * every spectrum of a .mgf / .mgf.gz file as a SageMzml run (MS2, centroided, no ion mobility, injection time 0, no spectrumRef),
@@ -494,7 +504,8 @@ int sage_hip_write_results(const char* path, int format, const SageHostDb* db, c
                            const char* const* spec_ids, const SagePostColumns* post);
 
 /* ---- label-free MS1 quantification (sage-cli runner.rs:562-575: lfq::build_feature_map(..).quantify(..) then
- * fdr::picked_precursor; crates/sage/src/lfq.rs, isotopes.rs, fdr.rs:228-287), MS1 spectra without ion mobility.
+ * fdr::picked_precursor; crates/sage/src/lfq.rs, isotopes.rs, fdr.rs:228-287).  sage_hip_lfq traces MS1 spectra without ion
+ * mobility; sage_hip_lfq_im below adds the per-peak mobility column and the mobility window of every feature.
  *   feature map   host: the first confident target feature per peptide; device: the charge x isotope x forward/decoy windows
  *                 (tol_bounds, no FMA), rocPRIM sorts by (rt, peptide, charge, isotope, decoy) and, per 16 384-window page,
  *                 by (mass_lo, rt position)
@@ -511,7 +522,7 @@ typedef struct SageLfqSettings {   /* lfq.rs:45-54 */
     int32_t integration;           /* SAGE_LFQ_APEX / SAGE_LFQ_SUM */
     double spectral_angle;
     float ppm_tolerance;
-    float mobility_pct_tolerance;  /* accepted; MS1 spectra carry no mobility here */
+    float mobility_pct_tolerance;  /* sage_hip_lfq_im: Tolerance::Pct(-t, t) around Feature.ims; sage_hip_lfq reads no mobility */
     float peptide_q_value;
     uint8_t combine_charge_states;
     uint8_t min_charge, max_charge;/* the search's precursor_charge range */
@@ -520,7 +531,7 @@ typedef struct SageLfqSettings {   /* lfq.rs:45-54 */
 
 typedef struct SageLfqInput {
     uint64_t n_features;
-    const SageFeature* features;   /* [n]: peptide_idx, label, calcmass, file_id are read */
+    const SageFeature* features;   /* [n]: peptide_idx, label, calcmass, file_id are read (sage_hip_lfq_im: ims, too) */
     const uint32_t* order;         /* [n] confidence order (SageRescoreOutput.order) or NULL: input order */
     const float* aligned_rt;       /* [n], input order */
     const float* peptide_q;        /* [n], input order */
@@ -560,6 +571,23 @@ typedef struct SageLfqOutput {
 
 /* SAGE_HIP_ERR_INVALID when `cap` is smaller than the grids the call finds (n_grids then holds the number needed). */
 int sage_hip_lfq(int device, const SageLfqInput* in, SageLfqOutput* out);
+
+/* sage_hip_lfq for ion-mobility MS1 spectra (lfq.rs:111-127, 267-286, 677-686; spectrum.rs:344-378).  Same inputs and outputs,
+ * plus, per MS1 batch, the mobility of every peak:
+ *   feature map   every window of a selected feature carries (mobility_lo, mobility_hi) =
+ *                 Tolerance::Pct(-mobility_pct_tolerance, mobility_pct_tolerance).bounds(feature.ims) (mass.rs:28-32, f32, no FMA).
+ *                 As in the reference, a feature with ims == 0 (no precursor mobility) gets the window [0, 0], and a negative or
+ *                 NaN ims gives bounds that no mobility satisfies: the predicate is evaluated as written
+ *   MS1 peaks     the stable sort by mass carries the mobility with the intensity
+ *   traces        a spectrum WITH mobility keeps a (peak, window) match only if mobility_hi >= m && mobility_lo <= m
+ *                 (mass_mobility_lookup; a NaN mobility matches nothing); a spectrum without one is traced as by sage_hip_lfq.
+ *                 The order of the contributions, and with it every grid bit, is that of the matches that remain
+ * ms1_mobility: [in->n_ms1] or NULL.  NULL, or no spectrum with mobility in any batch: exactly sage_hip_lfq, every output bit. */
+typedef struct SageLfqMobility {
+    const float* mobility;         /* per peak, indexed like the batch's mz (through its peak_off); NULL: no spectrum has one */
+    const uint8_t* has_mobility;   /* [n_spectra] RawSpectrum.mobility is Some; NULL: every spectrum, when `mobility` is given */
+} SageLfqMobility;
+int sage_hip_lfq_im(int device, const SageLfqInput* in, const SageLfqMobility* ms1_mobility, SageLfqOutput* out);
 
 /* lfq.tsv (sage-cli runner.rs:1182-1235): target grids with a peak, in the order given (rows: indices into the arrays). */
 int sage_hip_write_lfq(const char* path, const SageHostDb* db, const SageLfqOutput* grids, const uint64_t* rows, uint64_t n_rows,

@@ -226,6 +226,10 @@ class SageLfqOutput(C.Structure):
                 ("ms1_ms", C.c_float), ("trace_ms", C.c_float), ("integrate_ms", C.c_float), ("device_ms", C.c_float)]
 
 
+class SageLfqMobility(C.Structure):
+    _fields_ = [("mobility", c_float_p), ("has_mobility", c_u8_p)]
+
+
 class SageTmtInput(C.Structure):
     _fields_ = [("n_batches", C.c_uint32), ("batches", C.POINTER(SageRawBatch)), ("level", C.c_int32), ("n_labels", C.c_uint32),
                 ("labels", c_float_p), ("tolerance", SageTolerance), ("take_top_n", C.c_uint64), ("deisotope", C.c_int32),
@@ -321,6 +325,9 @@ def load():
         "sage_hip_write_results": (C.c_int, [C.c_char_p, C.c_int, vp, vp, C.c_uint64, c_u64_p, c_u64_p, C.POINTER(C.c_char_p),
                                              C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(SagePostColumns)]),
         "sage_hip_lfq": (C.c_int, [C.c_int, C.POINTER(SageLfqInput), C.POINTER(SageLfqOutput)]),
+        "sage_hip_lfq_im": (C.c_int, [C.c_int, C.POINTER(SageLfqInput), C.POINTER(SageLfqMobility), C.POINTER(SageLfqOutput)]),
+        "sage_hip_mzml_mobility": (c_float_p, [vp]),
+        "sage_hip_mzml_has_mobility": (C.c_int, [vp, c_u8_p]),
         "sage_hip_write_lfq": (C.c_int, [C.c_char_p, vp, C.POINTER(SageLfqOutput), c_u64_p, C.c_uint64, C.POINTER(C.c_char_p),
                                          C.c_uint32]),
         "sage_hip_fasta_num_targets": (C.c_int, [C.c_char_p, C.POINTER(SageDbParams), c_u64_p]),
@@ -350,6 +357,7 @@ EXPORTED_SYMBOLS = [
     "sage_hip_lfq", "sage_hip_write_lfq", "sage_hip_mzml_read_sn", "sage_hip_mzml_ion_injection_time", "sage_hip_mzml_precursor_ref",
     "sage_hip_tmt", "sage_hip_write_tmt", "sage_hip_mgf_read", "sage_hip_mzml_isolation_kinds", "sage_hip_mzml_charge_zero",
     "sage_hip_parse_f32", "sage_hip_batch_upload_kinds", "sage_hip_batch_process_upload_kinds", "sage_hip_score_batch_kinds",
+    "sage_hip_lfq_im", "sage_hip_mzml_mobility", "sage_hip_mzml_has_mobility",
 ]
 
 

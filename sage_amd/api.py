@@ -309,6 +309,7 @@ class RawSpectrum:  # spectrum.rs:81-106 (MS2, centroided)
     id: str = ""
     ion_injection_time: float = 0.0  # MS:1000927
     precursor_ref: str = ""          # precursors.first().spectrum_ref ("" == None)
+    mobility: Optional[np.ndarray] = None  # per-peak ion mobility of an MS1 spectrum (spectrum.rs:344), None without one
 
 
 @dataclass
@@ -503,12 +504,23 @@ class RawBatch:
         self.file_id = np.ascontiguousarray([s.file_id for s in spectra], dtype=np.uint32)
         self.ion_injection_time = f32([s.ion_injection_time for s in spectra])
         self.precursor_ref = [s.precursor_ref for s in spectra]
+        # per-peak ion mobility (MS1 only): None when no spectrum has one; else 0 inside the spectra without it
+        self.mobility = self.has_mobility = None
+        if any(s.mobility is not None for s in spectra):
+            for s in spectra:
+                if s.mobility is not None and len(s.mobility) != len(s.mz):
+                    raise ValueError(f"spectrum {s.id!r}: {len(s.mobility)} mobilities for {len(s.mz)} peaks")
+            self.mobility = cat([np.zeros(len(s.mz), np.float32) if s.mobility is None else np.asarray(s.mobility, np.float32)
+                                 for s in spectra])
+            self.has_mobility = np.ascontiguousarray([s.mobility is not None for s in spectra], dtype=np.uint8)
 
     @classmethod
     def from_arrays(cls, ids, peak_off, mz, intensities, precursor_mz, precursor_charge, isolation_lo, isolation_hi,
-                    scan_start_time, inverse_ion_mobility, file_id, ion_injection_time=None, precursor_ref=None) -> "RawBatch":
+                    scan_start_time, inverse_ion_mobility, file_id, ion_injection_time=None, precursor_ref=None, mobility=None,
+                    has_mobility=None) -> "RawBatch":
         """Adopt SoA arrays (NaN == None for the optional floats, 0 == unknown charge): what the C++ mzML reader returns.
-        ion_injection_time / precursor_ref default to 0.0 / ""."""
+        ion_injection_time / precursor_ref default to 0.0 / "".  mobility: per peak, like mz (MS1), or None; has_mobility: per
+        spectrum (None with a mobility array: every spectrum has one)."""
         b = cls.__new__(cls)
         b.n = len(precursor_mz)
         b.ids = list(ids)
@@ -523,6 +535,11 @@ class RawBatch:
         b.ion_injection_time = np.zeros(b.n, np.float32) if ion_injection_time is None else f32(ion_injection_time)
         b.precursor_ref = [""] * b.n if precursor_ref is None else list(precursor_ref)
         assert len(b.peak_off) == b.n + 1 and len(b.mz) == len(b.intensities) == int(b.peak_off[-1])
+        b.mobility = b.has_mobility = None
+        if mobility is not None:
+            b.mobility = f32(mobility)
+            b.has_mobility = np.ones(b.n, np.uint8) if has_mobility is None else np.ascontiguousarray(has_mobility, dtype=np.uint8)
+            assert len(b.mobility) == len(b.mz) and len(b.has_mobility) == b.n
         return b
 
     def slice(self, begin: int, end: int) -> "RawBatch":
@@ -532,7 +549,9 @@ class RawBatch:
                                     self.precursor_mz[begin:end], self.precursor_charge[begin:end], self.isolation_lo[begin:end],
                                     self.isolation_hi[begin:end], self.scan_start_time[begin:end],
                                     self.inverse_ion_mobility[begin:end], self.file_id[begin:end],
-                                    self.ion_injection_time[begin:end], self.precursor_ref[begin:end])
+                                    self.ion_injection_time[begin:end], self.precursor_ref[begin:end],
+                                    None if self.mobility is None else self.mobility[a:b],
+                                    None if self.mobility is None else self.has_mobility[begin:end])
 
     def subset(self, idx) -> "RawBatch":
         """The spectra at positions `idx` as a batch of their own (a shard that is not contiguous in the file: sharding.plan_mass_shards)."""
@@ -545,7 +564,9 @@ class RawBatch:
         return RawBatch.from_arrays([self.ids[i] for i in idx], off, self.mz[gather], self.intensities[gather], self.precursor_mz[idx],
                                     self.precursor_charge[idx], self.isolation_lo[idx], self.isolation_hi[idx], self.scan_start_time[idx],
                                     self.inverse_ion_mobility[idx], self.file_id[idx], self.ion_injection_time[idx],
-                                    [self.precursor_ref[i] for i in idx])
+                                    [self.precursor_ref[i] for i in idx],
+                                    None if self.mobility is None else self.mobility[gather],
+                                    None if self.mobility is None else self.has_mobility[idx])
 
     def spectrum(self, i: int) -> RawSpectrum:
         lo, hi = int(self.peak_off[i]), int(self.peak_off[i + 1])
@@ -553,7 +574,8 @@ class RawBatch:
         ims = None if np.isnan(self.inverse_ion_mobility[i]) else float(self.inverse_ion_mobility[i])
         return RawSpectrum(self.mz[lo:hi], self.intensities[lo:hi], float(self.precursor_mz[i]),
                            int(self.precursor_charge[i]) or None, iso, float(self.scan_start_time[i]), ims, int(self.file_id[i]),
-                           self.ids[i], float(self.ion_injection_time[i]), self.precursor_ref[i])
+                           self.ids[i], float(self.ion_injection_time[i]), self.precursor_ref[i],
+                           self.mobility[lo:hi] if self.mobility is not None and self.has_mobility[i] else None)
 
     def to_c(self):
         b = L.SageRawBatch()
@@ -942,11 +964,13 @@ class LfqResult:
 
 
 def lfq(features: np.ndarray, order, aligned_rt, peptide_q, alignments: np.ndarray, ms1: Sequence[RawBatch], carbon, sulfur,
-        settings: LfqSettings, precursor_charge, device: int = 0, debug: bool = False) -> LfqResult:
+        settings: LfqSettings, precursor_charge, device: int = 0, debug: bool = False, ion_mobility: bool = False) -> LfqResult:
     """build_feature_map(..).quantify(..) + picked_precursor (sage-cli runner.rs:562-575) on the device.
     features / aligned_rt / peptide_q: the run's PSMs (input order) and their rescoring outputs; order: confidence order
     (RescoreResult.order) or None; alignments: RtPrediction.alignments; ms1: raw MS1 spectra (RawBatch per file, file_id set);
-    carbon / sulfur: peptide_compositions of the database.  debug: also the warps and the grid matrices."""
+    carbon / sulfur: peptide_compositions of the database.  debug: also the warps and the grid matrices.
+    ion_mobility: sage_hip_lfq_im (lfq_im) instead of sage_hip_lfq — the batches' per-peak mobility columns and the features'
+    `ims` take part."""
     f = np.ascontiguousarray(features, dtype=L.FEATURE_DTYPE).reshape(-1)
     n = len(f)
     order_a = None if order is None else np.ascontiguousarray(order, dtype=np.uint32)
@@ -974,7 +998,15 @@ def lfq(features: np.ndarray, order, aligned_rt, peptide_q, alignments: np.ndarr
     cout.warps = L.as_ptr(r.warps, C.c_int32)
     if debug:
         cout.matrix = L.as_ptr(r.matrix, C.c_double)
-    L.check(L.load().sage_hip_lfq(device, C.byref(cin), C.byref(cout)))
+    if ion_mobility:
+        mob = (L.SageLfqMobility * max(len(ms1), 1))()
+        for k, b in enumerate(ms1):
+            if b.mobility is not None:
+                mob[k].mobility = L.as_ptr(b.mobility, C.c_float)
+                mob[k].has_mobility = L.as_ptr(b.has_mobility, C.c_uint8)
+        L.check(L.load().sage_hip_lfq_im(device, C.byref(cin), mob, C.byref(cout)))
+    else:
+        L.check(L.load().sage_hip_lfq(device, C.byref(cin), C.byref(cout)))
     g = int(cout.n_grids)
     for k in ("peptide_idx", "charge", "decoy", "has_peak", "peak_rt", "left", "right", "score", "spectral_angle", "q_value",
               "areas", "warps", "matrix"):
@@ -985,6 +1017,16 @@ def lfq(features: np.ndarray, order, aligned_rt, peptide_q, alignments: np.ndarr
     r.stage_ms = {"build_ms": float(cout.build_ms), "ms1_ms": float(cout.ms1_ms), "trace_ms": float(cout.trace_ms),
                   "integrate_ms": float(cout.integrate_ms), "device_ms": float(cout.device_ms)}
     return r
+
+
+def lfq_im(features, order, aligned_rt, peptide_q, alignments, ms1, carbon, sulfur, settings, precursor_charge, device: int = 0,
+           debug: bool = False) -> LfqResult:
+    """lfq for ion-mobility MS1 spectra (sage_hip_lfq_im; lfq.rs:111-127, 267-286, 677-686): every window carries
+    Tolerance::Pct(-t, t).bounds(feature.ims), t = settings.mobility_pct_tolerance, and a spectrum whose RawBatch has a mobility
+    column keeps a (peak, window) match only if the peak's mobility lies inside.  Spectra without the column are traced as by
+    lfq; with no mobility column anywhere the result is lfq's, bit for bit."""
+    return lfq(features, order, aligned_rt, peptide_q, alignments, ms1, carbon, sulfur, settings, precursor_charge, device, debug,
+               ion_mobility=True)
 
 
 # ---- TMT reporter-ion quantification (sage_hip_tmt) ----------------------------------------------------------------------------

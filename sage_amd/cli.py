@@ -495,14 +495,17 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         if not ms1_batches:
             log("no MS1 spectra found for quantification")  # lfq.rs:233
         carbon, sulfur = peptide_compositions(host.seq_off, host.seq)
+        # MS1 spectra with a per-peak ion-mobility array (timsTOF mzML): sage_hip_lfq_im, which reads the features' `ims` and
+        # lfq_settings.mobility_pct_tolerance (lfq.rs:111-127, 267-286); without one in any file, sage_hip_lfq as before
+        with_mobility = any(b.mobility is not None for b in ms1_batches)
         lfq_result = lfq(flat, post.order, rtp.aligned_rt, post.peptide_q, rtp.alignments, ms1_batches, carbon, sulfur,
-                         lfq_settings, sp["precursor_charge"], device=device)
+                         lfq_settings, sp["precursor_charge"], device=device, ion_mobility=with_mobility)
         log(f"discovered {lfq_result.passing} target MS1 peaks at 5% FDR")
         lfq_ms = (time.time() - t0) * 1000.0
         log(f"- label-free quantification: {int(lfq_ms):8d} ms")
         lfq_summary = {"q_precursor": lfq_result.passing, "lfq_grids": len(lfq_result.peptide_idx),
                        "lfq_windows": lfq_result.n_windows, "lfq_ms": lfq_ms, "lfq_device_ms": lfq_result.stage_ms["device_ms"],
-                       "lfq_stage_ms": lfq_result.stage_ms,
+                       "lfq_stage_ms": lfq_result.stage_ms, "lfq_ion_mobility": with_mobility,
                        "alignments": [{k: float(a[k]) if k != "file_id" else int(a[k]) for k in a.dtype.names}
                                       for a in rtp.alignments]}
     # writers: C++ (sage_hip_write_results) — byte-identical to output.feature_row / pin_row, which tests/test_cli_io.py checks

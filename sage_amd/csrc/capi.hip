@@ -309,7 +309,9 @@ int sage_hip_predict_rt(int device, const SageRtInput* in, SageRtOutput* out) {
     return rc == SAGE_HIP_OK ? rc : fail(rc, err);
 }
 
-int sage_hip_lfq(int device, const SageLfqInput* in, SageLfqOutput* out) {
+int sage_hip_lfq(int device, const SageLfqInput* in, SageLfqOutput* out) { return sage_hip_lfq_im(device, in, nullptr, out); }
+
+int sage_hip_lfq_im(int device, const SageLfqInput* in, const SageLfqMobility* ms1_mobility, SageLfqOutput* out) {
     if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: null argument");
     if (sage_hip_device_count() <= 0) return fail(SAGE_HIP_ERR_NO_DEVICE, "sage_hip_lfq: no HIP device (there is no CPU fallback)");
     const SageLfqSettings& st = in->settings;
@@ -328,7 +330,7 @@ int sage_hip_lfq(int device, const SageLfqInput* in, SageLfqOutput* out) {
         if (in->ms1[b].n_spectra && (!in->ms1[b].peak_off || !in->ms1[b].mz || !in->ms1[b].intensities))
             return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: null MS1 array");
     std::string err;
-    const int rc = lfq_on_device(device, *in, *out, err);
+    const int rc = lfq_on_device(device, *in, ms1_mobility, *out, err);
     return rc == SAGE_HIP_OK ? rc : fail(rc, err);
 }
 
@@ -498,6 +500,16 @@ float sage_hip_mzml_ion_injection_time(const SageMzml* run, uint64_t i) {
 const char* sage_hip_mzml_precursor_ref(const SageMzml* run, uint64_t i) {
     if (!run || i >= run->run.n()) return nullptr;
     return run->run.precursor_refs.data() + run->run.ref_off[i];
+}
+const float* sage_hip_mzml_mobility(const SageMzml* run) {
+    if (!run || run->run.has_mobility.empty()) return nullptr;
+    return run->run.mobility.data();
+}
+int sage_hip_mzml_has_mobility(const SageMzml* run, uint8_t* out) {
+    if (!run || (!out && run->run.n())) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mzml_has_mobility: null argument");
+    const MzmlRun& r = run->run;
+    for (uint64_t i = 0; i < r.n(); ++i) out[i] = r.has_mobility.empty() ? 0 : r.has_mobility[i];
+    return SAGE_HIP_OK;
 }
 void sage_hip_mzml_free(SageMzml* run) { delete run; }
 int sage_hip_mgf_read(const char* path, uint32_t file_id, SageMzml** out) {

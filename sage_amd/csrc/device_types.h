@@ -276,7 +276,7 @@ int build_peptide_mass_lut(const float* d_pep_mono, uint32_t np, float top_mass,
 int rescore_on_device(int device, const SageRescoreInput& in, SageRescoreOutput& out, std::string& err);
 int predict_rt_on_device(int device, const SageRtInput& in, SageRtOutput& out, std::string& err);
 // lfq.hip
-int lfq_on_device(int device, const SageLfqInput& in, SageLfqOutput& out, std::string& err);
+int lfq_on_device(int device, const SageLfqInput& in, const SageLfqMobility* mobility, SageLfqOutput& out, std::string& err);
 // tmt.hip: reporter-ion extraction, one wavefront per spectrum (peaks [off[i], off[i+1]); subtract_proton: the array holds raw
 // m/z); lo / hi: each label's window with the offset applied; region: [min lo, max hi].  out_*: [n * n_labels]
 void launch_tmt_extract(uint32_t n, const uint64_t* off, const float* mass_or_mz, const float* inten, bool subtract_proton,

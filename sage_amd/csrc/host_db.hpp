@@ -90,6 +90,8 @@ struct MzmlRun {
     std::vector<uint64_t> ref_off{0};  // [n + 1] into precursor_refs
     std::vector<uint8_t> iso_kind;     // SAGE_TOL_* of isolation_lo / hi; empty == all SAGE_TOL_DA (mzML)
     std::vector<uint8_t> charge_zero;  // precursors[0].charge == Some(0) (MGF `CHARGE=0`); empty == none
+    std::vector<float> mobility;       // per peak, like mz: the ion-mobility array of MS1 spectra; empty == no spectrum has one
+    std::vector<uint8_t> has_mobility; // [n] RawSpectrum.mobility is Some; empty == none
     uint64_t n() const { return precursor_mz.size(); }
 };
 bool read_mzml(const char* path, uint32_t file_id, int ms_level, int sn_level, MzmlRun& run, std::string& err);

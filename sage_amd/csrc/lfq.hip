@@ -1,6 +1,7 @@
 // lfq.hip — label-free MS1 quantification on the device: sage-core lfq.rs (build_feature_map, FeatureMap::quantify,
 // Grid::add_entry / summarize_traces, Traces::integrate), isotopes.rs and fdr::picked_precursor (fdr.rs:228-287), for MS1
-// spectra without ion mobility.  The C entry point is sage_hip_lfq (include/sage_hip.h).
+// spectra without ion mobility (sage_hip_lfq) and with a per-peak mobility column (sage_hip_lfq_im: lfq.rs:111-127, 267-286,
+// 677-686, spectrum.rs:344-378).  The C entry points are in include/sage_hip.h.
 //
 // Stages, all on one stream:
 //   feature map   host: the first confident target feature per peptide (confidence order), per-grid constants (rt_min,
@@ -18,6 +19,11 @@
 //                 `>=` keeps the last best offset), scores, best bin, peak bounds, Sum / Apex areas.  Only + * / sqrt on f64
 //                 besides acos (the device's ocml acos); the RT factor powf(0.33) comes from a host table.
 //   q-values      host: picked_precursor over the grids with a peak, a stable sort by f32 score in grid order.
+// Ion mobility (only when a spectrum of the call has the column; otherwise none of it is allocated, launched or compiled into the
+// kernels that run): one (mobility_lo, mobility_hi) record per selected feature, gathered per window through the same
+// permutation as the mass bounds; the peaks' mobilities gathered through the MS1 sort's permutation; count / fill as the
+// IM = true instances of the same templates, which read a window's record only after the four predicates of mass_lookup have
+// passed, and test it only in spectra that have mobility.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -164,7 +170,24 @@ __global__ void gather_windows_kernel(uint32_t n_windows, const uint32_t* __rest
     w_lo_key[j] = total_key(g_lo[g]);
 }
 
-// ---- MS1 peaks (spectrum.rs:380-412, no mobility) -------------------------------------------------------------------------
+// Tolerance::Pct(-pct, pct).bounds(feat.ims) of every selected feature (lfq.rs:111-115); x = mobility_lo, y = mobility_hi
+__global__ void mobility_bounds_kernel(uint32_t n_sel, float pct, const float* __restrict__ sel_ims, float2* __restrict__ sel_mob) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_sel) return;
+    float lo, hi;
+    sagecore::tol_bounds(sagecore::Tol{1, -pct, pct}, sel_ims[s], lo, hi);
+    sel_mob[s] = make_float2(lo, hi);
+}
+
+// every charge x isotope x forward/decoy window of a feature inherits its bounds (`..range`, `..fwd`: lfq.rs:145-164)
+__global__ void gather_mobility_kernel(uint32_t n_windows, uint32_t per_feature, const uint32_t* __restrict__ gen,
+                                       const float2* __restrict__ sel_mob, float2* __restrict__ w_mob) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_windows) return;
+    w_mob[j] = sel_mob[gen[j] / per_feature];
+}
+
+// ---- MS1 peaks (spectrum.rs:380-412; with mobility :344-378) ------------------------------------------------------------------
 __global__ void ms1_keys_kernel(uint64_t n, const float* __restrict__ mz, uint32_t* __restrict__ keys, uint32_t* __restrict__ idx) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -178,6 +201,14 @@ __global__ void ms1_gather_kernel(uint64_t n, const uint32_t* __restrict__ keys,
     if (i >= n) return;
     mass[i] = from_total_key(keys[i]);
     inten_out[i] = inten[idx[i]];
+}
+
+// the third column of spectrum.rs:346-362: the sort's permutation applied to the mobilities
+__global__ void ms1_gather_mobility_kernel(uint64_t n, const uint32_t* __restrict__ idx, const float* __restrict__ mob,
+                                           float* __restrict__ mob_out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    mob_out[i] = mob[idx[i]];
 }
 
 // ---- traces ---------------------------------------------------------------------------------------------------------------
@@ -204,9 +235,17 @@ struct WindowsDev {
     uint32_t n;
 };
 
-// Query::mass_lookup (lfq.rs:538-551) for one peak; f(window index) per match, in match order
-template <class F>
-__device__ inline void lookup(const WindowsDev& w, const SpecDev& sp, float mass, F&& f) {
+struct MobilityDev {  // read by the IM = true instances only
+    const float2* window;      // [windows] (mobility_lo, mobility_hi), in the windows' final order
+    const float* peak;         // [peaks] in sorted order
+    const uint8_t* spectrum;   // [spectra] the spectrum has mobility
+};
+
+// Query::mass_lookup (lfq.rs:538-551) for one peak; f(window index) per match, in match order.  IM: mass_mobility_lookup
+// (lfq.rs:677-686) when the peak's spectrum has mobility (`use_mob`), mass_lookup otherwise — the choice of lfq.rs:267.
+template <bool IM, class F>
+__device__ inline void lookup(const WindowsDev& w, const MobilityDev& md, const SpecDev& sp, float mass, bool use_mob, float mob,
+                              F&& f) {
     const float min_rt = sp.rt - RT_TOL, max_rt = sp.rt + RT_TOL;
     const uint32_t klo = total_key(mass - 0.1f), khi = total_key(mass + 0.1f);
     for (uint32_t page = sp.page_lo; page < sp.page_hi; ++page) {
@@ -216,7 +255,15 @@ __device__ inline void lookup(const WindowsDev& w, const SpecDev& sp, float mass
         search_keys(w.lo_key + a, b - a, klo, khi, il, ir);
         for (uint32_t e = a + il; e < a + ir; ++e) {
             const float rt = w.rt[e];
-            if (rt <= max_rt && rt >= min_rt && mass >= w.lo[e] && mass <= w.hi[e]) f(e);
+            if (rt <= max_rt && rt >= min_rt && mass >= w.lo[e] && mass <= w.hi[e]) {
+                if constexpr (IM) {
+                    if (use_mob) {
+                        const float2 b = md.window[e];
+                        if (!(b.y >= mob && b.x <= mob)) continue;
+                    }
+                }
+                f(e);
+            }
         }
     }
 }
@@ -231,14 +278,22 @@ __device__ inline uint32_t spectrum_of(const uint64_t* peak_off, uint32_t n_spec
     return a;
 }
 
+template <bool IM>
 __global__ void count_kernel(uint64_t n_peaks, const uint64_t* __restrict__ peak_off, uint32_t n_spec,
-                             const SpecDev* __restrict__ spec, const float* __restrict__ mass, WindowsDev w,
+                             const SpecDev* __restrict__ spec, const float* __restrict__ mass, WindowsDev w, MobilityDev md,
                              uint32_t* __restrict__ counts) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_peaks) return;
-    const SpecDev sp = spec[spectrum_of(peak_off, n_spec, i)];
+    const uint32_t s = spectrum_of(peak_off, n_spec, i);
+    const SpecDev sp = spec[s];
+    bool use_mob = false;
+    float mob = 0.0f;
+    if constexpr (IM) {
+        use_mob = md.spectrum[s] != 0;
+        mob = md.peak[i];
+    }
     uint32_t c = 0;
-    lookup(w, sp, mass[i], [&](uint32_t) { ++c; });
+    lookup<IM>(w, md, sp, mass[i], use_mob, mob, [&](uint32_t) { ++c; });
     counts[i] = c;
 }
 
@@ -251,9 +306,10 @@ struct SlotMap {  // window generation index -> grid slot (peptide, charge unles
     }
 };
 
+template <bool IM>
 __global__ void fill_kernel(uint64_t n_peaks, const uint64_t* __restrict__ peak_off, uint32_t n_spec,
                             const SpecDev* __restrict__ spec, const uint32_t* __restrict__ spec_file,
-                            const float* __restrict__ mass, const float* __restrict__ inten, WindowsDev w, SlotMap sm,
+                            const float* __restrict__ mass, const float* __restrict__ inten, WindowsDev w, MobilityDev md, SlotMap sm,
                             const uint64_t* __restrict__ offsets, uint32_t* __restrict__ cell_key, uint32_t* __restrict__ cidx,
                             float* __restrict__ c_rt, float* __restrict__ c_int, uint8_t* __restrict__ slot_hit) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -263,7 +319,13 @@ __global__ void fill_kernel(uint64_t n_peaks, const uint64_t* __restrict__ peak_
     const uint32_t file = spec_file[s];
     const float it = inten[i];
     uint64_t c = offsets[i];
-    lookup(w, sp, mass[i], [&](uint32_t e) {
+    bool use_mob = false;
+    float mob = 0.0f;
+    if constexpr (IM) {
+        use_mob = md.spectrum[s] != 0;
+        mob = md.peak[i];
+    }
+    lookup<IM>(w, md, sp, mass[i], use_mob, mob, [&](uint32_t e) {
         const uint32_t g = w.gen[e];
         const uint32_t slot = sm.slot(g);
         const uint32_t iso = (g >> 1) % N_ISO;
@@ -540,8 +602,14 @@ bool radix(LfqCtx& cx, Launch&& launch) {  // the two-call rocPRIM protocol
 
 inline uint32_t blocks(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 
-bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, SageLfqOutput& out) {
+bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobility, SageLfqOutput& out) {
     const SageLfqSettings& st = in.settings;
+    // ion mobility takes part only if some spectrum of the call has the column (lfq.rs:267 decides per spectrum)
+    bool im = false;
+    for (uint32_t b = 0; mobility && !im && b < in.n_ms1; ++b) {
+        if (!mobility[b].mobility) continue;
+        for (uint32_t i = 0; !im && i < in.ms1[b].n_spectra; ++i) im = !mobility[b].has_mobility || mobility[b].has_mobility[i];
+    }
     const uint32_t F = in.n_files;
     const uint32_t zmin = st.min_charge, nz = (uint32_t)st.max_charge - st.min_charge + 1;
     const bool combine = st.combine_charge_states != 0;
@@ -570,13 +638,14 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, SageLfqOutput& out) {
         }
     }
     std::vector<uint32_t> sel_pep;
-    std::vector<float> sel_rt, sel_mass;
+    std::vector<float> sel_rt, sel_mass, sel_ims;
     for (uint64_t p = 0; p < in.n_peptides; ++p)
         if (seen[p]) {
             const uint32_t i = first[p];
             sel_pep.push_back((uint32_t)p);
             sel_rt.push_back(in.aligned_rt[i]);
             sel_mass.push_back(in.features[i].calcmass);
+            if (im) sel_ims.push_back(in.features[i].ims);
             pick.push_back(i);
         }
     const uint64_t S = sel_pep.size();
@@ -640,6 +709,17 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, SageLfqOutput& out) {
                                                                    w_lo_key.p);
         LQ_TRY(hipGetLastError());
     }
+    DBuf<float> d_sel_ims;
+    DBuf<float2> d_sel_mob, w_mob;
+    if (im && W) {
+        LQ_TRY(d_sel_ims.alloc(S));
+        LQ_TRY(d_sel_mob.alloc(S));
+        LQ_TRY(w_mob.alloc(W));
+        LQ_TRY(hipMemcpyAsync(d_sel_ims.p, sel_ims.data(), S * 4, hipMemcpyHostToDevice, cx.stream));
+        mobility_bounds_kernel<<<blocks(S, TB), TB, 0, cx.stream>>>((uint32_t)S, st.mobility_pct_tolerance, d_sel_ims.p, d_sel_mob.p);
+        gather_mobility_kernel<<<blocks(W, TB), TB, 0, cx.stream>>>(W, nz * N_ISO * 2, gen.p, d_sel_mob.p, w_mob.p);
+        LQ_TRY(hipGetLastError());
+    }
     LQ_TRY(hipEventRecord(ev.e[1], cx.stream));
 
     // -- MS1 spectra: concatenated in the order given
@@ -657,6 +737,8 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, SageLfqOutput& out) {
     std::vector<uint64_t> h_off(n_spec + 1, 0);
     std::vector<float> h_mz(n_peaks), h_int(n_peaks), h_sst(n_spec);
     std::vector<uint32_t> h_file(n_spec);
+    std::vector<uint8_t> h_has(im ? n_spec : 0, 0);  // per spectrum: it has mobility
+    std::vector<uint64_t> batch_p0(in.n_ms1 + 1, 0);  // first peak of every batch in the concatenation
     {
         uint64_t s0 = 0, p0 = 0;
         for (uint32_t b = 0; b < in.n_ms1; ++b) {
@@ -670,6 +752,7 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, SageLfqOutput& out) {
                 }
                 std::memcpy(&h_mz[p0], r.mz + lo, (hi - lo) * 4);
                 std::memcpy(&h_int[p0], r.intensities + lo, (hi - lo) * 4);
+                if (im && mobility[b].mobility && (!mobility[b].has_mobility || mobility[b].has_mobility[i])) h_has[s0] = 1;
                 p0 += hi - lo;
                 h_off[s0 + 1] = p0;
                 h_sst[s0] = r.scan_start_time ? r.scan_start_time[i] : 0.0f;
@@ -681,6 +764,7 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, SageLfqOutput& out) {
                 }
                 ++s0;
             }
+            batch_p0[b + 1] = p0;
         }
     }
     DBuf<uint64_t> d_off;
@@ -713,6 +797,27 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, SageLfqOutput& out) {
         ms1_gather_kernel<<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, mks.p, mis.p, d_int_raw.p, d_mass.p, d_int.p);
         LQ_TRY(hipGetLastError());
     }
+    DBuf<float> d_mob_raw, d_mob;
+    DBuf<uint8_t> d_spec_mob;
+    if (im && n_peaks) {
+        LQ_TRY(d_mob_raw.alloc(n_peaks));
+        LQ_TRY(d_mob.alloc(n_peaks));
+        LQ_TRY(d_spec_mob.alloc(n_spec));
+        // The column of a batch goes up as it lies in the caller's array: peak_off ascends, so the peaks of a batch are one
+        // range of it (no host copy of a third of the MS1 data).  The values inside spectra without mobility are never tested.
+        for (uint32_t b = 0; b < in.n_ms1; ++b) {
+            const uint64_t n = batch_p0[b + 1] - batch_p0[b];
+            if (!n) continue;
+            if (mobility[b].mobility)
+                LQ_TRY(hipMemcpyAsync(d_mob_raw.p + batch_p0[b], mobility[b].mobility + in.ms1[b].peak_off[0], n * 4,
+                                      hipMemcpyHostToDevice, cx.stream));
+            else
+                LQ_TRY(hipMemsetAsync(d_mob_raw.p + batch_p0[b], 0, n * 4, cx.stream));
+        }
+        LQ_TRY(hipMemcpyAsync(d_spec_mob.p, h_has.data(), n_spec, hipMemcpyHostToDevice, cx.stream));
+        ms1_gather_mobility_kernel<<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, mis.p, d_mob_raw.p, d_mob.p);
+        LQ_TRY(hipGetLastError());
+    }
     LQ_TRY(hipEventRecord(ev.e[2], cx.stream));
 
     // -- traces
@@ -725,11 +830,13 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, SageLfqOutput& out) {
     LQ_TRY(counts.alloc(n_peaks));
     LQ_TRY(offs.alloc(n_peaks + 1));
     WindowsDev wd{w_rt.p, w_lo.p, w_hi.p, w_lo_key.p, gen.p, W};
+    const MobilityDev md{w_mob.p, d_mob.p, d_spec_mob.p};
     uint64_t M = 0;
     if (n_peaks && W) {
         spectrum_setup_kernel<<<blocks(n_spec, TB), TB, 0, cx.stream>>>(n_spec, d_sst.p, d_file.p, d_al.p, min_rt_key.p, n_pages,
                                                                         d_spec.p);
-        count_kernel<<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, d_off.p, n_spec, d_spec.p, d_mass.p, wd, counts.p);
+        if (im) count_kernel<true><<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, d_off.p, n_spec, d_spec.p, d_mass.p, wd, md, counts.p);
+        else count_kernel<false><<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, d_off.p, n_spec, d_spec.p, d_mass.p, wd, md, counts.p);
         LQ_TRY(hipGetLastError());
         if (!radix(cx, [&](void* t, size_t& b) {
                 return rocprim::inclusive_scan(t, b, counts.p, offs.p + 1, (size_t)n_peaks, rocprim::plus<uint64_t>(), cx.stream);
@@ -757,8 +864,12 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, SageLfqOutput& out) {
     uint32_t n_grids = 0;
     if (M) {
         SlotMap sm{nz, combine ? 1u : 0u, (uint32_t)rows_per_slot};
-        fill_kernel<<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, d_off.p, n_spec, d_spec.p, d_file.p, d_mass.p, d_int.p, wd, sm,
-                                                              offs.p, ckey.p, cidx.p, c_rt.p, c_int.p, slot_hit.p);
+        if (im)
+            fill_kernel<true><<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, d_off.p, n_spec, d_spec.p, d_file.p, d_mass.p, d_int.p,
+                                                                        wd, md, sm, offs.p, ckey.p, cidx.p, c_rt.p, c_int.p, slot_hit.p);
+        else
+            fill_kernel<false><<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, d_off.p, n_spec, d_spec.p, d_file.p, d_mass.p, d_int.p,
+                                                                         wd, md, sm, offs.p, ckey.p, cidx.p, c_rt.p, c_int.p, slot_hit.p);
         LQ_TRY(hipGetLastError());
         // stable: the contributions of one matrix row stay in (spectrum, peak, match) order
         if (!radix(cx, [&](void* t, size_t& b) {
@@ -900,7 +1011,7 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, SageLfqOutput& out) {
 
 }  // namespace
 
-int lfq_on_device(int device, const SageLfqInput& in, SageLfqOutput& out, std::string& err) {
+int lfq_on_device(int device, const SageLfqInput& in, const SageLfqMobility* mobility, SageLfqOutput& out, std::string& err) {
     LfqCtx cx;
     if (hipSetDevice(device) != hipSuccess) {
         err = "sage_hip_lfq: hipSetDevice failed";
@@ -910,7 +1021,7 @@ int lfq_on_device(int device, const SageLfqInput& in, SageLfqOutput& out, std::s
         err = cx.err;
         return cx.code;
     }
-    const bool ok = lfq_impl(cx, in, out);
+    const bool ok = lfq_impl(cx, in, mobility, out);
     (void)hipStreamSynchronize(cx.stream);
     (void)hipStreamDestroy(cx.stream);
     if (!ok) {

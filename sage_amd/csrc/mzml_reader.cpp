@@ -15,6 +15,10 @@
 //   * signal-to-noise (sn_level >= 0, :371-381): at that MS level, intensity[i] /= noise[i] (MS:1002744) over the shorter of
 //     the two arrays.  Only the spectrum's OWN noise array divides it: the reference keeps an unused noise array across
 //     spectra and would divide a later spectrum that has none; a spectrum without one keeps its intensities.
+//   * per-peak ion mobility of MS1 spectra — an addition: the reference's mzML reader ignores the array, its RawSpectrum.mobility
+//     comes from the Bruker reader only.  A binaryDataArray that carries one of the ion-mobility array accessions (is_mobility_array)
+//     and is neither m/z, intensity nor noise is the mobility column of a spectrum whose ms level is 1 (spectrum.rs:344 uses it at
+//     level 1 only); decoded like the others, stored as f32.  A length other than the m/z array's is an error for the file.
 // No XML library: mzML's spectrum blocks are flat enough for a tag scanner (attributes in single or double quotes, the five
 // predefined entities in attribute values, namespace prefixes stripped).
 #include <zlib.h>
@@ -194,13 +198,20 @@ bool inflate_all(const std::vector<uint8_t>& in, std::vector<uint8_t>& out) {
 // tag.  false: malformed (err says why; `unterminated`: the input ended inside the block).
 struct SpectrumOut {
     std::string id;
-    std::vector<float> mz, inten;
+    std::vector<float> mz, inten, mobility;
+    bool has_mobility = false;  // an ion-mobility array at ms level 1 (RawSpectrum.mobility is Some)
     std::string precursor_ref;  // spectrumRef of the kept precursor ("" when absent)
     float scan_start = 0.0f, prec_mz = 0.0f, prec_ims = NAN, iso_lo = NAN, iso_hi = NAN, ion_injection_time = 0.0f;
     uint8_t prec_charge = 0;
     bool have_precursor = false, have_lo = false, have_hi = false, centroid = false, keep = false;
     int level = 0;
 };
+// the ion-mobility array terms of the PSI-MS vocabulary: ion mobility array, mean ion mobility array, mean inverse reduced ion
+// mobility array, raw ion mobility array, raw inverse reduced ion mobility array (matched by accession only)
+bool is_mobility_array(std::string_view acc) {
+    return acc == "MS:1002893" || acc == "MS:1002816" || acc == "MS:1003006" || acc == "MS:1003007" || acc == "MS:1003008";
+}
+
 bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, int sn_level, SpectrumOut& o, std::string& err,
                     bool& unterminated) {
     std::vector<uint8_t> raw, plain;
@@ -219,13 +230,13 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, int sn_l
     uint8_t p_z = 0;
     int precursor_depth = 0, scan_depth = 0, bda_depth = 0;
     bool bda_f32 = false, bda_zlib = false;
-    int bda_kind = 0;  // 1 m/z, 2 intensity, 3 noise
+    int bda_kind = 0;  // 1 m/z, 2 intensity, 3 noise, 4 ion mobility
     std::string_view bda_text;
     struct Pending {
         std::string_view text;
         bool f32, zlib, set;
-    } pending[3] = {{std::string_view(), false, false, false}, {std::string_view(), false, false, false},
-                    {std::string_view(), false, false, false}};
+    } pending[4] = {{std::string_view(), false, false, false}, {std::string_view(), false, false, false},
+                    {std::string_view(), false, false, false}, {std::string_view(), false, false, false}};
     bool closed = t.self_closing;
     while (!closed && next_tag(p, e, t)) {
         if (t.closing) {
@@ -298,7 +309,8 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, int sn_l
                 } else if (in_bda && child_depth == bda_depth + 1) {
                     if (acc == "MS:1000514") bda_kind = 1;
                     else if (acc == "MS:1000515" && bda_kind != 1) bda_kind = 2;
-                    else if (acc == "MS:1002744" && bda_kind == 0) bda_kind = 3;  // (noise only when neither of the above)
+                    else if (acc == "MS:1002744" && (bda_kind == 0 || bda_kind == 4)) bda_kind = 3;  // (noise only when neither of the above)
+                    else if (is_mobility_array(acc) && bda_kind == 0) bda_kind = 4;  // (mobility only when none of the three)
                     else if (acc == "MS:1000574") bda_zlib = true;
                     else if (acc == "MS:1000521") bda_f32 = true;
                 } else if (child_depth == 2) {  // direct children of <spectrum>
@@ -356,10 +368,11 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, int sn_l
     o.keep = !(tic_zero || (ms_level >= 0 && (!have_level || level != ms_level)));
     o.id.swap(id);
     if (o.keep) {
-        std::vector<float> noise;
+        std::vector<float> noise, mobility;
         const bool sn = sn_level >= 0 && have_level && level == sn_level;
-        for (int k = 0; k < (sn ? 3 : 2); ++k) {
-            if (!pending[k].set) continue;
+        const bool im = have_level && level == 1;
+        for (int k = 0; k < 4; ++k) {
+            if (!pending[k].set || (k == 2 && !sn) || (k == 3 && !im)) continue;
             base64_decode(pending[k].text, raw);
             const std::vector<uint8_t>* bytes = &raw;
             if (pending[k].zlib) {
@@ -369,7 +382,7 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, int sn_l
                 }
                 bytes = &plain;
             }
-            std::vector<float>& dst = k == 0 ? mz : k == 1 ? inten : noise;
+            std::vector<float>& dst = k == 0 ? mz : k == 1 ? inten : k == 2 ? noise : mobility;
             if (pending[k].f32) {
                 dst.resize(bytes->size() / 4);
                 std::memcpy(dst.data(), bytes->data(), dst.size() * 4);
@@ -385,6 +398,15 @@ bool parse_spectrum(Tag t, const char*& p, const char* e, int ms_level, int sn_l
         const size_t n_sn = std::min(inten.size(), noise.size());  // (zipped: the shorter array decides)
         for (size_t i = 0; i < n_sn; ++i) inten[i] /= noise[i];
         inten.resize(mz.size(), 0.0f);  // (a spectrum with arrays of different lengths is malformed; keep the peak table rectangular)
+        if (im && pending[3].set) {
+            if (mobility.size() != mz.size()) {
+                err = "malformed mzML: ion mobility array of spectrum " + o.id + " holds " + std::to_string(mobility.size()) +
+                      " values for " + std::to_string(mz.size()) + " m/z values";
+                return false;
+            }
+            o.has_mobility = true;
+            o.mobility.swap(mobility);
+        }
         o.mz.swap(mz);
         o.inten.swap(inten);
     }
@@ -572,6 +594,12 @@ bool read_mzml(const char* path, uint32_t file_id, int ms_level, int sn_level, M
             id_bytes += outs[i].id.size() + 1;
         }
     const size_t n_keep = kept.size();
+    bool any_mobility = false;
+    for (size_t j : kept) any_mobility = any_mobility || outs[j].has_mobility;
+    if (any_mobility) {  // (peaks of spectra without the array hold 0; has_mobility tells them apart)
+        run.mobility.assign(n_peaks, 0.0f);
+        run.has_mobility.assign(n_keep, 0);
+    }
     run.mz.resize(n_peaks);
     run.intensities.resize(n_peaks);
     run.precursor_mz.resize(n_keep);
@@ -592,6 +620,11 @@ bool read_mzml(const char* path, uint32_t file_id, int ms_level, int sn_level, M
             if (!o.mz.empty()) {
                 std::memcpy(run.mz.data() + at, o.mz.data(), o.mz.size() * sizeof(float));
                 std::memcpy(run.intensities.data() + at, o.inten.data(), o.inten.size() * sizeof(float));
+            }
+            if (o.has_mobility) {
+                run.has_mobility[j] = 1;
+                if (!o.mobility.empty()) std::memcpy(run.mobility.data() + at, o.mobility.data(), o.mobility.size() * sizeof(float));
+                std::vector<float>().swap(o.mobility);
             }
             run.precursor_mz[j] = o.prec_mz;
             run.precursor_charge[j] = o.prec_charge;

@@ -105,15 +105,59 @@ def synthetic_lcms(db: IndexedDatabase, n_files: int = 3, n_peptides: int = 40, 
     return files
 
 
-def write_lcms(directory: str, files: List[LcmsFile], stem: str = "run") -> List[str]:
+def write_lcms(directory: str, files: List[LcmsFile], stem: str = "run", mobility=None) -> List[str]:
+    """mobility: per file, write_mzml's per-spectrum ion-mobility arrays (synthetic_ion_mobility), or None"""
     from .mzml import write_mzml
     os.makedirs(directory, exist_ok=True)
     paths = []
     for f, lf in enumerate(files):
         path = os.path.join(directory, f"{stem}{f}.mzML")
-        write_mzml(path, lf.spectra, lf.ms_levels)
+        if mobility is None or mobility[f] is None:
+            write_mzml(path, lf.spectra, lf.ms_levels)
+        else:
+            write_mzml(path, lf.spectra, lf.ms_levels, mobility=mobility[f])
         paths.append(path)
     return paths
+
+
+def synthetic_ion_mobility(db: IndexedDatabase, files: List[LcmsFile], seed: int = 0, spread_pct: float = 1.5, ppm: float = 15.0,
+                           charges=(2, 3, 4), n_isotopes: int = 4):
+    """An ion-mobility dimension for synthetic_lcms files.  Every peptide of the experiment gets a mobility k0 in [0.6, 1.4].
+    An MS2 spectrum of the peptide (found by its precursor m/z and charge) gets inverse_ion_mobility = k0, in place — the search
+    copies it to Feature.ims.  An MS1 peak within `ppm` of one of the peptide's charge x isotope m/z gets k0 * (1 + u / 100), u
+    uniform in +-spread_pct, so a mobility window narrower than the spread keeps some of a peptide's peaks and drops others; every
+    other peak gets a uniform mobility in [0.5, 1.6].  Returns (k0 per peptide, per file the per-spectrum f32 arrays — None for
+    spectra above level 1 —, the shape write_lcms / write_mzml take)."""
+    rng = np.random.default_rng(seed)
+    peps = files[0].peptides
+    k0 = rng.uniform(0.6, 1.4, len(peps)).astype(np.float32)
+    mono = db.pep_mono[peps].astype(np.float64)
+    z = np.asarray(charges, dtype=np.float64)
+    table = ((mono[:, None, None] + np.arange(n_isotopes)[None, None, :] * NEUTRON) / z[None, :, None] + PROTON).reshape(-1)
+    owner = np.repeat(np.arange(len(peps)), len(charges) * n_isotopes)
+    order = np.argsort(table)
+    table, owner = table[order], owner[order]
+    out = []
+    for lf in files:
+        per_spectrum = []
+        for s, lvl in zip(lf.spectra, lf.ms_levels):
+            if lvl != 1:
+                if s.precursor_charge:
+                    m = (s.precursor_mz - PROTON) * s.precursor_charge
+                    p = int(np.argmin(np.abs(mono - m)))
+                    if abs(mono[p] - m) <= 50e-6 * m:
+                        s.inverse_ion_mobility = float(k0[p])
+                per_spectrum.append(None)
+                continue
+            mz = s.mz.astype(np.float64)
+            mob = rng.uniform(0.5, 1.6, len(mz))
+            j = np.clip(np.searchsorted(table, mz), 1, len(table) - 1)
+            j = np.where(np.abs(table[j - 1] - mz) < np.abs(table[j] - mz), j - 1, j)
+            hit = np.abs(table[j] - mz) <= ppm * 1e-6 * mz
+            mob[hit] = k0[owner[j[hit]]] * (1.0 + rng.uniform(-spread_pct, spread_pct, int(hit.sum())) / 100.0)
+            per_spectrum.append(mob.astype(np.float32))
+        out.append(per_spectrum)
+    return k0, out
 
 
 @dataclass

@@ -13,6 +13,9 @@
   * signal-to-noise (`sn_level`, :371-381): at that MS level intensity[i] /= noise[i] (noise array MS:1002744, recognised
     only when the array is neither m/z nor intensity) over the shorter of the two arrays, in f32.  Only the spectrum's own
     noise array divides it; the reference would reuse an earlier spectrum's unused one.
+  * per-peak ion mobility of MS1 spectra — an addition over the reference's mzML reader, which ignores the array: a
+    binaryDataArray with one of MOBILITY_ARRAYS that is neither m/z, intensity nor noise becomes RawSpectrum.mobility (f32) of a
+    spectrum whose ms level is 1; other levels drop it (spectrum.rs:344).  A length other than the m/z array's is an error.
 `write_mzml` is ours (the reference has no writer): centroid MS2 spectra with 32-bit zlib arrays like the reference's
 test fixture (tests/LQSRPAAPPAPGPGQLTLR.mzML:117-126), used to feed synthetic workloads through the CLI.
 """
@@ -30,6 +33,10 @@ import numpy as np
 from .api import RawSpectrum
 
 _F32 = np.float32
+
+# ion mobility array, mean ion mobility array, mean inverse reduced ion mobility array, raw ion mobility array, raw inverse
+# reduced ion mobility array (PSI-MS; matched by accession only)
+MOBILITY_ARRAYS = ("MS:1002893", "MS:1002816", "MS:1003006", "MS:1003007", "MS:1003008")
 
 
 def _local(tag: str) -> str:
@@ -79,7 +86,7 @@ def read_mzml(path: str, file_id: int = 0, ms_level: Optional[int] = 2, sn_level
             continue
         mz = np.zeros(0, _F32)
         inten = np.zeros(0, _F32)
-        noise = None
+        noise = mobility = None
         scan_start, iit, prec_ref = 0.0, 0.0, ""
         prec_mz, prec_charge, prec_ims = 0.0, None, None
         iso_lo = iso_hi = None
@@ -134,8 +141,9 @@ def read_mzml(path: str, file_id: int = 0, ms_level: Optional[int] = 2, sn_level
                 accs = [cv.attrib.get("accession") for cv in sub if _local(cv.tag) == "cvParam"]
                 text = next((b.text for b in sub if _local(b.tag) == "binary"), None) or ""
                 kind = ("mz" if "MS:1000514" in accs else "intensity" if "MS:1000515" in accs else
-                        "noise" if "MS:1002744" in accs else None)
-                if not text or kind is None or (kind == "noise" and (sn_level is None or level != sn_level)):
+                        "noise" if "MS:1002744" in accs else "mobility" if any(a in MOBILITY_ARRAYS for a in accs) else None)
+                if (not text or kind is None or (kind == "noise" and (sn_level is None or level != sn_level)) or
+                        (kind == "mobility" and level != 1)):
                     continue
                 raw = base64.b64decode(text)
                 if "MS:1000574" in accs:
@@ -148,6 +156,8 @@ def read_mzml(path: str, file_id: int = 0, ms_level: Optional[int] = 2, sn_level
                     mz = arr
                 elif kind == "intensity":
                     inten = arr
+                elif kind == "mobility":
+                    mobility = arr
                 else:
                     noise = arr
         if noise is not None and len(noise):
@@ -156,8 +166,11 @@ def read_mzml(path: str, file_id: int = 0, ms_level: Optional[int] = 2, sn_level
             with np.errstate(divide="ignore", invalid="ignore"):
                 inten[:k] = inten[:k] / noise[:k]
         iso = (-iso_lo, iso_hi) if (iso_lo is not None and iso_hi is not None) else None
+        if mobility is not None and len(mobility) != len(mz):
+            raise ValueError(f"malformed mzML: ion mobility array of spectrum {el.attrib.get('id', '')} holds {len(mobility)} "
+                             f"values for {len(mz)} m/z values")
         out.append(RawSpectrum(mz, inten, prec_mz, prec_charge, iso, scan_start, prec_ims, file_id, el.attrib.get("id", ""), iit,
-                               prec_ref))
+                               prec_ref, mobility))
         el.clear()
     return out
 
@@ -193,6 +206,13 @@ def read_mzml_native(path: str, file_id: int = 0, ms_level: Optional[int] = 2, c
 
         peak_off = arr(v.peak_off, n + 1, np.uint64)
         npk = int(peak_off[-1])
+        mob_ptr = lib.sage_hip_mzml_mobility(h)
+        mobility = has_mobility = None
+        if mob_ptr:
+            mobility = arr(mob_ptr, npk, np.float32)
+            has_mobility = np.zeros(max(n, 1), np.uint8)
+            L.check(lib.sage_hip_mzml_has_mobility(h, L.as_ptr(has_mobility, C.c_uint8)))
+            has_mobility = has_mobility[:n]
         ids = [lib.sage_hip_mzml_spectrum_id(h, i).decode() for i in range(n)]
         return RawBatch.from_arrays(ids, peak_off, arr(v.mz, npk, np.float32), arr(v.intensities, npk, np.float32),
                                     arr(v.precursor_mz, n, np.float32), arr(v.precursor_charge, n, np.uint8),
@@ -200,21 +220,26 @@ def read_mzml_native(path: str, file_id: int = 0, ms_level: Optional[int] = 2, c
                                     arr(v.scan_start_time, n, np.float32), arr(v.inverse_ion_mobility, n, np.float32),
                                     arr(v.file_id, n, np.uint32),
                                     np.array([lib.sage_hip_mzml_ion_injection_time(h, i) for i in range(n)], dtype=np.float32),
-                                    [lib.sage_hip_mzml_precursor_ref(h, i).decode() for i in range(n)])
+                                    [lib.sage_hip_mzml_precursor_ref(h, i).decode() for i in range(n)],
+                                    mobility=mobility, has_mobility=has_mobility)
     finally:
         lib.sage_hip_mzml_free(h)
 
 
-def _b64(arr: np.ndarray) -> str:
-    return base64.b64encode(zlib.compress(np.ascontiguousarray(arr, dtype="<f4").tobytes())).decode()
+def _b64(arr: np.ndarray, bits: int = 32, compress: bool = True) -> str:
+    raw = np.ascontiguousarray(arr, dtype="<f4" if bits == 32 else "<f8").tobytes()
+    return base64.b64encode(zlib.compress(raw) if compress else raw).decode()
 
 
 def write_mzml(path: str, spectra: List[RawSpectrum], ms_levels: Optional[List[int]] = None, noise=None,
-               extra_precursors=None) -> None:
+               extra_precursors=None, mobility=None, mobility_encoding=(MOBILITY_ARRAYS[0], 32, True)) -> None:
     """Centroid MS2 spectra, 32-bit zlib arrays, selected ion m/z / charge, isolation offsets, scan start time (minutes).
     ms_levels: per spectrum (default 2); an `ms level` 1 spectrum is written without a precursor list.  A non-zero
-    ion_injection_time and a non-empty precursor_ref (spectrumRef) are written when set.  noise: per spectrum, a noise array
-    (MS:1002744) or None; extra_precursors: per spectrum, further precursor m/z (SPS-MS3) after the first, or None."""
+    ion_injection_time, a non-empty precursor_ref (spectrumRef) and an inverse_ion_mobility (MS:1002815 under <scan>) are written
+    when set.  noise: per spectrum, a noise array
+    (MS:1002744) or None; extra_precursors: per spectrum, further precursor m/z (SPS-MS3) after the first, or None.
+    mobility: per spectrum, a per-peak ion-mobility array or None (written at any ms level: the reader keeps it at level 1),
+    after the noise array; mobility_encoding: its (accession, 32 or 64 bits, zlib or not)."""
     with open(path, "w") as f:
         f.write('<?xml version="1.0" encoding="utf-8"?>\n<mzML xmlns="http://psi.hupo.org/ms/mzml" version="1.1.0">\n')
         f.write(f'<run id="synthetic"><spectrumList count="{len(spectra)}">\n')
@@ -227,12 +252,17 @@ def write_mzml(path: str, spectra: List[RawSpectrum], ms_levels: Optional[List[i
             iit = getattr(s, "ion_injection_time", 0.0)
             iit_cv = (f'<cvParam cvRef="MS" accession="MS:1000927" name="ion injection time" '
                       f'value="{np.format_float_positional(np.float32(iit), unique=True)}"/>' if iit else "")
+            ims = getattr(s, "inverse_ion_mobility", None)
+            if ims is not None:
+                iit_cv += (f'<cvParam cvRef="MS" accession="MS:1002815" name="inverse reduced ion mobility" '
+                           f'value="{np.format_float_positional(np.float32(ims), unique=True)}"/>')
             f.write(f'<scanList count="1"><scan><cvParam cvRef="MS" accession="MS:1000016" name="scan start time" '
                     f'value="{np.format_float_positional(np.float32(s.scan_start_time), unique=True)}" unitCvRef="UO" '
                     f'unitAccession="UO:0000031" unitName="minute"/>{iit_cv}</scan></scanList>\n')
             nz = None if noise is None else noise[i]
+            mob = None if mobility is None or mobility[i] is None else (mobility[i],) + tuple(mobility_encoding)
             if level == 1:
-                _write_arrays(f, s, nz)
+                _write_arrays(f, s, nz, mob)
                 continue
             ref = getattr(s, "precursor_ref", "")
             extra = [] if extra_precursors is None or extra_precursors[i] is None else list(extra_precursors[i])
@@ -255,17 +285,25 @@ def write_mzml(path: str, spectra: List[RawSpectrum], ms_levels: Optional[List[i
                         f'name="selected ion m/z" value="{np.format_float_positional(np.float32(x), unique=True)}"/>'
                         '</selectedIon></selectedIonList></precursor>')
             f.write('</precursorList>\n')
-            _write_arrays(f, s, nz)
+            _write_arrays(f, s, nz, mob)
         f.write('</spectrumList></run></mzML>\n')
 
 
-def _write_arrays(f, s, noise=None) -> None:
+def _write_arrays(f, s, noise=None, mobility=None) -> None:
     arrays = [("MS:1000514", "m/z array", s.mz), ("MS:1000515", "intensity array", s.intensity)]
     if noise is not None:
         arrays.append(("MS:1002744", "sampled noise intensity array", noise))
-    f.write(f'<binaryDataArrayList count="{len(arrays)}">')
+    f.write(f'<binaryDataArrayList count="{len(arrays) + (mobility is not None)}">')
     for acc, name, arr in arrays:
         f.write('<binaryDataArray><cvParam cvRef="MS" accession="MS:1000521" name="32-bit float"/>'
                 '<cvParam cvRef="MS" accession="MS:1000574" name="zlib compression"/>'
                 f'<cvParam cvRef="MS" accession="{acc}" name="{name}"/><binary>{_b64(arr)}</binary></binaryDataArray>')
+    if mobility is not None:
+        arr, acc, bits, compress = mobility
+        width = ('<cvParam cvRef="MS" accession="MS:1000521" name="32-bit float"/>' if bits == 32 else
+                 '<cvParam cvRef="MS" accession="MS:1000523" name="64-bit float"/>')
+        comp = ('<cvParam cvRef="MS" accession="MS:1000574" name="zlib compression"/>' if compress else
+                '<cvParam cvRef="MS" accession="MS:1000576" name="no compression"/>')
+        f.write(f'<binaryDataArray>{width}{comp}<cvParam cvRef="MS" accession="{acc}" name="ion mobility array"/>'
+                f'<binary>{_b64(arr, bits, compress)}</binary></binaryDataArray>')
     f.write('</binaryDataArrayList>\n</spectrum>\n')
