@@ -908,6 +908,8 @@ static int scorer_init(SageScorer* sp, SageDeviceDb* db, const SageScorerParams*
     d.wcap = 1024;
     d.dbg_flags = 0;
     if (const char* e = getenv("SAGE_HIP_DEBUG_FLAGS")) d.dbg_flags = (uint32_t)atoi(e);
+    d.rescore_general = 0;
+    if (const char* e = getenv("SAGE_HIP_RESCORE_GENERAL")) d.rescore_general = atoi(e) != 0 ? 1u : 0u;
     d.exact = 0;
     d.xcd_chunk = 1024;
     if (const char* e = getenv("SAGE_HIP_XCD_CHUNK")) d.xcd_chunk = (uint32_t)std::max(0, atoi(e));
@@ -1961,7 +1963,7 @@ static int enqueue_compute(SageScorer* s, const DevBatchView& view_in, OutSet& o
     }
     if (!no_timing) HIP_TRY(hipEventRecord(o.ev[1].e, st));
     if (with_rescore && (wide || !(fused || one_launch)))  // (behind search_kernel / the fused kernel: only the spectra the large-window kernels assembled)
-        launch_rescore(s->db->view, sc1, view, w1, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, rec, count_buf, nullptr, st);
+        HIP_TRY((hipError_t)launch_rescore(s->db->view, sc1, view, w1, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, rec, count_buf, nullptr, st));
     if (!no_timing) HIP_TRY(hipEventRecord(o.ev[2].e, st));
 retry_pass:
     if (o.two_pass && phase != 1) {
@@ -1973,7 +1975,7 @@ retry_pass:
         }
         if (wide) {  // (without the large-window kernels the retry pass is ONE launch: no marker inside it)
             if (!no_timing) HIP_TRY(hipEventRecord(o.ev[3].e, st));
-            launch_rescore(s->db->view, sc2, v2, w2, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, rec, count_buf, nullptr, st);
+            HIP_TRY((hipError_t)launch_rescore(s->db->view, sc2, v2, w2, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, rec, count_buf, nullptr, st));
         }
         if (!no_timing) HIP_TRY(hipEventRecord(o.ev[4].e, st));
     }
@@ -2534,8 +2536,8 @@ int sage_hip_quick_score_resident(SageScorer* s, SageDeviceBatch* b, int prefilt
         w.huge_stride = (uint32_t)huge_stride_bytes(s->dev);
     }
     if (prefilter_low_memory)
-        launch_rescore(s->db->view, s->dev, b->view, w, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, o.features.p,
-                       o.out_count.p, s->keep.p, s->stream);
+        HIP_TRY((hipError_t)launch_rescore(s->db->view, s->dev, b->view, w, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, o.features.p,
+                                           o.out_count.p, s->keep.p, s->stream));
     else
         launch_quick_mark(s->dev, b->view, w, s->keep.p, s->stream);
     HIP_TRY(hipGetLastError());

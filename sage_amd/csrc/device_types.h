@@ -100,6 +100,8 @@ struct DevScorer {
     uint32_t wcap;       // candidate-slot capacity of the LDS counter array of the narrow kernel: spectra with a
                          // larger precursor window go to the tiled large-window kernel
     uint32_t dbg_flags;  // timing experiments only (SAGE_HIP_DEBUG_FLAGS)
+    uint32_t rescore_general;  // 1: launch_rescore takes the general instance of rescore_kernel (CHIMERA == true) for every search
+                               //    (SAGE_HIP_RESCORE_GENERAL=1, read at scorer creation: tests and A/B runs of the two routes); host only
     uint32_t xcd_chunk;  // consecutive schedule positions one XCD takes at a time (kernels.hip: xcd_position); 0: round-robin
     uint32_t fast_log;   // 1: this pass is followed by the exact retry pass, so its rescoring kernel may carry the fast phase of the
                          //    correctly rounded logarithm only and queue the (rare) spectrum it cannot round for (crlog.h)
@@ -301,9 +303,10 @@ void launch_process_big(uint32_t n_big, const uint32_t* big_list, unsigned char*
                         uint32_t* out_count, void* stream);
 void launch_compact(uint32_t n, const uint64_t* peak_off, uint32_t stride, const float* sm, const float* si, float* masses,
                     float* intens, void* stream);
-void launch_rescore(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const DevWork& w,
-                    const double* lnfact_table, uint32_t lnfact_n, uint32_t max_ions, SageFeature* out,
-                    uint32_t* out_count, uint8_t* keep, void* stream);
+// (returns a hipError_t: hipErrorInvalidValue when `keep` would meet an instance compiled without quick_score's block)
+int launch_rescore(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const DevWork& w,
+                   const double* lnfact_table, uint32_t lnfact_n, uint32_t max_ions, SageFeature* out,
+                   uint32_t* out_count, uint8_t* keep, void* stream);
 // counts[n] -> h_counts (device view of page-locked memory) and the counter blocks (2 * CTR_COUNT words) of up to four parts
 struct EpilogueParts {
     uint32_t* src[4];  // (reset by the kernel after the copy)

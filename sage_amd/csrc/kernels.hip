@@ -3485,7 +3485,11 @@ struct LateArgs<RescoreKernargs> {
     __device__ __forceinline__ uint8_t* keep(uint8_t*) const { return ka->keep; }
 };
 
-template <bool ACC, class KA, bool FAST = false, class PC>
+// CHIMERA == false: the instance of a search without chimera rounds (Sage's default).  One round, straight-line: no round loop, no
+// remove_matched_peaks, nothing of the candidates kept alive for a second round across score_candidates — which is what the
+// general form pays its spills for.  CHIMERA == true serves both kinds of search (sc.chimera decides at run time).
+// quick_score's k-select (`keep`) is compiled into ACC instances only: launch_rescore never hands `keep` to another one.
+template <bool ACC, class KA, bool FAST = false, bool CHIMERA = true, class PC>
 __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const DevWork& w,
                                                  const double* __restrict__ lnfact_table, uint32_t lnfact_n,
                                                  SageFeature* __restrict__ out, uint32_t* __restrict__ out_count,
@@ -3576,7 +3580,7 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
         s.longest_b = s.longest_y = 0;
         pc.mark(5);  // (... the peak table and the bitmap)
         score_candidates<PC, false, FAST>(db, sc, pbm, plut, pm, pi, P, inv_w, valid, ion_base, lm1, nfz, any_fz2, any_fz3, nterm_mask, sym_tol,
-                                          s, pc, SAGE_ION_PREFETCH && round == 0, first0, first1, first2, first3, !sc.chimera);
+                                          s, pc, SAGE_ION_PREFETCH && round == 0, first0, first1, first2, first3, !CHIMERA || !sc.chimera);
         pc.mark(1);  // (... the lanes' own hits)
         // ---- from here on: the arguments through `la`, the spectrum's scalars from R.hdr (see LateArgs) ----
         LateArgs<KA> la(db, sc, b, w, lnfact_table, lnfact_n, out, out_count);
@@ -3601,9 +3605,9 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
             pass = (s.matched_b + s.matched_y) >= la.min_matched_peaks();  // scoring.rs:491
         }
         const uint32_t report_psms = la.report_psms();
-        const bool chimera = la.chimera() != 0u;
+        const bool chimera = CHIMERA && la.chimera() != 0u;
         const uint32_t per_round = chimera ? 1u : report_psms;
-        if (keep) {
+        if (ACC && keep) {
             // quick_score, prefilter_low_memory (scoring.rs:270-289): bounded_min_heapify(&mut scores, k) keeps the k
             // largest elements.  heap.rs compares with `<` / `>`, i.e. the DERIVED PartialOrd of Score — lexicographic
             // in field order, peptide first (scoring.rs:17-30) — not its hyperscore Ord.  The set of the k largest does
@@ -3769,7 +3773,7 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
         }
         pc.mark(4);
         n_emitted += emitted;
-        if (!chimera || emitted == 0 || round + 1 == report_psms) break;  // (chimera: report_psms rounds of one PSM)
+        if (!CHIMERA || !chimera || emitted == 0 || round + 1 == report_psms) break;  // (chimera: report_psms rounds of one PSM)
 
         // ---- remove_matched_peaks(winner), scoring.rs:598-644 ----
         const uint64_t wmask = __ballot(pass && rank == 0);
@@ -4004,7 +4008,8 @@ __host__ __device__ inline size_t narrow_scratch_bytes(const DevScorer& sc, cons
 // with exact trims, inline or behind a call — was measured: the extra code costs the hot path its registers, rescoring went
 // from 3.7 to 6.0 resp. 7.2 ms per 500 000 C3 spectra.  DESIGN.md 4.7.)
 // FAST: the instance with the short divisions (core.h: div_const_fast), for scorers whose dividends the host has bounded.
-template <bool PROF, bool ACC, bool FAST = false>
+// CHIMERA: see rescore_spectrum — false is the instance of every search without chimera rounds.
+template <bool PROF, bool ACC, bool FAST = false, bool CHIMERA = true>
 __global__ __launch_bounds__(64) SAGE_RESCORE_WAVES_ATTR void rescore_kernel(RescoreKernargs A) {
     // (ONE argument: rescore_spectrum reads what it needs late straight from the kernarg segment — LateArgs<RescoreKernargs>)
     const DevDbView& db = A.db;
@@ -4015,7 +4020,7 @@ __global__ __launch_bounds__(64) SAGE_RESCORE_WAVES_ATTR void rescore_kernel(Res
     const uint32_t lnfact_n = A.lnfact_n;
     SageFeature* __restrict__ out = A.out;
     uint32_t* __restrict__ out_count = A.out_count;
-    uint8_t* __restrict__ keep = A.keep;
+    uint8_t* __restrict__ keep = ACC ? A.keep : nullptr;  // (quick_score runs on ACC instances only: launch_rescore)
     typedef typename std::conditional<PROF, PhaseClock, NoClock>::type Clock;
     extern __shared__ __align__(16) unsigned char smem[];
     const uint32_t lane = lane_id();
@@ -4075,8 +4080,8 @@ __global__ __launch_bounds__(64) SAGE_RESCORE_WAVES_ATTR void rescore_kernel(Res
     }
     const uint64_t mine = lane < ncand ? row_word : PRESCORE_EMPTY;
     // (a list no trim touched is the reference's list already: equal hyperscores are ranked by it, no retry)
-    rescore_spectrum<ACC, RescoreKernargs, FAST>(db, sc, b, w, lnfact_table, lnfact_n, out, out_count, keep, R, spec, P, mine, tot_m, tot_s,
-                                                 sc.exact != 0 || st == ST_OK_ORDERED, true, pc);
+    rescore_spectrum<ACC, RescoreKernargs, FAST, CHIMERA>(db, sc, b, w, lnfact_table, lnfact_n, out, out_count, keep, R, spec, P, mine, tot_m,
+                                                          tot_s, sc.exact != 0 || st == ST_OK_ORDERED, true, pc);
 }
 
 #ifdef SAGE_HIP_EXPERIMENTS  // (measured slower than the two kernels, DESIGN.md 4.7: compiled only into experiment builds)
@@ -4421,8 +4426,10 @@ int tile_kernel_prepare(size_t max_lds_bytes) {
 int spectrum_kernel_prepare(size_t max_lds_bytes) {
     for (const void* f : {(const void*)prelim_kernel<true, true>, (const void*)prelim_kernel<true, false>, (const void*)prelim_kernel<false, true>,
                           (const void*)prelim_kernel<false, false>, (const void*)rescore_kernel<true, true>, (const void*)rescore_kernel<false, false>,
-                          (const void*)rescore_kernel<false, false, true>,
-                          (const void*)rescore_kernel<false, true>, (const void*)narrow_kernel<true, true>, (const void*)narrow_kernel<true, false>,
+                          (const void*)rescore_kernel<false, false, true>, (const void*)rescore_kernel<false, true>,
+                          (const void*)rescore_kernel<true, true, false, false>, (const void*)rescore_kernel<false, false, false, false>,
+                          (const void*)rescore_kernel<false, false, true, false>, (const void*)rescore_kernel<false, true, false, false>,
+                          (const void*)narrow_kernel<true, true>, (const void*)narrow_kernel<true, false>,
                           (const void*)narrow_kernel<false, true>, (const void*)narrow_kernel<false, false>, (const void*)annotate_kernel}) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes);
         if (e != hipSuccess) return (int)e;
@@ -4553,10 +4560,18 @@ void launch_prelim_tile(const DevDbView& db, const DevScorer& sc, const DevBatch
     }
     hipLaunchKernelGGL(tile_assemble_kernel<false>, dim3(capped(b.n)), dim3(64), assemble_lds, (hipStream_t)stream, sc, b, w);
 }
-void launch_rescore(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const DevWork& w,
-                    const double* lnfact_table, uint32_t lnfact_n, uint32_t max_ions, SageFeature* out,
-                    uint32_t* out_count, uint8_t* keep, void* stream) {
-    if (b.n == 0) return;
+// One instance of rescore_kernel<PROF, ACC, FAST, CHIMERA> per launch.  ACC == false carries the logarithm's fast phase only and no
+// quick_score code, CHIMERA == false no chimera rounds.
+template <bool CHIMERA>
+static void (*rescore_instance(bool prof, bool acc, bool fast))(RescoreKernargs) {
+    return prof ? rescore_kernel<true, true, false, CHIMERA>
+           : acc ? rescore_kernel<false, true, false, CHIMERA>
+                 : (fast ? rescore_kernel<false, false, true, CHIMERA> : rescore_kernel<false, false, false, CHIMERA>);
+}
+int launch_rescore(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const DevWork& w,
+                   const double* lnfact_table, uint32_t lnfact_n, uint32_t max_ions, SageFeature* out,
+                   uint32_t* out_count, uint8_t* keep, void* stream) {
+    if (b.n == 0) return (int)hipSuccess;
     if (sc.big_path) {  // report_psms > 32, or peptides of more than 1023 residues
         const uint32_t cap = w.hugebuf ? HUGE_GRID : TILE_GRID_CAP;
         const auto big = w.hugebuf ? (sc.long_runs ? rescore_big_kernel<true, true> : rescore_big_kernel<false, true>)
@@ -4564,15 +4579,21 @@ void launch_rescore(const DevDbView& db, const DevScorer& sc, const DevBatchView
         hipLaunchKernelGGL(big, dim3(b.n < cap ? b.n : cap), dim3(64),
                            rescore_lds_bytes(sc, b, max_ions, keep != nullptr, w.hugebuf != nullptr), (hipStream_t)stream, db, sc, b, w,
                            lnfact_table, lnfact_n, out, out_count, keep);
-        return;
+        return (int)hipSuccess;
     }
     // the first pass of a two-pass search (sc.fast_log) runs the instance with the logarithm's fast phase only (crlog.h)
     // (the production instance comes in two forms: with the short divisions where the host allows them — DevScorer::tol_mode)
-    const auto kern = w.dbg ? rescore_kernel<true, true>
-                      : (sc.fast_log && !keep) ? ((sc.tol_mode & TOL_FAST) ? rescore_kernel<false, false, true> : rescore_kernel<false, false>)
-                                               : rescore_kernel<false, true>;
+    // INVARIANT: quick_score (`keep`) runs on ACC instances only — the others are compiled without its block and ignore `keep`.
+    const bool prof = w.dbg != nullptr;
+    const bool acc = prof || !sc.fast_log || keep != nullptr;
+    if (keep && !acc) return (int)hipErrorInvalidValue;  // (a selection edited out of step with the kernels fails here, not silently)
+    // a search without chimera rounds takes the instance compiled without them (DevScorer::rescore_general: both routes in one build)
+    const bool general = sc.chimera != 0u || sc.rescore_general != 0u;
+    const bool fast = (sc.tol_mode & TOL_FAST) != 0u;
+    const auto kern = general ? rescore_instance<true>(prof, acc, fast) : rescore_instance<false>(prof, acc, fast);
     const RescoreKernargs args{db, sc, b, w, lnfact_table, lnfact_n, out, out_count, keep};
     hipLaunchKernelGGL(kern, dim3(b.n), dim3(64), rescore_lds_bytes(sc, b, max_ions, keep != nullptr), (hipStream_t)stream, args);
+    return (int)hipSuccess;
 }
 void launch_epilogue(const uint32_t* counts, uint32_t n, uint32_t* h_counts, const uint32_t* order, const EpilogueParts& parts, void* stream) {
     const uint32_t blocks = (n + 1023) / 1024;
