@@ -13,6 +13,9 @@
 
 #include "crlog.h"
 #include "device_types.h"
+// a failed HIP call of an entry point (HIP_TRY): the thread's error string is set, the status returned
+#define HIP_FAILED(e, what) fail(status_of(e), std::string(what) + ": " + hipGetErrorString(e))
+#include "hip_host.h"
 #include "host_db.hpp"
 
 using namespace sagehip;
@@ -25,45 +28,6 @@ int fail(int code, const std::string& msg) {
     g_last_error = msg;
     return code;
 }
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return fail(_e == hipErrorOutOfMemory ? SAGE_HIP_ERR_OOM : SAGE_HIP_ERR_HIP,           \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                        \
-    } while (0)
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    hipError_t alloc(size_t count) {
-        release();
-        n = count;
-        return hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
-    }
-    hipError_t upload(const T* src, size_t count) {
-        hipError_t e = alloc(count);
-        if (e != hipSuccess) return e;
-        return count ? hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
-    }
-    // grow-only: keep the allocation when it is large enough (no driver call on the steady-state path)
-    hipError_t reserve(size_t count) {
-        if (p && count <= n) return hipSuccess;
-        return alloc(std::max(count, n + n / 2));
-    }
-    size_t bytes() const { return n * sizeof(T); }
-};
 
 // page-locked host block, grow-only (staging of the streaming pipeline: DMA at full PCIe rate)
 struct Pinned {
@@ -93,17 +57,6 @@ T* carve(unsigned char*& cur, size_t count) {  // next 64-byte aligned array of 
     cur += ((count * sizeof(T) + 63) / 64) * 64;
     return p;
 }
-
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() = default;
-    Event(const Event&) = delete;
-    Event& operator=(const Event&) = delete;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-    hipError_t create(bool timing) { return e ? hipSuccess : hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming); }
-};
 
 }  // namespace
 
@@ -662,14 +615,10 @@ int sage_hip_db_create(const SageDbView* v, int device, SageDeviceDb** out) {
         HIP_TRY(d->tm_frag.alloc(nf + 2));
         hipError_t be = (hipError_t)generate_fragments_on_device(np, nk, d_kinds.p, d_seq_off.p, d_seq.p, d_mods.p, d_nterm.p, d->pep_mono.p,
                                                                 v->min_ion_index, d->ion_off.p, d->pm_off.p, d->ions.p, d->pm_frag.p, nullptr);
-        uint32_t* lut_p = nullptr;
         if (be == hipSuccess)
             be = (hipError_t)build_tile_copy_on_device(d->pm_frag.p, nf, tile_shift, (uint32_t)n_tiles, d_tile_off.p, lut_scale,
-                                                       d->tm_frag.p, &lut_p, &lut_stride, nullptr, TM_LUT_LAYOUT);
-        if (be != hipSuccess)
-            return fail(be == hipErrorOutOfMemory ? SAGE_HIP_ERR_OOM : SAGE_HIP_ERR_HIP, std::string("device index build: ") + hipGetErrorString(be));
-        d->tm_lut.p = lut_p;
-        d->tm_lut.n = (size_t)tm_lut_rows((uint32_t)n_tiles) * lut_stride;
+                                                       d->tm_frag.p, d->tm_lut, &lut_stride, nullptr, TM_LUT_LAYOUT);
+        if (be != hipSuccess) return fail(status_of(be), std::string("device index build: ") + hipGetErrorString(be));
         host_pm_off.swap(pm_off);
         HIP_TRY(d->pep_info.upload(info.data(), np));
     } else {
@@ -760,26 +709,17 @@ int sage_hip_db_create(const SageDbView* v, int device, SageDeviceDb** out) {
         DevBuf<uint64_t> d_tile2_off;
         HIP_TRY(d_tile2_off.upload(tile2_off.data(), n_tiles2 + 1));
         HIP_TRY(d->tm2_frag.alloc(nf + 2));
-        uint32_t* lut2_p = nullptr;
+        DevBuf<uint32_t> lut2;  // the row-major table
         uint32_t lut2_stride = 0;
         const hipError_t be = (hipError_t)build_tile_copy_on_device(d->pm_frag.p, nf, tile2_shift, (uint32_t)n_tiles2, d_tile2_off.p,
-                                                                    lut2_scale, d->tm2_frag.p, &lut2_p, &lut2_stride, nullptr);
-        if (be != hipSuccess)
-            return fail(be == hipErrorOutOfMemory ? SAGE_HIP_ERR_OOM : SAGE_HIP_ERR_HIP, std::string("device index build: ") + hipGetErrorString(be));
+                                                                    lut2_scale, d->tm2_frag.p, lut2, &lut2_stride, nullptr);
+        if (be != hipSuccess) return fail(status_of(be), std::string("device index build: ") + hipGetErrorString(be));
         // the table in succinct form (index_build.hip: build_succinct_lut_on_device; the row-major table is its input only —
         // 1.5 GB for C3 that the narrow kernel no longer reads a line of per lookup)
-        sagecore::LutWord* l1_p = nullptr;
-        uint32_t* pos_p = nullptr;
         uint32_t lut2_words = 0;
-        uint64_t n_pos = 0;
-        const hipError_t se = (hipError_t)build_succinct_lut_on_device(lut2_p, (uint32_t)n_tiles2, lut2_stride, &l1_p, &pos_p, &lut2_words, &n_pos, nullptr);
-        (void)hipFree(lut2_p);
-        if (se != hipSuccess)
-            return fail(se == hipErrorOutOfMemory ? SAGE_HIP_ERR_OOM : SAGE_HIP_ERR_HIP, std::string("device index build (succinct table): ") + hipGetErrorString(se));
-        d->tm2_l1.p = l1_p;
-        d->tm2_l1.n = (size_t)n_tiles2 * lut2_words;
-        d->tm2_pos.p = pos_p;
-        d->tm2_pos.n = (size_t)std::max<uint64_t>(n_pos, 1);
+        const hipError_t se = (hipError_t)build_succinct_lut_on_device(lut2.p, (uint32_t)n_tiles2, lut2_stride, d->tm2_l1, d->tm2_pos, &lut2_words, nullptr);
+        lut2.release();
+        if (se != hipSuccess) return fail(status_of(se), std::string("device index build (succinct table): ") + hipGetErrorString(se));
         d->view.tm2_frag = d->tm2_frag.p;
         d->view.tm2_l1 = d->tm2_l1.p;
         d->view.tm2_pos = d->tm2_pos.p;
@@ -793,18 +733,14 @@ int sage_hip_db_create(const SageDbView* v, int device, SageDeviceDb** out) {
     d->max_len = max_len;
     HIP_TRY((hipError_t)ion_abs_range_on_device(d->ions.p, ion_off[np], &d->ion_lo_bits, &d->ion_hi_bits));
     {  // the position table of the precursor-window search key
-        uint32_t* lut_p = nullptr;
         uint32_t bins = 0;
         float inv_w = 0.0f;
         // (SAGE_HIP_NO_PEP_LUT=1: without — every window through the full search; tests hold the two against each other)
         const bool off = getenv("SAGE_HIP_NO_PEP_LUT") && getenv("SAGE_HIP_NO_PEP_LUT")[0] == '1';
         const hipError_t be = off ? hipSuccess
-                                  : (hipError_t)build_peptide_mass_lut(d->pep_mono.p, (uint32_t)np, np ? d->h_pep_mono[np - 1] : 0.0f, &lut_p, &bins, &inv_w, nullptr);
-        if (be != hipSuccess)
-            return fail(be == hipErrorOutOfMemory ? SAGE_HIP_ERR_OOM : SAGE_HIP_ERR_HIP, std::string("peptide-mass table: ") + hipGetErrorString(be));
-        d->pep_lut.p = lut_p;
-        d->pep_lut.n = lut_p ? (size_t)bins + 1 : 0;
-        d->view.pep_lut = lut_p;
+                                  : (hipError_t)build_peptide_mass_lut(d->pep_mono.p, (uint32_t)np, np ? d->h_pep_mono[np - 1] : 0.0f, d->pep_lut, &bins, &inv_w, nullptr);
+        if (be != hipSuccess) return fail(status_of(be), std::string("peptide-mass table: ") + hipGetErrorString(be));
+        d->view.pep_lut = d->pep_lut.p;
         d->view.pep_lut_bins = bins;
         d->view.pep_lut_inv_w = inv_w;
     }
@@ -843,7 +779,7 @@ static int ensure_pm_frag(SageDeviceDb* db) {
     const hipError_t be = (hipError_t)rebuild_peptide_major_on_device(db->tm_frag.p, db->view.nf, db->pm_frag.p, nullptr);
     if (be != hipSuccess) {
         db->pm_frag.release();
-        return fail(be == hipErrorOutOfMemory ? SAGE_HIP_ERR_OOM : SAGE_HIP_ERR_HIP, std::string("peptide-major fragment list: ") + hipGetErrorString(be));
+        return fail(status_of(be), std::string("peptide-major fragment list: ") + hipGetErrorString(be));
     }
     db->bytes += db->pm_frag.bytes();
     db->view.pm_frag = db->pm_frag.p;
@@ -1387,118 +1323,6 @@ static int batch_upload(SageScorer* s, const SageSpectrumBatch* b, const uint8_t
     return SAGE_HIP_OK;
 }
 
-// SpectrumProcessor::process (spectrum.rs:279-412) of every spectrum of `raw` on the device: process_kernel (the LDS instance up
-// to 2 048 raw peaks, the global-workspace instance beyond) and the compaction into ProcessedSpectrum arrays, enqueued on
-// `stream`.  Spectra that keep fewer than min_peaks peaks are left with zero.  counts: the peaks each spectrum kept before
-// that filter; off: the offsets of peak_off.  `w` holds the inputs and intermediates until the caller's stream is done with
-// them.  What sage_hip_batch_process_upload and sage_hip_tmt share.
-struct ProcessScratch {
-    DevBuf<uint64_t> raw_off;
-    DevBuf<float> raw_mz, raw_int, sm, si;
-    DevBuf<uint8_t> zbuf;
-    DevBuf<uint32_t> cnt, big_list;
-    DevBuf<unsigned char> big_ws;
-};
-static int process_raw_on_device(const SageRawBatch* raw, uint64_t take_top_n, int deisotope, float min_deisotope_mz,
-                                 uint32_t min_peaks, hipStream_t stream, ProcessScratch& w, DevBuf<uint64_t>& peak_off,
-                                 DevBuf<float>& masses, DevBuf<float>& intensities, DevBuf<float>& tic,
-                                 std::vector<uint32_t>& counts, std::vector<uint64_t>& off) {
-    const uint32_t n = raw->n_spectra;
-    if (take_top_n == 0 || take_top_n > 0xFFFFu) return fail(SAGE_HIP_ERR_INVALID, "take_top_n must be in [1, 65535]");
-    const uint64_t total = n ? raw->peak_off[n] : 0;
-    uint32_t rcap = 1;
-    for (uint32_t i = 0; i < n; i++) {
-        if (raw->peak_off[i + 1] < raw->peak_off[i]) return fail(SAGE_HIP_ERR_INVALID, "peak_off is not monotone");
-        rcap = std::max<uint32_t>(rcap, (uint32_t)(raw->peak_off[i + 1] - raw->peak_off[i]));
-    }
-    if (total && (!raw->mz || !raw->intensities)) return fail(SAGE_HIP_ERR_INVALID, "missing peak arrays");
-    // the LDS instance of the kernel takes spectra up to PROCESS_LDS_PEAKS raw peaks (what three workgroups per CU can hold);
-    // larger ones go through the global-workspace instance, whatever their size
-    constexpr uint32_t PROCESS_LDS_PEAKS = 2048;
-    const uint32_t big_cap = rcap;
-    std::vector<uint32_t> big;
-    if (rcap > PROCESS_LDS_PEAKS) {
-        for (uint32_t i = 0; i < n; i++)
-            if (raw->peak_off[i + 1] - raw->peak_off[i] > PROCESS_LDS_PEAKS) big.push_back(i);
-        rcap = PROCESS_LDS_PEAKS;
-    }
-    uint32_t rpow2 = 1;
-    while (rpow2 < rcap) rpow2 <<= 1;
-    HIP_TRY((hipError_t)process_kernel_prepare(160 * 1024));
-    const uint32_t stride = (uint32_t)std::min<uint64_t>(take_top_n, big_cap);
-    HIP_TRY(w.raw_off.upload(raw->peak_off, n ? (size_t)n + 1 : 0));
-    HIP_TRY(w.raw_mz.upload(raw->mz, total));
-    HIP_TRY(w.raw_int.upload(raw->intensities, total));
-    HIP_TRY(w.zbuf.upload(raw->precursor_charge, n));
-    HIP_TRY(w.sm.alloc((size_t)n * stride));
-    HIP_TRY(w.si.alloc((size_t)n * stride));
-    HIP_TRY(w.cnt.alloc(n));
-    HIP_TRY(tic.alloc(n));
-    launch_process(n, w.raw_off.p, w.raw_mz.p, w.raw_int.p, w.zbuf.p, (uint32_t)take_top_n, deisotope != 0, min_deisotope_mz, rcap, rpow2,
-                   stride, w.sm.p, w.si.p, tic.p, w.cnt.p, stream);
-    HIP_TRY(hipGetLastError());
-    if (!big.empty()) {
-        // Groups of similar size, each with slices sized for ITS largest spectrum, launched one after the other over one
-        // workspace of bounded size (stream order makes the reuse safe): a batch with one 50 000-peak outlier among thousands of
-        // 3 000-peak spectra must not ask for (number of big spectra) x (the outlier's slice).
-        std::sort(big.begin(), big.end(), [&](uint32_t a, uint32_t b) {
-            const uint64_t na = raw->peak_off[a + 1] - raw->peak_off[a], nb = raw->peak_off[b + 1] - raw->peak_off[b];
-            return na != nb ? na < nb : a < b;
-        });
-        auto slice_of = [&](uint32_t spec, uint32_t* cap_out, uint32_t* pow2_out) {
-            const uint32_t cap = (uint32_t)(raw->peak_off[spec + 1] - raw->peak_off[spec]);
-            uint32_t p2 = 1;
-            while (p2 < cap) p2 <<= 1;
-            if (cap_out) *cap_out = cap;
-            if (pow2_out) *pow2_out = p2;
-            return process_lds_bytes(cap, p2);
-        };
-        const size_t budget = (size_t)1 << 30;  // bytes of workspace per launch (a single larger spectrum still gets its slice)
-        struct Group { size_t first, count; uint32_t cap, pow2; size_t slice; };
-        std::vector<Group> groups;
-        for (size_t i = 0; i < big.size();) {
-            // grow the group while (members) x (slice of the candidate member, the largest so far) fits the budget
-            size_t j = i;
-            uint32_t cap = 0, p2 = 0;
-            size_t slice = 0;
-            while (j < big.size()) {
-                uint32_t c, q;
-                const size_t sl = slice_of(big[j], &c, &q);
-                if (j > i && (j - i + 1) * sl > budget) break;
-                cap = c; p2 = q; slice = sl;
-                j++;
-            }
-            groups.push_back(Group{i, j - i, cap, p2, slice});
-            i = j;
-        }
-        size_t ws_bytes = 0;
-        for (const Group& g : groups) ws_bytes = std::max(ws_bytes, g.count * g.slice);
-        HIP_TRY(w.big_list.upload(big.data(), big.size()));
-        if (hipError_t e = w.big_ws.alloc(ws_bytes); e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(e == hipErrorOutOfMemory ? SAGE_HIP_ERR_OOM : SAGE_HIP_ERR_HIP,
-                        "preprocessing workspace of " + std::to_string(ws_bytes >> 20) + " MiB for a spectrum of " + std::to_string(big_cap) +
-                            " raw peaks: " + hipGetErrorString(e) + " (sage_hip_process_ms2 preprocesses a spectrum on the host)");
-        }
-        for (const Group& g : groups) {
-            launch_process_big((uint32_t)g.count, w.big_list.p + g.first, w.big_ws.p, w.raw_off.p, w.raw_mz.p, w.raw_int.p, w.zbuf.p, (uint32_t)take_top_n,
-                               deisotope != 0, min_deisotope_mz, g.cap, g.pow2, stride, w.sm.p, w.si.p, tic.p, w.cnt.p, stream);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    counts.assign(n, 0);
-    HIP_TRY(hipMemcpyAsync(counts.data(), w.cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    off.assign((size_t)n + 1, 0);
-    for (uint32_t i = 0; i < n; i++) off[i + 1] = off[i] + (counts[i] >= min_peaks ? counts[i] : 0);  // runner.rs:313
-    HIP_TRY(peak_off.upload(off.data(), n ? (size_t)n + 1 : 0));
-    HIP_TRY(masses.alloc(off[n]));
-    HIP_TRY(intensities.alloc(off[n]));
-    launch_compact(n, peak_off.p, stride, w.sm.p, w.si.p, masses.p, intensities.p, stream);
-    HIP_TRY(hipGetLastError());
-    return SAGE_HIP_OK;
-}
-
 static int batch_process_upload(SageScorer* s, const SageRawBatch* raw, const uint8_t* iso_kind, uint64_t take_top_n, int deisotope,
                                 float min_deisotope_mz, uint32_t min_peaks, SageDeviceBatch** out, uint32_t* out_npeaks) {
     if (!s || !raw || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
@@ -1515,10 +1339,11 @@ static int batch_process_upload(SageScorer* s, const SageRawBatch* raw, const ui
     ProcessScratch w;
     std::vector<uint32_t> counts;
     std::vector<uint64_t> off;
-    if (int rc = process_raw_on_device(raw, take_top_n, deisotope, min_deisotope_mz, min_peaks, s->stream, w, d->peak_off, d->masses,
-                                       d->intensities, d->tic, counts, off);
-        rc != SAGE_HIP_OK)
-        return rc;
+    Ctx cx;
+    cx.stream = s->stream;
+    if (!process_raw_on_device(cx, raw, take_top_n, deisotope, min_deisotope_mz, min_peaks, w, d->peak_off, d->masses, d->intensities, d->tic,
+                               counts, off))
+        return fail(cx.code, cx.err);
     if (out_npeaks) std::copy(counts.begin(), counts.end(), out_npeaks);
     uint32_t pcap = 1, zmax = 0;
     bool any_unknown = false;
@@ -1596,104 +1421,13 @@ int sage_hip_batch_download(SageDeviceBatch* b, uint64_t* peak_off, float* masse
     return SAGE_HIP_OK;
 }
 
-// ---- TMT reporter ions (sage tmt.rs:314-352 quantify, minus the host-side row fields) ----------------------------------------
+// TMT reporter ions (tmt.hip)
 int sage_hip_tmt(int device, const SageTmtInput* in, SageTmtOutput* out) {
     if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null argument");
     if (sage_hip_device_count() <= 0) return fail(SAGE_HIP_ERR_NO_DEVICE, "sage_hip_tmt: no HIP device (there is no CPU fallback)");
-    if ((in->n_batches && !in->batches) || (in->n_labels && !in->labels))
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null array");
-    if (in->tolerance.kind < 0 || in->tolerance.kind > 2) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: unknown tolerance kind");
-    const bool ms2 = in->level == 2;
-    const uint32_t L = in->n_labels;
-    uint64_t n_total = 0;
-    for (uint32_t b = 0; b < in->n_batches; ++b) {
-        const SageRawBatch& r = in->batches[b];
-        if (!r.n_spectra) continue;
-        if (!r.peak_off || (ms2 && !r.precursor_charge)) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null spectrum array");
-        for (uint32_t i = 0; i < r.n_spectra; ++i) {
-            if (r.peak_off[i + 1] < r.peak_off[i]) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: peak_off is not monotone");
-            if (r.peak_off[i + 1] - r.peak_off[i] > (uint64_t)INT32_MAX)
-                return fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_tmt: a spectrum of more than 2^31 - 1 peaks (peak_index is i32)");
-        }
-        if (r.peak_off[r.n_spectra] && (!r.mz || !r.intensities)) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: missing peak arrays");
-        n_total += r.n_spectra;
-    }
-    if (n_total && L && !out->intensity) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null output array");
-    out->upload_ms = out->process_ms = out->extract_ms = out->device_ms = 0.0f;
-    if (!n_total || !L) return SAGE_HIP_OK;
-    // each label's window in f32 on the host: Tolerance::bounds, then + offset (-PROTON); the region is their union's hull
-    const sagecore::Tol tol{in->tolerance.kind, in->tolerance.lo, in->tolerance.hi};
-    std::vector<float> lo(L), hi(L);
-    float region_lo = INFINITY, region_hi = -INFINITY;
-    for (uint32_t k = 0; k < L; ++k) {
-        sagecore::offset_bounds(tol, in->labels[k], -sagecore::PROTON, lo[k], hi[k]);
-        if (lo[k] < region_lo) region_lo = lo[k];
-        if (hi[k] > region_hi) region_hi = hi[k];
-    }
-    HIP_TRY(hipSetDevice(device));
-    struct Stream {
-        hipStream_t s = nullptr;
-        hipEvent_t e[4] = {};
-        ~Stream() {
-            for (hipEvent_t x : e)
-                if (x) (void)hipEventDestroy(x);
-            if (s) (void)hipStreamDestroy(s);
-        }
-    } cx;
-    HIP_TRY(hipStreamCreateWithFlags(&cx.s, hipStreamNonBlocking));
-    for (auto& e : cx.e) HIP_TRY(hipEventCreate(&e));
-    DevBuf<float> dlo, dhi, dint;
-    DevBuf<int32_t> didx;
-    HIP_TRY(dlo.upload(lo.data(), L));
-    HIP_TRY(dhi.upload(hi.data(), L));
-    uint64_t row = 0;
-    for (uint32_t b = 0; b < in->n_batches; ++b) {
-        const SageRawBatch& r = in->batches[b];
-        const uint32_t n = r.n_spectra;
-        if (!n) continue;
-        const uint64_t total = r.peak_off[n], cells = (uint64_t)n * L;
-        HIP_TRY(dint.reserve(cells));
-        if (out->peak_index) HIP_TRY(didx.reserve(cells));
-        HIP_TRY(hipEventRecord(cx.e[0], cx.s));
-        ProcessScratch w;
-        DevBuf<uint64_t> poff;
-        DevBuf<float> pm, pi, tic;
-        if (ms2) {  // the search's own preprocessing (min_peaks 0: every spectrum is quantified, runner.rs:334-359)
-            std::vector<uint32_t> counts;
-            std::vector<uint64_t> off;
-            if (int rc = process_raw_on_device(&r, in->take_top_n, in->deisotope, in->min_deisotope_mz, 0, cx.s, w, poff, pm, pi, tic,
-                                               counts, off);
-                rc != SAGE_HIP_OK)
-                return rc;
-        } else {    // mass = mz - PROTON in the kernel; the raw peaks as given
-            HIP_TRY(poff.alloc((size_t)n + 1));
-            HIP_TRY(pm.alloc(total));
-            HIP_TRY(pi.alloc(total));
-            HIP_TRY(hipMemcpyAsync(poff.p, r.peak_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, cx.s));
-            if (total) {
-                HIP_TRY(hipMemcpyAsync(pm.p, r.mz, total * 4, hipMemcpyHostToDevice, cx.s));
-                HIP_TRY(hipMemcpyAsync(pi.p, r.intensities, total * 4, hipMemcpyHostToDevice, cx.s));
-            }
-        }
-        HIP_TRY(hipEventRecord(cx.e[1], cx.s));
-        launch_tmt_extract(n, poff.p, pm.p, pi.p, !ms2, dlo.p, dhi.p, L, region_lo, region_hi, dint.p,
-                           out->peak_index ? didx.p : nullptr, cx.s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(cx.e[2], cx.s));
-        HIP_TRY(hipMemcpyAsync(out->intensity + row * L, dint.p, cells * 4, hipMemcpyDeviceToHost, cx.s));
-        if (out->peak_index) HIP_TRY(hipMemcpyAsync(out->peak_index + row * L, didx.p, cells * 4, hipMemcpyDeviceToHost, cx.s));
-        HIP_TRY(hipEventRecord(cx.e[3], cx.s));
-        HIP_TRY(hipStreamSynchronize(cx.s));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, cx.e[0], cx.e[1]));
-        (ms2 ? out->process_ms : out->upload_ms) += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, cx.e[1], cx.e[2]));
-        out->extract_ms += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, cx.e[0], cx.e[3]));
-        out->device_ms += ms;
-        row += n;
-    }
-    return SAGE_HIP_OK;
+    std::string err;
+    const int rc = tmt_on_device(device, *in, *out, err);
+    return rc == SAGE_HIP_OK ? rc : fail(rc, err);
 }
 
 void sage_hip_batch_free(SageDeviceBatch* b) {

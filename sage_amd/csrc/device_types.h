@@ -259,32 +259,21 @@ struct SideStream {
 void launch_prelim_tile(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const DevWork& w, void* stream,
                         const SideStream* side = nullptr);
 uint32_t queries_per_spectrum(const DevScorer& sc);
-// index_build.hip (both return a hipError_t)
+// index_build.hip (each returns a hipError_t)
 int generate_fragments_on_device(uint64_t np, uint32_t nk, const uint8_t* d_kinds, const uint64_t* d_seq_off, const uint8_t* d_seq,
                                  const float* d_mods, const float* d_nterm, const float* d_mono, uint64_t min_ion_index,
                                  const uint64_t* d_ion_off, const uint64_t* d_pm_off, float* d_ions, SageTheoretical* d_pm_frag,
                                  void* stream);
 int ion_abs_range_on_device(const float* d_ions, uint64_t n, uint32_t* lo_bits, uint32_t* hi_bits);
 int rebuild_peptide_major_on_device(const SageTheoretical* d_tm_frag, uint64_t nf, SageTheoretical* d_pm_frag, void* stream);
-int build_tile_copy_on_device(const SageTheoretical* d_pm_frag, uint64_t nf, uint32_t tile_shift, uint32_t n_tiles,
-                              const uint64_t* d_tile_off, float lut_scale, SageTheoretical* d_tm_frag, uint32_t** d_lut_out,
-                              uint32_t* lut_stride_out, void* stream, int layout = 0);
-// lut[n_tiles][lut_stride] (row-major, as build_tile_copy_on_device makes it) -> its succinct form; the arrays are allocated here
-int build_succinct_lut_on_device(const uint32_t* d_lut, uint32_t n_tiles, uint32_t lut_stride, sagecore::LutWord** d_l1_out, uint32_t** d_pos_out,
-                                 uint32_t* words_out, uint64_t* n_pos_out, void* stream);
-int build_peptide_mass_lut(const float* d_pep_mono, uint32_t np, float top_mass, uint32_t** d_lut_out, uint32_t* bins_out, float* inv_w_out,
-                           void* stream);
+// (build_tile_copy_on_device, build_succinct_lut_on_device, build_peptide_mass_lut: hip_host.h — they fill owning buffers)
 // rescore.hip
 int rescore_on_device(int device, const SageRescoreInput& in, SageRescoreOutput& out, std::string& err);
 int predict_rt_on_device(int device, const SageRtInput& in, SageRtOutput& out, std::string& err);
 // lfq.hip
 int lfq_on_device(int device, const SageLfqInput& in, const SageLfqMobility* mobility, SageLfqOutput& out, std::string& err);
-// tmt.hip: reporter-ion extraction, one wavefront per spectrum (peaks [off[i], off[i+1]); subtract_proton: the array holds raw
-// m/z); lo / hi: each label's window with the offset applied; region: [min lo, max hi].  out_*: [n * n_labels]
-void launch_tmt_extract(uint32_t n, const uint64_t* off, const float* mass_or_mz, const float* inten, bool subtract_proton,
-                        const float* lo, const float* hi, uint32_t n_labels, float region_lo, float region_hi, float* out_int,
-                        int32_t* out_idx, void* stream);
-// process.hip
+// tmt.hip: sage_hip_tmt behind its null-argument checks
+int tmt_on_device(int device, const SageTmtInput& in, SageTmtOutput& out, std::string& err);
 // launch schedule of a batch (index_build.hip): order[k] = spectrum scored by block k, ascending neutral precursor mass
 size_t schedule_temp_bytes(uint32_t n);
 int schedule_on_device(uint32_t n, const float* d_precursor_mz, const uint8_t* d_charge, uint32_t min_charge, uint32_t* d_keys_a,
@@ -292,6 +281,7 @@ int schedule_on_device(uint32_t n, const float* d_precursor_mz, const uint8_t* d
 void schedule_records_on_device(uint32_t n, const uint32_t* d_order, const uint64_t* d_peak_off, const float* d_precursor_mz,
                                 const uint8_t* d_charge, const float* d_iso_lo, const float* d_iso_hi, const uint8_t* d_iso_kind,
                                 uint4* d_sched, void* stream);
+// process.hip (process_raw_on_device: hip_host.h)
 size_t process_lds_bytes(uint32_t rcap, uint32_t rpow2);
 int process_kernel_prepare(size_t max_lds_bytes);
 void launch_process(uint32_t n, const uint64_t* raw_off, const float* raw_mz, const float* raw_int, const uint8_t* charge,

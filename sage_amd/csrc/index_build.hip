@@ -19,6 +19,8 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "device_types.h"
+#define HIP_FAILED(e, what) (int)(e)  // (what a failed HIP_TRY returns here)
+#include "hip_host.h"
 
 using namespace sagecore;
 
@@ -170,27 +172,20 @@ __global__ __launch_bounds__(256) void ion_range_kernel(uint64_t n, const float*
 
 }  // namespace
 
-#define BUILD_TRY(expr)                  \
-    do {                                 \
-        hipError_t _e = (expr);          \
-        if (_e != hipSuccess) return _e; \
-    } while (0)
-
-// Both functions return a hipError_t; all pointers are device pointers.
+// Every function below returns a hipError_t; all pointers are device pointers.  Scratch lives in DevBufs, so an early return frees it.
 
 // The range of |ion| over the n entries of the rescoring table (bit patterns of f32; n == 0: {0xFFFFFFFF, 0}).
 int ion_abs_range_on_device(const float* d_ions, uint64_t n, uint32_t* lo_bits, uint32_t* hi_bits) {
-    uint32_t* d_out = nullptr;
+    DevBuf<uint32_t> d_out;
     uint32_t h[2] = {0xFFFFFFFFu, 0u};
-    BUILD_TRY(hipMalloc(&d_out, sizeof(h)));
-    hipError_t e = hipMemcpy(d_out, h, sizeof(h), hipMemcpyHostToDevice);
+    HIP_TRY(d_out.alloc(2));
+    hipError_t e = hipMemcpy(d_out.p, h, sizeof(h), hipMemcpyHostToDevice);
     if (e == hipSuccess && n) {
         const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 4096);
-        hipLaunchKernelGGL(ion_range_kernel, dim3(grid), dim3(256), 0, 0, n, d_ions, d_out);
+        hipLaunchKernelGGL(ion_range_kernel, dim3(grid), dim3(256), 0, 0, n, d_ions, d_out.p);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpy(h, d_out, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(d_out);
+    if (e == hipSuccess) e = hipMemcpy(h, d_out.p, sizeof(h), hipMemcpyDeviceToHost);
     *lo_bits = h[0];
     *hi_bits = h[1];
     return e;
@@ -225,43 +220,61 @@ __global__ __launch_bounds__(256) void pepmass_lut_kernel(const float* __restric
     }
     lut[b] = lo;
 }
-int build_peptide_mass_lut(const float* d_pep_mono, uint32_t np, float top_mass, uint32_t** d_lut_out, uint32_t* bins_out, float* inv_w_out,
+int build_peptide_mass_lut(const float* d_pep_mono, uint32_t np, float top_mass, DevBuf<uint32_t>& lut, uint32_t* bins_out, float* inv_w_out,
                            void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    *d_lut_out = nullptr;
     *bins_out = 0;
     *inv_w_out = 0.0f;
     if (np == 0 || !(top_mass >= 0.0f) || !(top_mass < 1.0e30f)) return (int)hipSuccess;
     float inv_w = 128.0f;  // 1/128 Da: ~4 peptides of a human tryptic database per bin on average
     while ((double)top_mass * inv_w + 2.0 > 4194304.0) inv_w *= 0.5f;
     const uint32_t bins = (uint32_t)((double)top_mass * inv_w) + 1u;
-    uint32_t* d_lut = nullptr;
-    BUILD_TRY(hipMalloc((void**)&d_lut, ((size_t)bins + 1) * 4));
-    hipLaunchKernelGGL(pepmass_lut_kernel, dim3((bins + 1 + 255) / 256), dim3(256), 0, stream, d_pep_mono, np, bins, inv_w, d_lut);
-    BUILD_TRY(hipGetLastError());
-    BUILD_TRY(hipStreamSynchronize(stream));
-    *d_lut_out = d_lut;
+    HIP_TRY(lut.alloc((size_t)bins + 1));
+    hipLaunchKernelGGL(pepmass_lut_kernel, dim3((bins + 1 + 255) / 256), dim3(256), 0, stream, d_pep_mono, np, bins, inv_w, lut.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     *bins_out = bins;
     *inv_w_out = inv_w;
     return (int)hipSuccess;
 }
 
+namespace {
+// The nf entries of `src` in (tile, m/z, peptide) order for tiles of 2^tile_shift peptides -> dst ([nf + 2], padded): one radix
+// sort of 64-bit keys.  Enqueued on `stream`; `s` holds the keys until the caller has synchronised.
+struct SortScratch {  // (released in the order k_in, k_out, tmp)
+    DevBuf<unsigned char> tmp;
+    DevBuf<uint64_t> k_out, k_in;
+};
+int sort_entries_on_device(const SageTheoretical* src, uint64_t nf, uint32_t tile_shift, SageTheoretical* dst, SortScratch& s,
+                           hipStream_t stream) {
+    HIP_TRY(s.k_in.alloc(nf));
+    HIP_TRY(s.k_out.alloc(nf));
+    if (nf) {
+        hipLaunchKernelGGL(encode_kernel, dim3((uint32_t)((nf + 255) / 256)), dim3(256), 0, stream, nf, tile_shift, src, s.k_in.p);
+        HIP_TRY(with_scratch(s.tmp, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, s.k_in.p, s.k_out.p, nf, 0, 64, stream); }));
+    }
+    hipLaunchKernelGGL(decode_kernel, dim3((uint32_t)((nf + 2 + 255) / 256)), dim3(256), 0, stream, nf, tile_shift, s.k_out.p, dst);
+    HIP_TRY(hipGetLastError());
+    return (int)hipSuccess;
+}
+}  // namespace
+
 // A tile-major copy of the peptide-major list for tiles of 2^tile_shift peptides (d_tile_off: [n_tiles + 1] fragment
 // offsets of the tile boundaries) + its position table at `lut_scale` cells per Da.  d_tm_frag ([nf + 2]) is the caller's,
 // the table is allocated here (its width depends on the largest fragment m/z).
 int build_tile_copy_on_device(const SageTheoretical* d_pm_frag, uint64_t nf, uint32_t tile_shift, uint32_t n_tiles,
-                              const uint64_t* d_tile_off, float lut_scale, SageTheoretical* d_tm_frag, uint32_t** d_lut_out,
+                              const uint64_t* d_tile_off, float lut_scale, SageTheoretical* d_tm_frag, DevBuf<uint32_t>& lut,
                               uint32_t* lut_stride_out, void* stream_, int layout) {
     hipStream_t stream = (hipStream_t)stream_;
     // largest finite fragment m/z -> table width
-    uint32_t* d_max = nullptr;
-    BUILD_TRY(hipMalloc((void**)&d_max, 256 * 4));
-    BUILD_TRY(hipMemsetAsync(d_max, 0, 256 * 4, stream));
-    if (nf) hipLaunchKernelGGL(maxmz_kernel, dim3((uint32_t)((nf + 255) / 256)), dim3(256), 0, stream, nf, d_pm_frag, d_max);
+    DevBuf<uint32_t> d_max;
+    HIP_TRY(d_max.alloc(256));
+    HIP_TRY(hipMemsetAsync(d_max.p, 0, 256 * 4, stream));
+    if (nf) hipLaunchKernelGGL(maxmz_kernel, dim3((uint32_t)((nf + 255) / 256)), dim3(256), 0, stream, nf, d_pm_frag, d_max.p);
     uint32_t max_slots[256] = {};
-    BUILD_TRY(hipMemcpyAsync(max_slots, d_max, 256 * 4, hipMemcpyDeviceToHost, stream));
-    BUILD_TRY(hipStreamSynchronize(stream));
-    (void)hipFree(d_max);
+    HIP_TRY(hipMemcpyAsync(max_slots, d_max.p, 256 * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    d_max.release();
     uint32_t max_bits = 0;  // positive floats order like their bit patterns
     for (uint32_t v : max_slots) max_bits = v > max_bits ? v : max_bits;
     float max_mz;
@@ -269,63 +282,30 @@ int build_tile_copy_on_device(const SageTheoretical* d_pm_frag, uint64_t nf, uin
     const double cells = ceil((double)max_mz * lut_scale) + 3.0;
     const uint32_t lut_stride = (uint32_t)(cells < 64.0e6 ? cells : 64.0e6);
     if ((double)n_tiles * lut_stride > 4.0e9) return (int)hipErrorInvalidValue;
-    // (tile, m/z, peptide) order: one radix sort of 64-bit keys
-    uint64_t *k_in = nullptr, *k_out = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    BUILD_TRY(hipMalloc((void**)&k_in, (nf ? nf : 1) * 8));
-    BUILD_TRY(hipMalloc((void**)&k_out, (nf ? nf : 1) * 8));
-    if (nf) {
-        hipLaunchKernelGGL(encode_kernel, dim3((uint32_t)((nf + 255) / 256)), dim3(256), 0, stream, nf, tile_shift, d_pm_frag, k_in);
-        BUILD_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, k_in, k_out, nf, 0, 64, stream));
-        BUILD_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1));
-        BUILD_TRY(rocprim::radix_sort_keys(tmp, tmp_bytes, k_in, k_out, nf, 0, 64, stream));
-    }
-    hipLaunchKernelGGL(decode_kernel, dim3((uint32_t)((nf + 2 + 255) / 256)), dim3(256), 0, stream, nf, tile_shift, k_out, d_tm_frag);
-    BUILD_TRY(hipGetLastError());
-    uint32_t* d_lut = nullptr;
+    SortScratch keys;
+    if (int e = sort_entries_on_device(d_pm_frag, nf, tile_shift, d_tm_frag, keys, stream)) return e;
     const uint64_t lut_n = (uint64_t)(layout == 2 ? (n_tiles + 3u) & ~3u : n_tiles) * lut_stride;
-    BUILD_TRY(hipMalloc((void**)&d_lut, (lut_n ? lut_n : 1) * 4));
+    HIP_TRY(lut.alloc(lut_n));
     const dim3 lut_grid((uint32_t)((lut_n + 255) / 256));
     if (layout == 2)
-        hipLaunchKernelGGL(lut_kernel<2>, lut_grid, dim3(256), 0, stream, n_tiles, lut_stride, lut_scale, d_tile_off, d_tm_frag, d_lut);
+        hipLaunchKernelGGL(lut_kernel<2>, lut_grid, dim3(256), 0, stream, n_tiles, lut_stride, lut_scale, d_tile_off, d_tm_frag, lut.p);
     else if (layout == 1)
-        hipLaunchKernelGGL(lut_kernel<1>, lut_grid, dim3(256), 0, stream, n_tiles, lut_stride, lut_scale, d_tile_off, d_tm_frag, d_lut);
+        hipLaunchKernelGGL(lut_kernel<1>, lut_grid, dim3(256), 0, stream, n_tiles, lut_stride, lut_scale, d_tile_off, d_tm_frag, lut.p);
     else
-        hipLaunchKernelGGL(lut_kernel<0>, lut_grid, dim3(256), 0, stream, n_tiles, lut_stride, lut_scale, d_tile_off, d_tm_frag, d_lut);
-    BUILD_TRY(hipGetLastError());
-    BUILD_TRY(hipStreamSynchronize(stream));
-    (void)hipFree(k_in);
-    (void)hipFree(k_out);
-    if (tmp) (void)hipFree(tmp);
-    *d_lut_out = d_lut;
+        hipLaunchKernelGGL(lut_kernel<0>, lut_grid, dim3(256), 0, stream, n_tiles, lut_stride, lut_scale, d_tile_off, d_tm_frag, lut.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     *lut_stride_out = lut_stride;
     return (int)hipSuccess;
 }
 
-
 // The peptide-major fragment list out of a tile-major copy (either one: they hold the same entries): the tile copy's own sort with
 // tiles of ONE peptide — the key is (peptide, m/z).  The order inside a peptide is by m/z, not by (kind, ion index) as generated; the
 // stream variant of the preliminary kernels, the list's only reader, counts matches and does not care.  d_pm_frag: [nf + 2].
-int rebuild_peptide_major_on_device(const SageTheoretical* d_tm_frag, uint64_t nf, SageTheoretical* d_pm_frag, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    uint64_t *k_in = nullptr, *k_out = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    BUILD_TRY(hipMalloc((void**)&k_in, (nf ? nf : 1) * 8));
-    BUILD_TRY(hipMalloc((void**)&k_out, (nf ? nf : 1) * 8));
-    if (nf) {
-        hipLaunchKernelGGL(encode_kernel, dim3((uint32_t)((nf + 255) / 256)), dim3(256), 0, stream, nf, 0u, d_tm_frag, k_in);
-        BUILD_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, k_in, k_out, nf, 0, 64, stream));
-        BUILD_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1));
-        BUILD_TRY(rocprim::radix_sort_keys(tmp, tmp_bytes, k_in, k_out, nf, 0, 64, stream));
-    }
-    hipLaunchKernelGGL(decode_kernel, dim3((uint32_t)((nf + 2 + 255) / 256)), dim3(256), 0, stream, nf, 0u, k_out, d_pm_frag);
-    BUILD_TRY(hipGetLastError());
-    BUILD_TRY(hipStreamSynchronize(stream));
-    (void)hipFree(k_in);
-    (void)hipFree(k_out);
-    if (tmp) (void)hipFree(tmp);
+int rebuild_peptide_major_on_device(const SageTheoretical* d_tm_frag, uint64_t nf, SageTheoretical* d_pm_frag, void* stream) {
+    SortScratch keys;
+    if (int e = sort_entries_on_device(d_tm_frag, nf, 0u, d_pm_frag, keys, (hipStream_t)stream)) return e;
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return (int)hipSuccess;
 }
 
@@ -369,45 +349,35 @@ __global__ __launch_bounds__(256) void lut_fill_kernel(const uint32_t* __restric
 }
 }  // namespace
 
-int build_succinct_lut_on_device(const uint32_t* d_lut, uint32_t n_tiles, uint32_t lut_stride, sagecore::LutWord** d_l1_out, uint32_t** d_pos_out,
-                                 uint32_t* words_out, uint64_t* n_pos_out, void* stream_) {
+int build_succinct_lut_on_device(const uint32_t* d_lut, uint32_t n_tiles, uint32_t lut_stride, DevBuf<sagecore::LutWord>& l1,
+                                 DevBuf<uint32_t>& pos, uint32_t* words_out, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const uint32_t words = (lut_stride + 31) / 32;
     const uint64_t n = (uint64_t)n_tiles * words;
-    sagecore::LutWord* d_l1 = nullptr;
-    uint32_t *d_counts = nullptr, *d_ranks = nullptr, *d_pos = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    BUILD_TRY(hipMalloc((void**)&d_l1, (n ? n : 1) * sizeof(sagecore::LutWord)));
-    BUILD_TRY(hipMalloc((void**)&d_counts, (n ? n : 1) * 4));
-    BUILD_TRY(hipMalloc((void**)&d_ranks, (n ? n : 1) * 4));
-    uint64_t total = 0;
+    DevBuf<unsigned char> tmp;  // (released in the order counts, ranks, tmp)
+    DevBuf<uint32_t> ranks, counts;
+    HIP_TRY(l1.alloc(n));
+    HIP_TRY(counts.alloc(n));
+    HIP_TRY(ranks.alloc(n));
     if (n) {
         const dim3 grid((uint32_t)((n + 255) / 256));
-        hipLaunchKernelGGL(lut_bits_kernel, grid, dim3(256), 0, stream, d_lut, n_tiles, lut_stride, words, d_l1, d_counts);
-        BUILD_TRY(hipGetLastError());
-        BUILD_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, d_counts, d_ranks, 0u, n, rocprim::plus<uint32_t>(), stream));
-        BUILD_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1));
-        BUILD_TRY(rocprim::exclusive_scan(tmp, tmp_bytes, d_counts, d_ranks, 0u, n, rocprim::plus<uint32_t>(), stream));
+        hipLaunchKernelGGL(lut_bits_kernel, grid, dim3(256), 0, stream, d_lut, n_tiles, lut_stride, words, l1.p, counts.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(with_scratch(tmp, [&](void* t, size_t& b) {
+            return rocprim::exclusive_scan(t, b, counts.p, ranks.p, 0u, n, rocprim::plus<uint32_t>(), stream);
+        }));
         uint32_t last_rank = 0, last_count = 0;
-        BUILD_TRY(hipMemcpyAsync(&last_rank, d_ranks + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-        BUILD_TRY(hipMemcpyAsync(&last_count, d_counts + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-        BUILD_TRY(hipStreamSynchronize(stream));
-        total = (uint64_t)last_rank + last_count;  // (<= entries + tiles < 2^32: capi.hip refuses more fragments)
-        BUILD_TRY(hipMalloc((void**)&d_pos, (total ? total : 1) * 4));
-        hipLaunchKernelGGL(lut_fill_kernel, grid, dim3(256), 0, stream, d_lut, n_tiles, lut_stride, words, d_ranks, d_l1, d_pos);
-        BUILD_TRY(hipGetLastError());
-        BUILD_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(&last_rank, ranks.p + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&last_count, counts.p + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(pos.alloc((uint64_t)last_rank + last_count));  // (>= 1, <= entries + tiles < 2^32: capi.hip refuses more fragments)
+        hipLaunchKernelGGL(lut_fill_kernel, grid, dim3(256), 0, stream, d_lut, n_tiles, lut_stride, words, ranks.p, l1.p, pos.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
     } else {
-        BUILD_TRY(hipMalloc((void**)&d_pos, 4));
+        HIP_TRY(pos.alloc(1));
     }
-    (void)hipFree(d_counts);
-    (void)hipFree(d_ranks);
-    if (tmp) (void)hipFree(tmp);
-    *d_l1_out = d_l1;
-    *d_pos_out = d_pos;
     *words_out = words;
-    *n_pos_out = total;
     return (int)hipSuccess;
 }
 

@@ -36,8 +36,8 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
-#include "../../include/sage_hip.h"
 #include "core.h"
+#include "hip_host.h"
 
 namespace sagehip {
 
@@ -51,46 +51,6 @@ constexpr uint32_t PAGE = 16 * 1024;   // lfq.rs:176
 constexpr int SLACK = 75;              // lfq.rs:371
 constexpr int IB = 256;                // threads of an integration block
 constexpr int TB = 256;                // threads of a row-parallel block
-
-struct LfqCtx {
-    hipStream_t stream = nullptr;
-    std::string err;
-    int code = SAGE_HIP_OK;
-    bool check(hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        code = e == hipErrorOutOfMemory ? SAGE_HIP_ERR_OOM : SAGE_HIP_ERR_HIP;
-        err = std::string("sage_hip_lfq: ") + what + ": " + hipGetErrorString(e);
-        return false;
-    }
-};
-#define LQ_TRY(expr)                              \
-    do {                                          \
-        if (!cx.check((expr), #expr)) return false; \
-    } while (0)
-
-template <class T>
-struct DBuf {
-    T* p = nullptr;
-    DBuf() = default;
-    DBuf(const DBuf&) = delete;
-    DBuf& operator=(const DBuf&) = delete;
-    ~DBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-    }
-};
-
-struct Events {
-    hipEvent_t e[5] = {};
-    ~Events() {
-        for (auto& x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 SAGE_HD uint32_t total_key(float f) {  // ascending u32 order == f32::total_cmp
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -590,19 +550,9 @@ inline uint32_t bits_for(uint64_t n) {  // radix-sort key width that holds 0..n-
     return b;
 }
 
-template <class Launch>
-bool radix(LfqCtx& cx, Launch&& launch) {  // the two-call rocPRIM protocol
-    size_t bytes = 0;
-    LQ_TRY(launch((void*)nullptr, bytes));
-    DBuf<uint8_t> tmp;
-    LQ_TRY(tmp.alloc(bytes));
-    LQ_TRY(launch((void*)tmp.p, bytes));
-    return true;
-}
-
 inline uint32_t blocks(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 
-bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobility, SageLfqOutput& out) {
+bool lfq_impl(Ctx& cx, const SageLfqInput& in, const SageLfqMobility* mobility, SageLfqOutput& out) {
     const SageLfqSettings& st = in.settings;
     // ion mobility takes part only if some spectrum of the call has the column (lfq.rs:267 decides per spectrum)
     bool im = false;
@@ -615,9 +565,9 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobilit
     const bool combine = st.combine_charge_states != 0;
     const float ppm = std::fabs(st.ppm_tolerance);
     const double sa_thr = std::fabs(st.spectral_angle);
-    Events ev;
-    for (auto& e : ev.e) LQ_TRY(hipEventCreate(&e));
-    LQ_TRY(hipEventRecord(ev.e[0], cx.stream));
+    Events<5> ev;
+    HIP_TRY(ev.create());
+    HIP_TRY(hipEventRecord(ev[0], cx.stream));
 
     // -- feature map: selection (lfq.rs:99-141) on the host, features in confidence order
     std::vector<uint8_t> seen(in.n_peptides, 0);
@@ -680,47 +630,45 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobilit
         }
     }
     const uint32_t n_pages = (W + PAGE - 1) / PAGE;
-    DBuf<float> d_sel_rt, d_sel_mass, g_rt, g_lo, g_hi, w_rt, w_lo, w_hi;
-    DBuf<uint64_t> k1, k1s, k2, k2s;
-    DBuf<uint32_t> pos, gen, w_lo_key, min_rt_key;
-    LQ_TRY(d_sel_rt.alloc(S));
-    LQ_TRY(d_sel_mass.alloc(S));
-    for (auto* b : {&g_rt, &g_lo, &g_hi, &w_rt, &w_lo, &w_hi}) LQ_TRY(b->alloc(W));
-    for (auto* b : {&k1, &k1s, &k2, &k2s}) LQ_TRY(b->alloc(W));
-    for (auto* b : {&pos, &gen, &w_lo_key}) LQ_TRY(b->alloc(W));
-    LQ_TRY(min_rt_key.alloc(n_pages));
+    DevBuf<float> d_sel_rt, d_sel_mass, g_rt, g_lo, g_hi, w_rt, w_lo, w_hi;
+    DevBuf<uint64_t> k1, k1s, k2, k2s;
+    DevBuf<uint32_t> pos, gen, w_lo_key, min_rt_key;
+    HIP_TRY(d_sel_rt.alloc(S));
+    HIP_TRY(d_sel_mass.alloc(S));
+    for (auto* b : {&g_rt, &g_lo, &g_hi, &w_rt, &w_lo, &w_hi}) HIP_TRY(b->alloc(W));
+    for (auto* b : {&k1, &k1s, &k2, &k2s}) HIP_TRY(b->alloc(W));
+    for (auto* b : {&pos, &gen, &w_lo_key}) HIP_TRY(b->alloc(W));
+    HIP_TRY(min_rt_key.alloc(n_pages));
     if (S) {
-        LQ_TRY(hipMemcpyAsync(d_sel_rt.p, sel_rt.data(), S * 4, hipMemcpyHostToDevice, cx.stream));
-        LQ_TRY(hipMemcpyAsync(d_sel_mass.p, sel_mass.data(), S * 4, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_sel_rt.p, sel_rt.data(), S * 4, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_sel_mass.p, sel_mass.data(), S * 4, hipMemcpyHostToDevice, cx.stream));
     }
     if (W) {
         windows_kernel<<<blocks(W, TB), TB, 0, cx.stream>>>(W, nz, zmin, ppm, d_sel_rt.p, d_sel_mass.p, g_rt.p, g_lo.p, g_hi.p, k1.p);
-        if (!radix(cx, [&](void* t, size_t& b) {
+        HIP_TRY(with_scratch<DevBuf<uint8_t>>([&](void* t, size_t& b) {
                 return rocprim::radix_sort_keys(t, b, k1.p, k1s.p, (size_t)W, 0, 64, cx.stream);
-            }))
-            return false;
+            }));
         page_keys_kernel<<<blocks(W, TB), TB, 0, cx.stream>>>(W, k1s.p, g_lo.p, k2.p, pos.p, min_rt_key.p);
         // stable: equal (page, mass_lo) keep their rt order
-        if (!radix(cx, [&](void* t, size_t& b) {
+        HIP_TRY(with_scratch<DevBuf<uint8_t>>([&](void* t, size_t& b) {
                 return rocprim::radix_sort_pairs(t, b, k2.p, k2s.p, pos.p, gen.p, (size_t)W, 0, 32 + bits_for(n_pages), cx.stream);
-            }))
-            return false;
+            }));
         gather_windows_kernel<<<blocks(W, TB), TB, 0, cx.stream>>>(W, gen.p, g_rt.p, g_lo.p, g_hi.p, w_rt.p, w_lo.p, w_hi.p,
                                                                    w_lo_key.p);
-        LQ_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    DBuf<float> d_sel_ims;
-    DBuf<float2> d_sel_mob, w_mob;
+    DevBuf<float> d_sel_ims;
+    DevBuf<float2> d_sel_mob, w_mob;
     if (im && W) {
-        LQ_TRY(d_sel_ims.alloc(S));
-        LQ_TRY(d_sel_mob.alloc(S));
-        LQ_TRY(w_mob.alloc(W));
-        LQ_TRY(hipMemcpyAsync(d_sel_ims.p, sel_ims.data(), S * 4, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(d_sel_ims.alloc(S));
+        HIP_TRY(d_sel_mob.alloc(S));
+        HIP_TRY(w_mob.alloc(W));
+        HIP_TRY(hipMemcpyAsync(d_sel_ims.p, sel_ims.data(), S * 4, hipMemcpyHostToDevice, cx.stream));
         mobility_bounds_kernel<<<blocks(S, TB), TB, 0, cx.stream>>>((uint32_t)S, st.mobility_pct_tolerance, d_sel_ims.p, d_sel_mob.p);
         gather_mobility_kernel<<<blocks(W, TB), TB, 0, cx.stream>>>(W, nz * N_ISO * 2, gen.p, d_sel_mob.p, w_mob.p);
-        LQ_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    LQ_TRY(hipEventRecord(ev.e[1], cx.stream));
+    HIP_TRY(hipEventRecord(ev[1], cx.stream));
 
     // -- MS1 spectra: concatenated in the order given
     uint64_t n_spec64 = 0, n_peaks = 0;
@@ -767,68 +715,67 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobilit
             batch_p0[b + 1] = p0;
         }
     }
-    DBuf<uint64_t> d_off;
-    DBuf<float> d_mz, d_int_raw, d_mass, d_int, d_sst;
-    DBuf<uint32_t> d_file, mk, mks, mi, mis;
-    DBuf<SageAlignment> d_al;
-    LQ_TRY(d_off.alloc(n_spec + 1));
-    for (auto* b : {&d_mz, &d_int_raw, &d_mass, &d_int}) LQ_TRY(b->alloc(n_peaks));
-    for (auto* b : {&mk, &mks, &mi, &mis}) LQ_TRY(b->alloc(n_peaks));
-    LQ_TRY(d_sst.alloc(n_spec));
-    LQ_TRY(d_file.alloc(n_spec));
-    LQ_TRY(d_al.alloc(F));
-    LQ_TRY(hipMemcpyAsync(d_off.p, h_off.data(), (n_spec + 1) * 8, hipMemcpyHostToDevice, cx.stream));
+    DevBuf<uint64_t> d_off;
+    DevBuf<float> d_mz, d_int_raw, d_mass, d_int, d_sst;
+    DevBuf<uint32_t> d_file, mk, mks, mi, mis;
+    DevBuf<SageAlignment> d_al;
+    HIP_TRY(d_off.alloc(n_spec + 1));
+    for (auto* b : {&d_mz, &d_int_raw, &d_mass, &d_int}) HIP_TRY(b->alloc(n_peaks));
+    for (auto* b : {&mk, &mks, &mi, &mis}) HIP_TRY(b->alloc(n_peaks));
+    HIP_TRY(d_sst.alloc(n_spec));
+    HIP_TRY(d_file.alloc(n_spec));
+    HIP_TRY(d_al.alloc(F));
+    HIP_TRY(hipMemcpyAsync(d_off.p, h_off.data(), (n_spec + 1) * 8, hipMemcpyHostToDevice, cx.stream));
     if (n_peaks) {
-        LQ_TRY(hipMemcpyAsync(d_mz.p, h_mz.data(), n_peaks * 4, hipMemcpyHostToDevice, cx.stream));
-        LQ_TRY(hipMemcpyAsync(d_int_raw.p, h_int.data(), n_peaks * 4, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_mz.p, h_mz.data(), n_peaks * 4, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_int_raw.p, h_int.data(), n_peaks * 4, hipMemcpyHostToDevice, cx.stream));
     }
     if (n_spec) {
-        LQ_TRY(hipMemcpyAsync(d_sst.p, h_sst.data(), n_spec * 4, hipMemcpyHostToDevice, cx.stream));
-        LQ_TRY(hipMemcpyAsync(d_file.p, h_file.data(), n_spec * 4, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_sst.p, h_sst.data(), n_spec * 4, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_file.p, h_file.data(), n_spec * 4, hipMemcpyHostToDevice, cx.stream));
     }
-    if (F) LQ_TRY(hipMemcpyAsync(d_al.p, in.alignments, F * sizeof(SageAlignment), hipMemcpyHostToDevice, cx.stream));
+    if (F) HIP_TRY(hipMemcpyAsync(d_al.p, in.alignments, F * sizeof(SageAlignment), hipMemcpyHostToDevice, cx.stream));
     if (n_peaks) {
         ms1_keys_kernel<<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, d_mz.p, mk.p, mi.p);
-        if (!radix(cx, [&](void* t, size_t& b) {
+        HIP_TRY(with_scratch<DevBuf<uint8_t>>([&](void* t, size_t& b) {
                 return rocprim::segmented_radix_sort_pairs(t, b, mk.p, mks.p, mi.p, mis.p, (unsigned int)n_peaks, n_spec,
                                                            d_off.p, d_off.p + 1, 0, 32, cx.stream);
-            }))
-            return false;
+            }));
         ms1_gather_kernel<<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, mks.p, mis.p, d_int_raw.p, d_mass.p, d_int.p);
-        LQ_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    DBuf<float> d_mob_raw, d_mob;
-    DBuf<uint8_t> d_spec_mob;
+    DevBuf<float> d_mob_raw, d_mob;
+    DevBuf<uint8_t> d_spec_mob;
     if (im && n_peaks) {
-        LQ_TRY(d_mob_raw.alloc(n_peaks));
-        LQ_TRY(d_mob.alloc(n_peaks));
-        LQ_TRY(d_spec_mob.alloc(n_spec));
+        HIP_TRY(d_mob_raw.alloc(n_peaks));
+        HIP_TRY(d_mob.alloc(n_peaks));
+        HIP_TRY(d_spec_mob.alloc(n_spec));
         // The column of a batch goes up as it lies in the caller's array: peak_off ascends, so the peaks of a batch are one
         // range of it (no host copy of a third of the MS1 data).  The values inside spectra without mobility are never tested.
         for (uint32_t b = 0; b < in.n_ms1; ++b) {
             const uint64_t n = batch_p0[b + 1] - batch_p0[b];
             if (!n) continue;
             if (mobility[b].mobility)
-                LQ_TRY(hipMemcpyAsync(d_mob_raw.p + batch_p0[b], mobility[b].mobility + in.ms1[b].peak_off[0], n * 4,
+                HIP_TRY(hipMemcpyAsync(d_mob_raw.p + batch_p0[b], mobility[b].mobility + in.ms1[b].peak_off[0], n * 4,
                                       hipMemcpyHostToDevice, cx.stream));
             else
-                LQ_TRY(hipMemsetAsync(d_mob_raw.p + batch_p0[b], 0, n * 4, cx.stream));
+                HIP_TRY(hipMemsetAsync(d_mob_raw.p + batch_p0[b], 0, n * 4, cx.stream));
         }
-        LQ_TRY(hipMemcpyAsync(d_spec_mob.p, h_has.data(), n_spec, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_spec_mob.p, h_has.data(), n_spec, hipMemcpyHostToDevice, cx.stream));
         ms1_gather_mobility_kernel<<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, mis.p, d_mob_raw.p, d_mob.p);
-        LQ_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    LQ_TRY(hipEventRecord(ev.e[2], cx.stream));
+    HIP_TRY(hipEventRecord(ev[2], cx.stream));
 
     // -- traces
     out.n_windows = W;
     out.n_grids = out.n_contributions = out.passing = 0;
-    DBuf<SpecDev> d_spec;
-    DBuf<uint32_t> counts;
-    DBuf<uint64_t> offs;
-    LQ_TRY(d_spec.alloc(n_spec));
-    LQ_TRY(counts.alloc(n_peaks));
-    LQ_TRY(offs.alloc(n_peaks + 1));
+    DevBuf<SpecDev> d_spec;
+    DevBuf<uint32_t> counts;
+    DevBuf<uint64_t> offs;
+    HIP_TRY(d_spec.alloc(n_spec));
+    HIP_TRY(counts.alloc(n_peaks));
+    HIP_TRY(offs.alloc(n_peaks + 1));
     WindowsDev wd{w_rt.p, w_lo.p, w_hi.p, w_lo_key.p, gen.p, W};
     const MobilityDev md{w_mob.p, d_mob.p, d_spec_mob.p};
     uint64_t M = 0;
@@ -837,14 +784,13 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobilit
                                                                         d_spec.p);
         if (im) count_kernel<true><<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, d_off.p, n_spec, d_spec.p, d_mass.p, wd, md, counts.p);
         else count_kernel<false><<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, d_off.p, n_spec, d_spec.p, d_mass.p, wd, md, counts.p);
-        LQ_TRY(hipGetLastError());
-        if (!radix(cx, [&](void* t, size_t& b) {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(with_scratch<DevBuf<uint8_t>>([&](void* t, size_t& b) {
                 return rocprim::inclusive_scan(t, b, counts.p, offs.p + 1, (size_t)n_peaks, rocprim::plus<uint64_t>(), cx.stream);
-            }))
-            return false;
-        LQ_TRY(hipMemsetAsync(offs.p, 0, 8, cx.stream));
-        LQ_TRY(hipMemcpyAsync(&M, offs.p + n_peaks, 8, hipMemcpyDeviceToHost, cx.stream));
-        LQ_TRY(hipStreamSynchronize(cx.stream));
+            }));
+        HIP_TRY(hipMemsetAsync(offs.p, 0, 8, cx.stream));
+        HIP_TRY(hipMemcpyAsync(&M, offs.p + n_peaks, 8, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipStreamSynchronize(cx.stream));
     }
     out.n_contributions = M;
     if (M >= (1ull << 32)) {
@@ -852,15 +798,15 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobilit
         cx.err = "sage_hip_lfq: more than 2^32 (peak, window) matches in one call";
         return false;
     }
-    DBuf<uint32_t> ckey, ckeys, cidx, cidxs, grid_of_slot, slot_of_grid, d_slot_file;
-    DBuf<float> c_rt, c_int, d_slot_rt, d_slot_dist;
-    DBuf<uint8_t> slot_hit;
-    for (auto* b : {&ckey, &ckeys, &cidx, &cidxs}) LQ_TRY(b->alloc(M));
-    LQ_TRY(c_rt.alloc(M));
-    LQ_TRY(c_int.alloc(M));
-    LQ_TRY(slot_hit.alloc(n_slots));
-    LQ_TRY(grid_of_slot.alloc(n_slots));
-    LQ_TRY(hipMemsetAsync(slot_hit.p, 0, std::max<uint32_t>(n_slots, 1), cx.stream));
+    DevBuf<uint32_t> ckey, ckeys, cidx, cidxs, grid_of_slot, slot_of_grid, d_slot_file;
+    DevBuf<float> c_rt, c_int, d_slot_rt, d_slot_dist;
+    DevBuf<uint8_t> slot_hit;
+    for (auto* b : {&ckey, &ckeys, &cidx, &cidxs}) HIP_TRY(b->alloc(M));
+    HIP_TRY(c_rt.alloc(M));
+    HIP_TRY(c_int.alloc(M));
+    HIP_TRY(slot_hit.alloc(n_slots));
+    HIP_TRY(grid_of_slot.alloc(n_slots));
+    HIP_TRY(hipMemsetAsync(slot_hit.p, 0, std::max<uint32_t>(n_slots, 1), cx.stream));
     uint32_t n_grids = 0;
     if (M) {
         SlotMap sm{nz, combine ? 1u : 0u, (uint32_t)rows_per_slot};
@@ -870,23 +816,21 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobilit
         else
             fill_kernel<false><<<blocks(n_peaks, TB), TB, 0, cx.stream>>>(n_peaks, d_off.p, n_spec, d_spec.p, d_file.p, d_mass.p, d_int.p,
                                                                          wd, md, sm, offs.p, ckey.p, cidx.p, c_rt.p, c_int.p, slot_hit.p);
-        LQ_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         // stable: the contributions of one matrix row stay in (spectrum, peak, match) order
-        if (!radix(cx, [&](void* t, size_t& b) {
+        HIP_TRY(with_scratch<DevBuf<uint8_t>>([&](void* t, size_t& b) {
                 return rocprim::radix_sort_pairs(t, b, ckey.p, ckeys.p, cidx.p, cidxs.p, (size_t)M, 0,
                                                  bits_for(n_slots64 * rows_per_slot), cx.stream);
-            }))
-            return false;
-        if (!radix(cx, [&](void* t, size_t& b) {
+            }));
+        HIP_TRY(with_scratch<DevBuf<uint8_t>>([&](void* t, size_t& b) {
                 return rocprim::exclusive_scan(t, b, slot_hit.p, grid_of_slot.p, 0u, (size_t)n_slots, rocprim::plus<uint32_t>(),
                                                cx.stream);
-            }))
-            return false;
+            }));
         uint32_t last = 0;
         uint8_t last_hit = 0;
-        LQ_TRY(hipMemcpyAsync(&last, grid_of_slot.p + n_slots - 1, 4, hipMemcpyDeviceToHost, cx.stream));
-        LQ_TRY(hipMemcpyAsync(&last_hit, slot_hit.p + n_slots - 1, 1, hipMemcpyDeviceToHost, cx.stream));
-        LQ_TRY(hipStreamSynchronize(cx.stream));
+        HIP_TRY(hipMemcpyAsync(&last, grid_of_slot.p + n_slots - 1, 4, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipMemcpyAsync(&last_hit, slot_hit.p + n_slots - 1, 1, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipStreamSynchronize(cx.stream));
         n_grids = last + last_hit;
     }
     out.n_grids = n_grids;
@@ -896,26 +840,26 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobilit
         return false;
     }
     const uint64_t rows_total = (uint64_t)n_grids * rows_per_slot;
-    DBuf<double> matrix, kern, rtf, dotb, angb, d_score, d_sa, d_areas;
-    DBuf<uint32_t> d_peak, d_left, d_right;
-    DBuf<int32_t> d_warps;
-    DBuf<uint8_t> d_has;
-    LQ_TRY(slot_of_grid.alloc(n_grids));
-    LQ_TRY(matrix.alloc(rows_total * GRID));
-    LQ_TRY(d_slot_rt.alloc(n_slots));
-    LQ_TRY(d_slot_file.alloc(n_slots));
-    LQ_TRY(d_slot_dist.alloc((size_t)n_slots * 3));
+    DevBuf<double> matrix, kern, rtf, dotb, angb, d_score, d_sa, d_areas;
+    DevBuf<uint32_t> d_peak, d_left, d_right;
+    DevBuf<int32_t> d_warps;
+    DevBuf<uint8_t> d_has;
+    HIP_TRY(slot_of_grid.alloc(n_grids));
+    HIP_TRY(matrix.alloc(rows_total * GRID));
+    HIP_TRY(d_slot_rt.alloc(n_slots));
+    HIP_TRY(d_slot_file.alloc(n_slots));
+    HIP_TRY(d_slot_dist.alloc((size_t)n_slots * 3));
     if (n_grids) {
-        LQ_TRY(hipMemcpyAsync(d_slot_rt.p, slot_rt.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, cx.stream));
-        LQ_TRY(hipMemcpyAsync(d_slot_file.p, slot_file.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, cx.stream));
-        LQ_TRY(hipMemcpyAsync(d_slot_dist.p, slot_dist.data(), (size_t)n_slots * 12, hipMemcpyHostToDevice, cx.stream));
-        LQ_TRY(hipMemsetAsync(matrix.p, 0, rows_total * GRID * 8, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_slot_rt.p, slot_rt.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_slot_file.p, slot_file.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_slot_dist.p, slot_dist.data(), (size_t)n_slots * 12, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemsetAsync(matrix.p, 0, rows_total * GRID * 8, cx.stream));
         grid_list_kernel<<<blocks(n_slots, TB), TB, 0, cx.stream>>>(n_slots, slot_hit.p, grid_of_slot.p, slot_of_grid.p);
         row_reduce_kernel<<<blocks(rows_total, TB), TB, 0, cx.stream>>>(rows_total, (uint32_t)rows_per_slot, slot_of_grid.p, ckeys.p,
                                                                        cidxs.p, M, c_rt.p, c_int.p, d_slot_rt.p, matrix.p);
-        LQ_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    LQ_TRY(hipEventRecord(ev.e[3], cx.stream));
+    HIP_TRY(hipEventRecord(ev[3], cx.stream));
 
     // -- integration
     const std::vector<double> k = gaussian_kernel(0.5, K_WIDTH);
@@ -924,55 +868,55 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobilit
         const int c = GRID / 2;
         h_rtf[rt] = std::pow(1.0 - ((double)std::abs(rt - c) / (double)c), 0.33);
     }
-    LQ_TRY(kern.alloc(K_WIDTH));
-    LQ_TRY(rtf.alloc(GRID));
-    LQ_TRY(dotb.alloc((size_t)n_grids * F * GRID));
-    LQ_TRY(angb.alloc((size_t)n_grids * F * GRID));
-    LQ_TRY(d_score.alloc(n_grids));
-    LQ_TRY(d_sa.alloc(n_grids));
-    LQ_TRY(d_areas.alloc((size_t)n_grids * F));
-    LQ_TRY(d_peak.alloc(n_grids));
-    LQ_TRY(d_left.alloc(n_grids));
-    LQ_TRY(d_right.alloc(n_grids));
-    LQ_TRY(d_warps.alloc((size_t)n_grids * F));
-    LQ_TRY(d_has.alloc(n_grids));
+    HIP_TRY(kern.alloc(K_WIDTH));
+    HIP_TRY(rtf.alloc(GRID));
+    HIP_TRY(dotb.alloc((size_t)n_grids * F * GRID));
+    HIP_TRY(angb.alloc((size_t)n_grids * F * GRID));
+    HIP_TRY(d_score.alloc(n_grids));
+    HIP_TRY(d_sa.alloc(n_grids));
+    HIP_TRY(d_areas.alloc((size_t)n_grids * F));
+    HIP_TRY(d_peak.alloc(n_grids));
+    HIP_TRY(d_left.alloc(n_grids));
+    HIP_TRY(d_right.alloc(n_grids));
+    HIP_TRY(d_warps.alloc((size_t)n_grids * F));
+    HIP_TRY(d_has.alloc(n_grids));
     std::vector<uint32_t> h_slot(n_grids);
     if (n_grids) {
-        LQ_TRY(hipMemcpyAsync(kern.p, k.data(), K_WIDTH * 8, hipMemcpyHostToDevice, cx.stream));
-        LQ_TRY(hipMemcpyAsync(rtf.p, h_rtf.data(), GRID * 8, hipMemcpyHostToDevice, cx.stream));
-        LQ_TRY(hipMemsetAsync(d_areas.p, 0, (size_t)n_grids * F * 8, cx.stream));
+        HIP_TRY(hipMemcpyAsync(kern.p, k.data(), K_WIDTH * 8, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(rtf.p, h_rtf.data(), GRID * 8, hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemsetAsync(d_areas.p, 0, (size_t)n_grids * F * 8, cx.stream));
         IntegrateArgs A{matrix.p, slot_of_grid.p, d_slot_file.p, d_slot_dist.p, kern.p, rtf.p, dotb.p, angb.p, F,
                         st.peak_scoring, st.integration, sa_thr, d_has.p, d_peak.p, d_left.p, d_right.p, d_score.p, d_sa.p,
                         d_areas.p, d_warps.p};
         integrate_kernel<<<n_grids, IB, 0, cx.stream>>>(A);
-        LQ_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    LQ_TRY(hipEventRecord(ev.e[4], cx.stream));
+    HIP_TRY(hipEventRecord(ev[4], cx.stream));
     if (n_grids) {
-        LQ_TRY(hipMemcpyAsync(h_slot.data(), slot_of_grid.p, (size_t)n_grids * 4, hipMemcpyDeviceToHost, cx.stream));
-        LQ_TRY(hipMemcpyAsync(out.has_peak, d_has.p, n_grids, hipMemcpyDeviceToHost, cx.stream));
-        LQ_TRY(hipMemcpyAsync(out.peak_rt, d_peak.p, (size_t)n_grids * 4, hipMemcpyDeviceToHost, cx.stream));
-        LQ_TRY(hipMemcpyAsync(out.left, d_left.p, (size_t)n_grids * 4, hipMemcpyDeviceToHost, cx.stream));
-        LQ_TRY(hipMemcpyAsync(out.right, d_right.p, (size_t)n_grids * 4, hipMemcpyDeviceToHost, cx.stream));
-        LQ_TRY(hipMemcpyAsync(out.score, d_score.p, (size_t)n_grids * 8, hipMemcpyDeviceToHost, cx.stream));
-        LQ_TRY(hipMemcpyAsync(out.spectral_angle, d_sa.p, (size_t)n_grids * 8, hipMemcpyDeviceToHost, cx.stream));
-        if (F) LQ_TRY(hipMemcpyAsync(out.areas, d_areas.p, (size_t)n_grids * F * 8, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipMemcpyAsync(h_slot.data(), slot_of_grid.p, (size_t)n_grids * 4, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipMemcpyAsync(out.has_peak, d_has.p, n_grids, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipMemcpyAsync(out.peak_rt, d_peak.p, (size_t)n_grids * 4, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipMemcpyAsync(out.left, d_left.p, (size_t)n_grids * 4, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipMemcpyAsync(out.right, d_right.p, (size_t)n_grids * 4, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipMemcpyAsync(out.score, d_score.p, (size_t)n_grids * 8, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipMemcpyAsync(out.spectral_angle, d_sa.p, (size_t)n_grids * 8, hipMemcpyDeviceToHost, cx.stream));
+        if (F) HIP_TRY(hipMemcpyAsync(out.areas, d_areas.p, (size_t)n_grids * F * 8, hipMemcpyDeviceToHost, cx.stream));
         if (out.warps && F)
-            LQ_TRY(hipMemcpyAsync(out.warps, d_warps.p, (size_t)n_grids * F * 4, hipMemcpyDeviceToHost, cx.stream));
+            HIP_TRY(hipMemcpyAsync(out.warps, d_warps.p, (size_t)n_grids * F * 4, hipMemcpyDeviceToHost, cx.stream));
         if (out.matrix && rows_total)
-            LQ_TRY(hipMemcpyAsync(out.matrix, matrix.p, rows_total * GRID * 8, hipMemcpyDeviceToHost, cx.stream));
+            HIP_TRY(hipMemcpyAsync(out.matrix, matrix.p, rows_total * GRID * 8, hipMemcpyDeviceToHost, cx.stream));
     }
-    LQ_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     float ms = 0.0f;
-    LQ_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     out.build_ms = ms;
-    LQ_TRY(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[1], ev[2]));
     out.ms1_ms = ms;
-    LQ_TRY(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[2], ev[3]));
     out.trace_ms = ms;
-    LQ_TRY(hipEventElapsedTime(&ms, ev.e[3], ev.e[4]));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[3], ev[4]));
     out.integrate_ms = ms;
-    LQ_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[4]));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[4]));
     out.device_ms = ms;
 
     // -- keys, then picked_precursor (fdr.rs:228-287) over the grids with a peak
@@ -1012,18 +956,20 @@ bool lfq_impl(LfqCtx& cx, const SageLfqInput& in, const SageLfqMobility* mobilit
 }  // namespace
 
 int lfq_on_device(int device, const SageLfqInput& in, const SageLfqMobility* mobility, SageLfqOutput& out, std::string& err) {
-    LfqCtx cx;
+    Ctx cx;
+    cx.prefix = "sage_hip_lfq: ";
     if (hipSetDevice(device) != hipSuccess) {
         err = "sage_hip_lfq: hipSetDevice failed";
         return SAGE_HIP_ERR_NO_DEVICE;
     }
-    if (!cx.check(hipStreamCreateWithFlags(&cx.stream, hipStreamNonBlocking), "hipStreamCreate")) {
+    Stream stream;
+    if (!cx.check(stream.create(), "hipStreamCreate")) {
         err = cx.err;
         return cx.code;
     }
+    cx.stream = stream.s;
     const bool ok = lfq_impl(cx, in, mobility, out);
     (void)hipStreamSynchronize(cx.stream);
-    (void)hipStreamDestroy(cx.stream);
     if (!ok) {
         err = cx.err;
         return cx.code ? cx.code : SAGE_HIP_ERR_HIP;

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"
+#include "hip_host.h"
 
 using namespace sagecore;
 
@@ -27,6 +28,7 @@ namespace sagehip {
 namespace {
 
 constexpr uint32_t WAVE = 64;
+constexpr uint32_t PROCESS_LDS_PEAKS = 2048;  // raw peaks the LDS instance of the kernel takes (process_raw_on_device)
 
 struct ProcLds {
     float* mz;        // [rcap] raw m/z
@@ -267,6 +269,110 @@ void launch_compact(uint32_t n, const uint64_t* peak_off, uint32_t stride, const
                     float* intens, void* stream) {
     if (n == 0) return;
     hipLaunchKernelGGL(compact_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, n, peak_off, stride, sm, si, masses, intens);
+}
+
+// SpectrumProcessor::process (spectrum.rs:279-412) of every spectrum of `raw` on the device: process_kernel (the LDS instance up
+// to 2 048 raw peaks, the global-workspace instance beyond) and the compaction into ProcessedSpectrum arrays, enqueued on
+// `stream`.  Spectra that keep fewer than min_peaks peaks are left with zero.  counts: the peaks each spectrum kept before
+// that filter; off: the offsets of peak_off.  `w` holds the inputs and intermediates until the caller's stream is done with
+// them.  What sage_hip_batch_process_upload and sage_hip_tmt share.
+bool process_raw_on_device(Ctx& cx, const SageRawBatch* raw, uint64_t take_top_n, int deisotope, float min_deisotope_mz, uint32_t min_peaks,
+                           ProcessScratch& w, DevBuf<uint64_t>& peak_off, DevBuf<float>& masses, DevBuf<float>& intensities,
+                           DevBuf<float>& tic, std::vector<uint32_t>& counts, std::vector<uint64_t>& off) {
+    const hipStream_t stream = cx.stream;
+    const uint32_t n = raw->n_spectra;
+    if (take_top_n == 0 || take_top_n > 0xFFFFu) return cx.fail(SAGE_HIP_ERR_INVALID, "take_top_n must be in [1, 65535]");
+    const uint64_t total = n ? raw->peak_off[n] : 0;
+    uint32_t rcap = 1;
+    for (uint32_t i = 0; i < n; i++) {
+        if (raw->peak_off[i + 1] < raw->peak_off[i]) return cx.fail(SAGE_HIP_ERR_INVALID, "peak_off is not monotone");
+        rcap = std::max<uint32_t>(rcap, (uint32_t)(raw->peak_off[i + 1] - raw->peak_off[i]));
+    }
+    if (total && (!raw->mz || !raw->intensities)) return cx.fail(SAGE_HIP_ERR_INVALID, "missing peak arrays");
+    // the LDS instance of the kernel takes spectra up to PROCESS_LDS_PEAKS raw peaks (what three workgroups per CU can hold);
+    // larger ones go through the global-workspace instance, whatever their size
+    const uint32_t big_cap = rcap;
+    std::vector<uint32_t> big;
+    if (rcap > PROCESS_LDS_PEAKS) {
+        for (uint32_t i = 0; i < n; i++)
+            if (raw->peak_off[i + 1] - raw->peak_off[i] > PROCESS_LDS_PEAKS) big.push_back(i);
+        rcap = PROCESS_LDS_PEAKS;
+    }
+    uint32_t rpow2 = 1;
+    while (rpow2 < rcap) rpow2 <<= 1;
+    HIP_TRY((hipError_t)process_kernel_prepare(160 * 1024));
+    const uint32_t stride = (uint32_t)std::min<uint64_t>(take_top_n, big_cap);
+    HIP_TRY(w.raw_off.upload(raw->peak_off, n ? (size_t)n + 1 : 0));
+    HIP_TRY(w.raw_mz.upload(raw->mz, total));
+    HIP_TRY(w.raw_int.upload(raw->intensities, total));
+    HIP_TRY(w.zbuf.upload(raw->precursor_charge, n));
+    HIP_TRY(w.sm.alloc((size_t)n * stride));
+    HIP_TRY(w.si.alloc((size_t)n * stride));
+    HIP_TRY(w.cnt.alloc(n));
+    HIP_TRY(tic.alloc(n));
+    launch_process(n, w.raw_off.p, w.raw_mz.p, w.raw_int.p, w.zbuf.p, (uint32_t)take_top_n, deisotope != 0, min_deisotope_mz, rcap, rpow2,
+                   stride, w.sm.p, w.si.p, tic.p, w.cnt.p, stream);
+    HIP_TRY(hipGetLastError());
+    if (!big.empty()) {
+        // Groups of similar size, each with slices sized for ITS largest spectrum, launched one after the other over one
+        // workspace of bounded size (stream order makes the reuse safe): a batch with one 50 000-peak outlier among thousands of
+        // 3 000-peak spectra must not ask for (number of big spectra) x (the outlier's slice).
+        std::sort(big.begin(), big.end(), [&](uint32_t a, uint32_t b) {
+            const uint64_t na = raw->peak_off[a + 1] - raw->peak_off[a], nb = raw->peak_off[b + 1] - raw->peak_off[b];
+            return na != nb ? na < nb : a < b;
+        });
+        auto slice_of = [&](uint32_t spec, uint32_t* cap_out, uint32_t* pow2_out) {
+            const uint32_t cap = (uint32_t)(raw->peak_off[spec + 1] - raw->peak_off[spec]);
+            uint32_t p2 = 1;
+            while (p2 < cap) p2 <<= 1;
+            if (cap_out) *cap_out = cap;
+            if (pow2_out) *pow2_out = p2;
+            return process_lds_bytes(cap, p2);
+        };
+        const size_t budget = (size_t)1 << 30;  // bytes of workspace per launch (a single larger spectrum still gets its slice)
+        struct Group { size_t first, count; uint32_t cap, pow2; size_t slice; };
+        std::vector<Group> groups;
+        for (size_t i = 0; i < big.size();) {
+            // grow the group while (members) x (slice of the candidate member, the largest so far) fits the budget
+            size_t j = i;
+            uint32_t cap = 0, p2 = 0;
+            size_t slice = 0;
+            while (j < big.size()) {
+                uint32_t c, q;
+                const size_t sl = slice_of(big[j], &c, &q);
+                if (j > i && (j - i + 1) * sl > budget) break;
+                cap = c; p2 = q; slice = sl;
+                j++;
+            }
+            groups.push_back(Group{i, j - i, cap, p2, slice});
+            i = j;
+        }
+        size_t ws_bytes = 0;
+        for (const Group& g : groups) ws_bytes = std::max(ws_bytes, g.count * g.slice);
+        HIP_TRY(w.big_list.upload(big.data(), big.size()));
+        if (hipError_t e = w.big_ws.alloc(ws_bytes); e != hipSuccess) {
+            (void)hipGetLastError();
+            return cx.fail(status_of(e),
+                        "preprocessing workspace of " + std::to_string(ws_bytes >> 20) + " MiB for a spectrum of " + std::to_string(big_cap) +
+                            " raw peaks: " + hipGetErrorString(e) + " (sage_hip_process_ms2 preprocesses a spectrum on the host)");
+        }
+        for (const Group& g : groups) {
+            launch_process_big((uint32_t)g.count, w.big_list.p + g.first, w.big_ws.p, w.raw_off.p, w.raw_mz.p, w.raw_int.p, w.zbuf.p, (uint32_t)take_top_n,
+                               deisotope != 0, min_deisotope_mz, g.cap, g.pow2, stride, w.sm.p, w.si.p, tic.p, w.cnt.p, stream);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    counts.assign(n, 0);
+    HIP_TRY(hipMemcpyAsync(counts.data(), w.cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    off.assign((size_t)n + 1, 0);
+    for (uint32_t i = 0; i < n; i++) off[i + 1] = off[i] + (counts[i] >= min_peaks ? counts[i] : 0);  // runner.rs:313
+    HIP_TRY(peak_off.upload(off.data(), n ? (size_t)n + 1 : 0));
+    HIP_TRY(masses.alloc(off[n]));
+    HIP_TRY(intensities.alloc(off[n]));
+    launch_compact(n, peak_off.p, stride, w.sm.p, w.si.p, masses.p, intensities.p, stream);
+    HIP_TRY(hipGetLastError());
+    return true;
 }
 
 }  // namespace sagehip

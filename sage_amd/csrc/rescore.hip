@@ -34,8 +34,8 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/reverse_iterator.hpp>
 
-#include "../../include/sage_hip.h"
 #include "detmath.h"
+#include "hip_host.h"
 
 namespace sagehip {
 
@@ -591,33 +591,6 @@ struct Buf {
     }
 };
 
-struct EventPair {  // start / stop events of one call, destroyed on every exit path
-    hipEvent_t start = nullptr, stop = nullptr;
-    EventPair() = default;
-    EventPair(const EventPair&) = delete;
-    EventPair& operator=(const EventPair&) = delete;
-    ~EventPair() {
-        if (start) (void)hipEventDestroy(start);
-        if (stop) (void)hipEventDestroy(stop);
-    }
-};
-
-struct Ctx {
-    hipStream_t stream = nullptr;
-    std::string err;
-    int code = SAGE_HIP_OK;
-    bool check(hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        code = e == hipErrorOutOfMemory ? SAGE_HIP_ERR_OOM : SAGE_HIP_ERR_HIP;
-        err = std::string(what) + ": " + hipGetErrorString(e);
-        return false;
-    }
-};
-#define RS_TRY(expr)                         \
-    do {                                     \
-        if (!cx.check((expr), #expr)) return false; \
-    } while (0)
-
 uint32_t grid_for(uint64_t n, uint32_t block) { return (uint32_t)std::max<uint64_t>(1, (n + block - 1) / block); }
 uint32_t blocks_for(uint64_t n) { return (uint32_t)std::min<uint64_t>(MAX_BLOCKS, std::max<uint64_t>(1, (n + RB - 1) / RB)); }
 
@@ -641,11 +614,11 @@ bool blocked_sum(Ctx& cx, const double* d_x, uint64_t n, int mode, double mean, 
     if (n == 0) return true;
     const uint64_t nblk = (n + DB - 1) / DB;
     Buf<double> part;
-    RS_TRY(part.alloc(nblk));
+    HIP_TRY(part.alloc(nblk));
     blocked_sum_kernel<<<grid_for(nblk, 64), 64, 0, cx.stream>>>(d_x, n, mode, mean, part.p);
     std::vector<double> h(nblk);
-    RS_TRY(hipMemcpyAsync(h.data(), part.p, nblk * 8, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), part.p, nblk * 8, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     out = fold_partials(h);
     return true;
 }
@@ -656,20 +629,20 @@ bool kde_build(Ctx& cx, const double* d_scores, const uint8_t* d_decoy, uint64_t
     // the class vectors `d` and `t` (kde.rs:86-98), each in input order
     Buf<uint32_t> flags, dpos;
     Buf<double> xs, mm;
-    RS_TRY(flags.alloc(n));
-    RS_TRY(dpos.alloc(n));
-    RS_TRY(xs.alloc(n));
+    HIP_TRY(flags.alloc(n));
+    HIP_TRY(dpos.alloc(n));
+    HIP_TRY(xs.alloc(n));
     class_flags_kernel<<<grid_for(n, RB), RB, 0, cx.stream>>>(d_decoy, n, flags.p);
     if (!exclusive_count(cx, flags.p, dpos.p, n)) return false;
     uint32_t last_pos = 0, last_flag = 0;
-    RS_TRY(hipMemcpyAsync(&last_pos, dpos.p + (n - 1), 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(&last_flag, flags.p + (n - 1), 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(&last_pos, dpos.p + (n - 1), 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(&last_flag, flags.p + (n - 1), 4, hipMemcpyDeviceToHost, cx.stream));
     const uint32_t nb = blocks_for(n);
-    RS_TRY(mm.alloc((size_t)nb * 2));
+    HIP_TRY(mm.alloc((size_t)nb * 2));
     minmax_kernel<<<nb, RB, 0, cx.stream>>>(d_scores, n, mm.p);
     std::vector<double> hmm((size_t)nb * 2);
-    RS_TRY(hipMemcpyAsync(hmm.data(), mm.p, hmm.size() * 8, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipMemcpyAsync(hmm.data(), mm.p, hmm.size() * 8, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     const uint64_t cnt_u[2] = {(uint64_t)last_pos + last_flag, n - ((uint64_t)last_pos + last_flag)};
     class_split_kernel<<<grid_for(n, RB), RB, 0, cx.stream>>>(d_scores, d_decoy, dpos.p, n, cnt_u[0], xs.p);
     double mn = std::numeric_limits<double>::max(), mx = std::numeric_limits<double>::lowest();
@@ -694,16 +667,16 @@ bool kde_build(Ctx& cx, const double* d_scores, const uint8_t* d_decoy, uint64_t
     const double step = (mx - mn) / (double)(nbins - 1);
     const uint32_t nblk[2] = {(uint32_t)((cnt_u[0] + DB - 1) / DB), (uint32_t)((cnt_u[1] + DB - 1) / DB)};
     Buf<double> pdf_partial[2];
-    RS_TRY(fit.bins.alloc(nbins));
+    HIP_TRY(fit.bins.alloc(nbins));
     for (int c = 0; c < 2; ++c) {
-        RS_TRY(pdf_partial[c].alloc((size_t)nblk[c] * nbins));
+        HIP_TRY(pdf_partial[c].alloc((size_t)nblk[c] * nbins));
         if (nblk[c])
             kde_pdf_kernel<<<dim3(grid_for(nbins, KDE_THREADS), nblk[c]), KDE_THREADS, 0, cx.stream>>>(cls_x[c], cnt_u[c], mn, step,
                                                                                                    nbins, bw[c], pdf_partial[c].p);
     }
     kde_finish_kernel<<<1, 1024, 0, cx.stream>>>(pdf_partial[0].p, nblk[0], pdf_partial[1].p, nblk[1], nbins, constant[0],
                                                 constant[1], pi, monotonic ? 1 : 0, fit.bins.p);
-    RS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     fit.dev = KdeDev{fit.bins.p, mn, step, nbins};
     return true;
 }
@@ -788,35 +761,24 @@ bool gauss_solve(const Dense& left, const Dense& right, std::vector<double>& out
 
 // descending stable sort of `n` f32 scores given as total-order keys; order_out[j] = index of the j-th best
 bool sort_desc(Ctx& cx, uint32_t* d_keys_in, uint32_t* d_idx_in, uint32_t n, uint32_t* d_keys_out, uint32_t* d_idx_out) {
-    size_t temp_bytes = 0;
-    RS_TRY(rocprim::radix_sort_pairs_desc((void*)nullptr, temp_bytes, d_keys_in, d_keys_out, d_idx_in, d_idx_out, n, 0, 32,
-                                          cx.stream));
     Buf<uint8_t> temp;
-    RS_TRY(temp.alloc(temp_bytes));
-    RS_TRY(rocprim::radix_sort_pairs_desc((void*)temp.p, temp_bytes, d_keys_in, d_keys_out, d_idx_in, d_idx_out, n, 0, 32,
-                                          cx.stream));
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(with_scratch(temp, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs_desc(t, b, d_keys_in, d_keys_out, d_idx_in, d_idx_out, n, 0, 32, cx.stream); }));
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     return true;
 }
 
 // out[j] = sum of flags[0..j]
 bool prefix_count(Ctx& cx, const uint32_t* d_flags, uint32_t* d_out, uint32_t n) {
-    size_t temp_bytes = 0;
-    RS_TRY(rocprim::inclusive_scan((void*)nullptr, temp_bytes, d_flags, d_out, (size_t)n, rocprim::plus<uint32_t>(), cx.stream));
     Buf<uint8_t> temp;
-    RS_TRY(temp.alloc(temp_bytes));
-    RS_TRY(rocprim::inclusive_scan((void*)temp.p, temp_bytes, d_flags, d_out, (size_t)n, rocprim::plus<uint32_t>(), cx.stream));
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(with_scratch(temp, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, d_flags, d_out, (size_t)n, rocprim::plus<uint32_t>(), cx.stream); }));
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     return true;
 }
 
 // out[j] = sum of flags[0..j)
 bool exclusive_count(Ctx& cx, const uint32_t* d_flags, uint32_t* d_out, uint64_t n) {
-    size_t temp_bytes = 0;
-    RS_TRY(rocprim::exclusive_scan((void*)nullptr, temp_bytes, d_flags, d_out, 0u, (size_t)n, rocprim::plus<uint32_t>(), cx.stream));
     Buf<uint8_t> temp;
-    RS_TRY(temp.alloc(temp_bytes));
-    RS_TRY(rocprim::exclusive_scan((void*)temp.p, temp_bytes, d_flags, d_out, 0u, (size_t)n, rocprim::plus<uint32_t>(), cx.stream));
+    HIP_TRY(with_scratch(temp, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, d_flags, d_out, 0u, (size_t)n, rocprim::plus<uint32_t>(), cx.stream); }));
     return true;
 }
 
@@ -825,12 +787,9 @@ bool suffix_min(Ctx& cx, const float* d_q, float* d_out, uint32_t n) {
     if (n == 0) return true;
     auto in = rocprim::make_reverse_iterator(d_q + n);
     auto out = rocprim::make_reverse_iterator(d_out + n);
-    size_t temp_bytes = 0;
-    RS_TRY(rocprim::inclusive_scan((void*)nullptr, temp_bytes, in, out, (size_t)n, OpFmin(), cx.stream));
     Buf<uint8_t> temp;
-    RS_TRY(temp.alloc(temp_bytes));
-    RS_TRY(rocprim::inclusive_scan((void*)temp.p, temp_bytes, in, out, (size_t)n, OpFmin(), cx.stream));
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(with_scratch(temp, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, in, out, (size_t)n, OpFmin(), cx.stream); }));
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     return true;
 }
 
@@ -840,9 +799,9 @@ bool picked(Ctx& cx, const uint32_t* d_key, uint32_t n_keys, const uint8_t* d_de
     passing = 0;
     if (n_keys == 0) {  // no feature takes part: every q stays 1.0
         Buf<float> dummy;
-        RS_TRY(dummy.alloc(2));
+        HIP_TRY(dummy.alloc(2));
         picked_gather_kernel<<<grid_for(n, RB), RB, 0, cx.stream>>>(d_key, d_decoy, n, dummy.p, d_q_out);
-        RS_TRY(hipStreamSynchronize(cx.stream));
+        HIP_TRY(hipStreamSynchronize(cx.stream));
         return true;
     }
     const uint32_t n_rows = 2 * n_keys;
@@ -852,36 +811,34 @@ bool picked(Ctx& cx, const uint32_t* d_key, uint32_t n_keys, const uint8_t* d_de
     Buf<float> pep, dsum, q, qmin, side_q;
     Buf<uint32_t> target_flag, target_cum;
     Buf<unsigned long long> d_pass;
-    RS_TRY(side.alloc(n_rows));
-    RS_TRY(row_key.alloc(n_rows));
-    RS_TRY(row_id.alloc(n_rows));
-    RS_TRY(sorted_key.alloc(n_rows));
-    RS_TRY(sorted_id.alloc(n_rows));
-    RS_TRY(counters.alloc(2));
-    RS_TRY(winner.alloc(n_keys));
-    RS_TRY(winner_decoy.alloc(n_keys));
-    RS_TRY(row_decoy.alloc(n_rows));
-    RS_TRY(pep.alloc((size_t)n_rows + CS_TILE));
-    RS_TRY(dsum.alloc((size_t)n_rows + CS_TILE));
-    RS_TRY(q.alloc(n_rows));
-    RS_TRY(qmin.alloc(n_rows));
-    RS_TRY(target_flag.alloc(n_rows));
-    RS_TRY(target_cum.alloc(n_rows));
-    RS_TRY(side_q.alloc(n_rows));
-    RS_TRY(d_pass.alloc(1));
-    RS_TRY(hipMemsetAsync(side.p, 0, (size_t)n_rows * 4, cx.stream));
-    RS_TRY(hipMemsetAsync(counters.p, 0, 8, cx.stream));
+    HIP_TRY(side.alloc(n_rows));
+    HIP_TRY(row_key.alloc(n_rows));
+    HIP_TRY(row_id.alloc(n_rows));
+    HIP_TRY(sorted_key.alloc(n_rows));
+    HIP_TRY(sorted_id.alloc(n_rows));
+    HIP_TRY(counters.alloc(2));
+    HIP_TRY(winner.alloc(n_keys));
+    HIP_TRY(winner_decoy.alloc(n_keys));
+    HIP_TRY(row_decoy.alloc(n_rows));
+    HIP_TRY(pep.alloc((size_t)n_rows + CS_TILE));
+    HIP_TRY(dsum.alloc((size_t)n_rows + CS_TILE));
+    HIP_TRY(q.alloc(n_rows));
+    HIP_TRY(qmin.alloc(n_rows));
+    HIP_TRY(target_flag.alloc(n_rows));
+    HIP_TRY(target_cum.alloc(n_rows));
+    HIP_TRY(side_q.alloc(n_rows));
+    HIP_TRY(d_pass.alloc(1));
+    HIP_TRY(hipMemsetAsync(side.p, 0, (size_t)n_rows * 4, cx.stream));
+    HIP_TRY(hipMemsetAsync(counters.p, 0, 8, cx.stream));
     picked_max_kernel<<<grid_for(n, RB), RB, 0, cx.stream>>>(d_key, d_decoy, d_score, n, side.p);
     picked_rows_kernel<<<grid_for(n_keys, RB), RB, 0, cx.stream>>>(side.p, n_keys, winner.p, winner_decoy.p, row_key.p, row_id.p,
                                                                     counters.p);
     uint32_t h_counters[2];
-    RS_TRY(hipMemcpyAsync(h_counters, counters.p, 8, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipMemcpyAsync(h_counters, counters.p, 8, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     if (h_counters[1]) {
-        cx.code = SAGE_HIP_ERR_INVALID;
-        cx.err = "sage_hip_rescore: competition keys must be dense (" + std::to_string(h_counters[1]) + " of " +
-                 std::to_string(n_keys) + " ids are not used by any feature)";
-        return false;
+        return cx.fail(SAGE_HIP_ERR_INVALID, "sage_hip_rescore: competition keys must be dense (" + std::to_string(h_counters[1]) + " of " +
+                                                 std::to_string(n_keys) + " ids are not used by any feature)");
     }
     const uint32_t m = h_counters[0];
     KdeFit est;
@@ -894,17 +851,17 @@ bool picked(Ctx& cx, const uint32_t* d_key, uint32_t n_keys, const uint8_t* d_de
     seq_cumsum_kernel<<<1, 64, 0, cx.stream>>>(pep.p, m_padded, dsum.p);
     picked_q_kernel<<<grid_for(m, RB), RB, 0, cx.stream>>>(dsum.p, target_cum.p, m, q.p);
     if (!suffix_min(cx, q.p, qmin.p, m)) return false;
-    RS_TRY(hipMemsetAsync(d_pass.p, 0, 8, cx.stream));
+    HIP_TRY(hipMemsetAsync(d_pass.p, 0, 8, cx.stream));
     count_passing_kernel<<<grid_for(m, RB), RB, 0, cx.stream>>>(qmin.p, m, row_decoy.p, 0.01f, d_pass.p);
     // rows that do not exist keep q = 1.0 (never read: a feature's own side always exists)
     std::vector<float> ones(n_rows, 1.0f);
-    RS_TRY(hipMemcpyAsync(side_q.p, ones.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, cx.stream));
+    HIP_TRY(hipMemcpyAsync(side_q.p, ones.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, cx.stream));
     picked_scatter_kernel<<<grid_for(m, RB), RB, 0, cx.stream>>>(sorted_id.p, qmin.p, m, side_q.p);
     picked_gather_kernel<<<grid_for(n, RB), RB, 0, cx.stream>>>(d_key, d_decoy, n, side_q.p, d_q_out);
     unsigned long long h_pass = 0;
-    RS_TRY(hipMemcpyAsync(&h_pass, d_pass.p, 8, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipGetLastError());
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipMemcpyAsync(&h_pass, d_pass.p, 8, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     passing = h_pass;
     return true;
 }
@@ -918,39 +875,38 @@ bool rescore_impl(Ctx& cx, const SageRescoreInput& in, SageRescoreOutput& out) {
     Buf<float> a_rt, d_rt, d_ims, discriminant, posterior, spectrum_q, peptide_q, protein_q, qsorted, qmin_sorted;
     Buf<uint32_t> pkey, prkey, keys, idx, keys_sorted, order;
     Buf<unsigned long long> d_pass;
-    RS_TRY(feats.alloc(n));
-    RS_TRY(decoy.alloc(n));
-    RS_TRY(dmass.alloc(n));
-    RS_TRY(rows.alloc(n * NF));
-    RS_TRY(disc.alloc(n));
-    RS_TRY(discriminant.alloc(n));
-    RS_TRY(posterior.alloc(n));
-    RS_TRY(spectrum_q.alloc(n));
-    RS_TRY(peptide_q.alloc(n));
-    RS_TRY(protein_q.alloc(n));
-    RS_TRY(qsorted.alloc(n));
-    RS_TRY(qmin_sorted.alloc(n));
-    RS_TRY(pkey.alloc(n));
-    RS_TRY(prkey.alloc(n));
-    RS_TRY(keys.alloc(n));
-    RS_TRY(idx.alloc(n));
-    RS_TRY(keys_sorted.alloc(n));
-    RS_TRY(order.alloc(n));
-    RS_TRY(d_pass.alloc(1));
-    RS_TRY(hipMemcpyAsync(feats.p, in.features, n * sizeof(SageFeature), hipMemcpyHostToDevice, cx.stream));
-    RS_TRY(hipMemcpyAsync(pkey.p, in.peptide_key, n * 4, hipMemcpyHostToDevice, cx.stream));
-    RS_TRY(hipMemcpyAsync(prkey.p, in.protein_key, n * 4, hipMemcpyHostToDevice, cx.stream));
+    HIP_TRY(feats.alloc(n));
+    HIP_TRY(decoy.alloc(n));
+    HIP_TRY(dmass.alloc(n));
+    HIP_TRY(rows.alloc(n * NF));
+    HIP_TRY(disc.alloc(n));
+    HIP_TRY(discriminant.alloc(n));
+    HIP_TRY(posterior.alloc(n));
+    HIP_TRY(spectrum_q.alloc(n));
+    HIP_TRY(peptide_q.alloc(n));
+    HIP_TRY(protein_q.alloc(n));
+    HIP_TRY(qsorted.alloc(n));
+    HIP_TRY(qmin_sorted.alloc(n));
+    HIP_TRY(pkey.alloc(n));
+    HIP_TRY(prkey.alloc(n));
+    HIP_TRY(keys.alloc(n));
+    HIP_TRY(idx.alloc(n));
+    HIP_TRY(keys_sorted.alloc(n));
+    HIP_TRY(order.alloc(n));
+    HIP_TRY(d_pass.alloc(1));
+    HIP_TRY(hipMemcpyAsync(feats.p, in.features, n * sizeof(SageFeature), hipMemcpyHostToDevice, cx.stream));
+    HIP_TRY(hipMemcpyAsync(pkey.p, in.peptide_key, n * 4, hipMemcpyHostToDevice, cx.stream));
+    HIP_TRY(hipMemcpyAsync(prkey.p, in.protein_key, n * 4, hipMemcpyHostToDevice, cx.stream));
     const float* opt[3] = {in.aligned_rt, in.delta_rt_model, in.delta_ims_model};
     Buf<float>* optbuf[3] = {&a_rt, &d_rt, &d_ims};
     for (int k = 0; k < 3; ++k)
         if (opt[k]) {
-            RS_TRY(optbuf[k]->alloc(n));
-            RS_TRY(hipMemcpyAsync(optbuf[k]->p, opt[k], n * 4, hipMemcpyHostToDevice, cx.stream));
+            HIP_TRY(optbuf[k]->alloc(n));
+            HIP_TRY(hipMemcpyAsync(optbuf[k]->p, opt[k], n * 4, hipMemcpyHostToDevice, cx.stream));
         }
-    EventPair ev;
-    RS_TRY(hipEventCreate(&ev.start));
-    RS_TRY(hipEventCreate(&ev.stop));
-    RS_TRY(hipEventRecord(ev.start, cx.stream));
+    Events<2> ev;  // start, stop
+    HIP_TRY(ev.create());
+    HIP_TRY(hipEventRecord(ev[0], cx.stream));
     const uint32_t g = grid_for(n, RB);
     prep_kernel<<<g, RB, 0, cx.stream>>>(feats.p, n, tol_kind, decoy.p, dmass.p);
 
@@ -964,12 +920,12 @@ bool rescore_impl(Ctx& cx, const SageRescoreInput& in, SageRescoreOutput& out) {
     rows_kernel<<<g, RB, 0, cx.stream>>>(feats.p, n, dmass.p, mass_model.dev, a_rt.p, d_rt.p, d_ims.p, rows.p);
 
     // train (:57-127): class sums -> means -> scatter -> solve; both passes in the reference's row order (seq_lda_kernel)
-    RS_TRY(folded.alloc(2 * NF * NF + 2 * NF));
+    HIP_TRY(folded.alloc(2 * NF * NF + 2 * NF));
     seq_lda_kernel<false><<<dim3(1, 2), SEQ_THREADS, 0, cx.stream>>>(rows.p, decoy.p, n, nullptr, folded.p);
     double class_sum[2][NF];
-    RS_TRY(hipMemcpyAsync(class_sum, folded.p, sizeof(class_sum), hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(class_sum, folded.p, sizeof(class_sum), hipMemcpyDeviceToHost, cx.stream));
     // class counts: the decoy flags summed by the mass-model fit would do; recount on the host from the labels instead
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     uint64_t class_count[2] = {0, 0};
     for (uint64_t i = 0; i < n; ++i) class_count[in.features[i].label == -1 ? 0 : 1]++;
     bool fitted = class_count[0] != 0 && class_count[1] != 0;  // :83-85
@@ -979,11 +935,11 @@ bool rescore_impl(Ctx& cx, const SageRescoreInput& in, SageRescoreOutput& out) {
         for (int c = 0; c < 2; ++c)
             for (int j = 0; j < NF; ++j) class_mean[c][j] = class_sum[c][j] / (double)class_count[c];
         double* d_mean = folded.p + 2 * NF * NF;
-        RS_TRY(hipMemcpyAsync(d_mean, class_mean, sizeof(class_mean), hipMemcpyHostToDevice, cx.stream));
+        HIP_TRY(hipMemcpyAsync(d_mean, class_mean, sizeof(class_mean), hipMemcpyHostToDevice, cx.stream));
         seq_lda_kernel<true><<<dim3(1, 2), SEQ_THREADS, 0, cx.stream>>>(rows.p, decoy.p, n, d_mean, folded.p);
         std::vector<double> scatter(2 * NF * NF);
-        RS_TRY(hipMemcpyAsync(scatter.data(), folded.p, scatter.size() * 8, hipMemcpyDeviceToHost, cx.stream));
-        RS_TRY(hipStreamSynchronize(cx.stream));
+        HIP_TRY(hipMemcpyAsync(scatter.data(), folded.p, scatter.size() * 8, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipStreamSynchronize(cx.stream));
         Dense within(NF, NF), mu(NF, 1);
         for (int c = 0; c < 2; ++c)  // :105-108
             for (int e = 0; e < NF * NF; ++e) within.a[e] += scatter[c * NF * NF + e] / (double)class_count[c];
@@ -1013,29 +969,29 @@ bool rescore_impl(Ctx& cx, const SageRescoreInput& in, SageRescoreOutput& out) {
     if (!prefix_count(cx, keys.p, idx.p, (uint32_t)n)) return false;
     q_from_counts_kernel<<<g, RB, 0, cx.stream>>>(idx.p, (uint32_t)n, qsorted.p);
     if (!suffix_min(cx, qsorted.p, qmin_sorted.p, (uint32_t)n)) return false;
-    RS_TRY(hipMemsetAsync(d_pass.p, 0, 8, cx.stream));
+    HIP_TRY(hipMemsetAsync(d_pass.p, 0, 8, cx.stream));
     count_passing_kernel<<<g, RB, 0, cx.stream>>>(qmin_sorted.p, (uint32_t)n, nullptr, 0.01f, d_pass.p);
     scatter_by_order_kernel<<<g, RB, 0, cx.stream>>>(order.p, qmin_sorted.p, (uint32_t)n, spectrum_q.p);
     unsigned long long h_pass = 0;
-    RS_TRY(hipMemcpyAsync(&h_pass, d_pass.p, 8, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipGetLastError());
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipMemcpyAsync(&h_pass, d_pass.p, 8, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     out.passing_spectrum = h_pass;
 
     // ---- fdr.rs:123-187 ----
     if (!picked(cx, pkey.p, in.n_peptide_keys, decoy.p, discriminant.p, n, peptide_q.p, out.passing_peptide)) return false;
     if (!picked(cx, prkey.p, in.n_protein_keys, decoy.p, discriminant.p, n, protein_q.p, out.passing_protein)) return false;
-    RS_TRY(hipEventRecord(ev.stop, cx.stream));
+    HIP_TRY(hipEventRecord(ev[1], cx.stream));
 
-    RS_TRY(hipMemcpyAsync(out.discriminant_score, discriminant.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(out.posterior_error, posterior.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(out.spectrum_q, spectrum_q.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(out.peptide_q, peptide_q.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(out.protein_q, protein_q.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
-    if (out.order) RS_TRY(hipMemcpyAsync(out.order, order.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.discriminant_score, discriminant.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.posterior_error, posterior.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.spectrum_q, spectrum_q.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.peptide_q, peptide_q.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.protein_q, protein_q.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
+    if (out.order) HIP_TRY(hipMemcpyAsync(out.order, order.p, n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     float ms = 0.0f;
-    RS_TRY(hipEventElapsedTime(&ms, ev.start, ev.stop));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     out.device_ms = ms;
     return true;
 }
@@ -1342,14 +1298,14 @@ bool fit_and_predict(Ctx& cx, const SageFeature* d_f, const uint8_t* d_train, co
     r2 = 0.0;
     const uint32_t nb = (uint32_t)std::min<uint64_t>(256, std::max<uint64_t>(1, (n + 255) / 256));
     Buf<double> partial, folded;
-    RS_TRY(partial.alloc((size_t)nb * W));
-    RS_TRY(folded.alloc(W));
+    HIP_TRY(partial.alloc((size_t)nb * W));
+    HIP_TRY(folded.alloc(W));
     xtx_kernel<E><<<nb, XTX_THREADS, 0, cx.stream>>>(d_f, d_train, d_seq_off, d_seq, d_mono, d_aligned, n, partial.p);
     fold_partials_kernel<<<grid_for(W, RB), RB, 0, cx.stream>>>(partial.p, nb, W, folded.p);
     std::vector<double> h(W);
-    RS_TRY(hipMemcpyAsync(h.data(), folded.p, (size_t)W * 8, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipGetLastError());
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), folded.p, (size_t)W * 8, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     const double cnt = h[D * D + D + 2];
     if (cnt == 0.0) return true;  // regression.rs:86-88
     const double sum_y = h[D * D + D], sum_y2 = h[D * D + D + 1];
@@ -1363,15 +1319,15 @@ bool fit_and_predict(Ctx& cx, const SageFeature* d_f, const uint8_t* d_train, co
     for (int j = 0; j < D; ++j) bw.w[j] = beta[j];
     const uint32_t pb = grid_for(n, PRED_THREADS);
     Buf<double> sse_partial;
-    RS_TRY(sse_partial.alloc(pb));
+    HIP_TRY(sse_partial.alloc(pb));
     predict_kernel<E><<<pb, PRED_THREADS, 0, cx.stream>>>(d_f, d_train, d_seq_off, d_seq, d_mono, d_aligned, n, bw, 0, hi_clamp,
                                                            sse_partial.p, nullptr, nullptr);
     predict_kernel<E><<<pb, PRED_THREADS, 0, cx.stream>>>(d_f, d_train, d_seq_off, d_seq, d_mono, d_aligned, n, bw, 1, hi_clamp,
                                                            nullptr, d_pred, d_delta);
     std::vector<double> hs(pb);
-    RS_TRY(hipMemcpyAsync(hs.data(), sse_partial.p, (size_t)pb * 8, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipGetLastError());
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipMemcpyAsync(hs.data(), sse_partial.p, (size_t)pb * 8, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     double sse = 0.0;
     for (double v : hs) sse += v;
     r2 = 1.0 - sse / y_var;
@@ -1388,49 +1344,45 @@ bool predict_rt_impl(Ctx& cx, const SageRtInput& in, SageRtOutput& out) {
     Buf<float> mono, q_sorted, qmin_sorted, spectrum_q, aligned, pred_rt, d_rt, pred_ims, d_ims;
     Buf<uint32_t> idx, order, flags, cum, max_rt_u, counters;
     Buf<unsigned long long> dummy_pass;
-    RS_TRY(feats.alloc(n));
-    RS_TRY(seq_off.alloc((size_t)n + 1));
-    RS_TRY(seq.alloc(n_res));
-    RS_TRY(mono.alloc(n));
-    RS_TRY(keys.alloc(n));
-    RS_TRY(keys_sorted.alloc(n));
-    RS_TRY(idx.alloc(n));
-    RS_TRY(order.alloc(n));
-    RS_TRY(flags.alloc(n));
-    RS_TRY(cum.alloc(n));
-    RS_TRY(decoy.alloc(n));
-    RS_TRY(train.alloc(n));
-    RS_TRY(q_sorted.alloc(n));
-    RS_TRY(qmin_sorted.alloc(n));
-    RS_TRY(spectrum_q.alloc(n));
-    RS_TRY(aligned.alloc(n));
-    RS_TRY(pred_rt.alloc(n));
-    RS_TRY(d_rt.alloc(n));
-    RS_TRY(pred_ims.alloc(n));
-    RS_TRY(d_ims.alloc(n));
-    RS_TRY(max_rt_u.alloc(nf));
-    RS_TRY(counters.alloc(1));
-    RS_TRY(hipMemcpyAsync(feats.p, in.features, (size_t)n * sizeof(SageFeature), hipMemcpyHostToDevice, cx.stream));
-    RS_TRY(hipMemcpyAsync(seq_off.p, in.seq_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, cx.stream));
-    RS_TRY(hipMemcpyAsync(seq.p, in.seq, n_res, hipMemcpyHostToDevice, cx.stream));
-    RS_TRY(hipMemcpyAsync(mono.p, in.monoisotopic, (size_t)n * 4, hipMemcpyHostToDevice, cx.stream));
-    RS_TRY(hipMemsetAsync(max_rt_u.p, 0, (size_t)nf * 4, cx.stream));
-    RS_TRY(hipMemsetAsync(counters.p, 0, 4, cx.stream));
-    EventPair ev;
-    RS_TRY(hipEventCreate(&ev.start));
-    RS_TRY(hipEventCreate(&ev.stop));
-    RS_TRY(hipEventRecord(ev.start, cx.stream));
+    HIP_TRY(feats.alloc(n));
+    HIP_TRY(seq_off.alloc((size_t)n + 1));
+    HIP_TRY(seq.alloc(n_res));
+    HIP_TRY(mono.alloc(n));
+    HIP_TRY(keys.alloc(n));
+    HIP_TRY(keys_sorted.alloc(n));
+    HIP_TRY(idx.alloc(n));
+    HIP_TRY(order.alloc(n));
+    HIP_TRY(flags.alloc(n));
+    HIP_TRY(cum.alloc(n));
+    HIP_TRY(decoy.alloc(n));
+    HIP_TRY(train.alloc(n));
+    HIP_TRY(q_sorted.alloc(n));
+    HIP_TRY(qmin_sorted.alloc(n));
+    HIP_TRY(spectrum_q.alloc(n));
+    HIP_TRY(aligned.alloc(n));
+    HIP_TRY(pred_rt.alloc(n));
+    HIP_TRY(d_rt.alloc(n));
+    HIP_TRY(pred_ims.alloc(n));
+    HIP_TRY(d_ims.alloc(n));
+    HIP_TRY(max_rt_u.alloc(nf));
+    HIP_TRY(counters.alloc(1));
+    HIP_TRY(hipMemcpyAsync(feats.p, in.features, (size_t)n * sizeof(SageFeature), hipMemcpyHostToDevice, cx.stream));
+    HIP_TRY(hipMemcpyAsync(seq_off.p, in.seq_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, cx.stream));
+    HIP_TRY(hipMemcpyAsync(seq.p, in.seq, n_res, hipMemcpyHostToDevice, cx.stream));
+    HIP_TRY(hipMemcpyAsync(mono.p, in.monoisotopic, (size_t)n * 4, hipMemcpyHostToDevice, cx.stream));
+    HIP_TRY(hipMemsetAsync(max_rt_u.p, 0, (size_t)nf * 4, cx.stream));
+    HIP_TRY(hipMemsetAsync(counters.p, 0, 4, cx.stream));
+    Events<2> ev;  // start, stop
+    HIP_TRY(ev.create());
+    HIP_TRY(hipEventRecord(ev[0], cx.stream));
     const uint32_t g = grid_for(n, RB);
 
     // ---- runner.rs:517-520: sort by poisson (f64 total order, ascending), spectrum_q_value ----
     poisson_keys_kernel<<<g, RB, 0, cx.stream>>>(feats.p, n, keys.p, idx.p, decoy.p);
     {
-        size_t temp_bytes = 0;
-        RS_TRY(rocprim::radix_sort_pairs((void*)nullptr, temp_bytes, keys.p, keys_sorted.p, idx.p, order.p, n, 0, 64, cx.stream));
         Buf<uint8_t> temp;
-        RS_TRY(temp.alloc(temp_bytes));
-        RS_TRY(rocprim::radix_sort_pairs((void*)temp.p, temp_bytes, keys.p, keys_sorted.p, idx.p, order.p, n, 0, 64, cx.stream));
-        RS_TRY(hipStreamSynchronize(cx.stream));
+        HIP_TRY(with_scratch(temp, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, keys.p, keys_sorted.p, idx.p, order.p, n, 0, 64, cx.stream); }));
+        HIP_TRY(hipStreamSynchronize(cx.stream));
     }
     decoy_flags_kernel<<<g, RB, 0, cx.stream>>>(order.p, decoy.p, n, flags.p);
     if (!prefix_count(cx, flags.p, cum.p, n)) return false;
@@ -1442,34 +1394,29 @@ bool predict_rt_impl(Ctx& cx, const SageRtInput& in, SageRtOutput& out) {
     // ---- global_alignment (retention_alignment.rs:100-173) ----
     std::vector<uint32_t> h_max(nf);
     uint32_t h_bad = 0;
-    RS_TRY(hipMemcpyAsync(h_max.data(), max_rt_u.p, (size_t)nf * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(&h_bad, counters.p, 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipGetLastError());
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipMemcpyAsync(h_max.data(), max_rt_u.p, (size_t)nf * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(&h_bad, counters.p, 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     if (h_bad) {
-        cx.code = SAGE_HIP_ERR_INVALID;
-        cx.err = "sage_hip_predict_rt: a feature's file_id is >= n_files";
-        return false;
+        return cx.fail(SAGE_HIP_ERR_INVALID, "sage_hip_predict_rt: a feature's file_id is >= n_files");
     }
     std::vector<double> h_max_d(nf);
     for (uint32_t k = 0; k < nf; ++k) h_max_d[k] = (double)h_max[k];
     Buf<double> d_max;
-    RS_TRY(d_max.alloc(nf));
-    RS_TRY(hipMemcpyAsync(d_max.p, h_max_d.data(), (size_t)nf * 8, hipMemcpyHostToDevice, cx.stream));
+    HIP_TRY(d_max.alloc(nf));
+    HIP_TRY(hipMemcpyAsync(d_max.p, h_max_d.data(), (size_t)nf * 8, hipMemcpyHostToDevice, cx.stream));
     // group the training PSMs by (peptide, file): 64-bit radix sort, run heads take the minimum
     group_keys_kernel<<<g, RB, 0, cx.stream>>>(feats.p, train.p, n, keys.p, idx.p);
     {
-        size_t temp_bytes = 0;
-        RS_TRY(rocprim::radix_sort_pairs((void*)nullptr, temp_bytes, keys.p, keys_sorted.p, idx.p, order.p, n, 0, 64, cx.stream));
         Buf<uint8_t> temp;
-        RS_TRY(temp.alloc(temp_bytes));
-        RS_TRY(rocprim::radix_sort_pairs((void*)temp.p, temp_bytes, keys.p, keys_sorted.p, idx.p, order.p, n, 0, 64, cx.stream));
-        RS_TRY(hipStreamSynchronize(cx.stream));
+        HIP_TRY(with_scratch(temp, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, keys.p, keys_sorted.p, idx.p, order.p, n, 0, 64, cx.stream); }));
+        HIP_TRY(hipStreamSynchronize(cx.stream));
     }
     // number of training PSMs = position of the first sentinel key; count it with the flags of the q pass
     std::vector<uint8_t> h_train(n);
-    RS_TRY(hipMemcpyAsync(h_train.data(), train.p, n, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipMemcpyAsync(h_train.data(), train.p, n, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     uint32_t m = 0;
     for (uint32_t i = 0; i < n; ++i) m += h_train[i];
     uint32_t n_rows = 0;
@@ -1477,27 +1424,27 @@ bool predict_rt_impl(Ctx& cx, const SageRtInput& in, SageRtOutput& out) {
     if (m) {
         row_start_kernel<<<grid_for(m, RB), RB, 0, cx.stream>>>(keys_sorted.p, m, flags.p);
         if (!prefix_count(cx, flags.p, cum.p, m)) return false;
-        RS_TRY(hipMemcpyAsync(&n_rows, cum.p + (m - 1), 4, hipMemcpyDeviceToHost, cx.stream));
-        RS_TRY(hipStreamSynchronize(cx.stream));
+        HIP_TRY(hipMemcpyAsync(&n_rows, cum.p + (m - 1), 4, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipStreamSynchronize(cx.stream));
     }
-    RS_TRY(mat.alloc((size_t)std::max<uint32_t>(n_rows, 1) * nf));
-    RS_TRY(mean_rts.alloc(std::max<uint32_t>(n_rows, 1)));
+    HIP_TRY(mat.alloc((size_t)std::max<uint32_t>(n_rows, 1) * nf));
+    HIP_TRY(mean_rts.alloc(std::max<uint32_t>(n_rows, 1)));
     std::vector<SageAlignment> al(nf);
     {
         std::vector<double> len(nf, 0.0), dot(nf, 0.0), sum_x(nf, 0.0), sum_y(nf, 0.0), sx2(nf, 1e-8), x_mean(nf), y_mean(nf);
         if (n_rows) {
-            RS_TRY(hipMemsetAsync(mat.p, 0xFF, (size_t)n_rows * nf * 8, cx.stream));  // all-ones bit pattern: a NaN
+            HIP_TRY(hipMemsetAsync(mat.p, 0xFF, (size_t)n_rows * nf * 8, cx.stream));  // all-ones bit pattern: a NaN
             run_min_kernel<<<grid_for(m, RB), RB, 0, cx.stream>>>(feats.p, keys_sorted.p, order.p, cum.p, m, nf, d_max.p, mat.p);
             row_mean_kernel<<<grid_for(n_rows, RB), RB, 0, cx.stream>>>(mat.p, n_rows, nf, mean_rts.p);
             const uint32_t nb = (uint32_t)std::min<uint32_t>(64, grid_for(n_rows, RB));
             Buf<double> partial, d_xmean;
-            RS_TRY(partial.alloc((size_t)nb * nf * 4));
-            RS_TRY(d_xmean.alloc(nf));
+            HIP_TRY(partial.alloc((size_t)nb * nf * 4));
+            HIP_TRY(d_xmean.alloc(nf));
             std::vector<double> hp((size_t)nb * nf * 4);
             align_sums_kernel<<<dim3(nb, nf), RB, 0, cx.stream>>>(mat.p, mean_rts.p, n_rows, nf, 0, nullptr, partial.p);
-            RS_TRY(hipMemcpyAsync(hp.data(), partial.p, hp.size() * 8, hipMemcpyDeviceToHost, cx.stream));
-            RS_TRY(hipGetLastError());
-            RS_TRY(hipStreamSynchronize(cx.stream));
+            HIP_TRY(hipMemcpyAsync(hp.data(), partial.p, hp.size() * 8, hipMemcpyDeviceToHost, cx.stream));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(cx.stream));
             for (uint32_t b = 0; b < nb; ++b)
                 for (uint32_t k = 0; k < nf; ++k) {
                     const double* o = &hp[((size_t)b * nf + k) * 4];
@@ -1507,11 +1454,11 @@ bool predict_rt_impl(Ctx& cx, const SageRtInput& in, SageRtOutput& out) {
                     sum_y[k] += o[3];
                 }
             for (uint32_t k = 0; k < nf; ++k) x_mean[k] = sum_x[k] / len[k];
-            RS_TRY(hipMemcpyAsync(d_xmean.p, x_mean.data(), (size_t)nf * 8, hipMemcpyHostToDevice, cx.stream));
+            HIP_TRY(hipMemcpyAsync(d_xmean.p, x_mean.data(), (size_t)nf * 8, hipMemcpyHostToDevice, cx.stream));
             align_sums_kernel<<<dim3(nb, nf), RB, 0, cx.stream>>>(mat.p, mean_rts.p, n_rows, nf, 1, d_xmean.p, partial.p);
-            RS_TRY(hipMemcpyAsync(hp.data(), partial.p, hp.size() * 8, hipMemcpyDeviceToHost, cx.stream));
-            RS_TRY(hipGetLastError());
-            RS_TRY(hipStreamSynchronize(cx.stream));
+            HIP_TRY(hipMemcpyAsync(hp.data(), partial.p, hp.size() * 8, hipMemcpyDeviceToHost, cx.stream));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(cx.stream));
             for (uint32_t b = 0; b < nb; ++b)
                 for (uint32_t k = 0; k < nf; ++k) sx2[k] += hp[((size_t)b * nf + k) * 4];
         }
@@ -1525,8 +1472,8 @@ bool predict_rt_impl(Ctx& cx, const SageRtInput& in, SageRtOutput& out) {
         }
     }
     Buf<SageAlignment> d_al;
-    RS_TRY(d_al.alloc(nf));
-    RS_TRY(hipMemcpyAsync(d_al.p, al.data(), (size_t)nf * sizeof(SageAlignment), hipMemcpyHostToDevice, cx.stream));
+    HIP_TRY(d_al.alloc(nf));
+    HIP_TRY(hipMemcpyAsync(d_al.p, al.data(), (size_t)nf * sizeof(SageAlignment), hipMemcpyHostToDevice, cx.stream));
     aligned_rt_kernel<<<g, RB, 0, cx.stream>>>(feats.p, n, d_al.p, aligned.p);
 
     // ---- retention_model::predict, mobility_model::predict; Feature defaults where a model is not fitted ----
@@ -1543,18 +1490,18 @@ bool predict_rt_impl(Ctx& cx, const SageRtInput& in, SageRtOutput& out) {
         return false;
     out.rt_fitted = rt_ok;
     out.ims_fitted = ims_ok;
-    RS_TRY(hipEventRecord(ev.stop, cx.stream));
-    RS_TRY(hipMemcpyAsync(out.spectrum_q, spectrum_q.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(out.aligned_rt, aligned.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(out.predicted_rt, pred_rt.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(out.delta_rt_model, d_rt.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(out.predicted_ims, pred_ims.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipMemcpyAsync(out.delta_ims_model, d_ims.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
-    RS_TRY(hipGetLastError());
-    RS_TRY(hipStreamSynchronize(cx.stream));
+    HIP_TRY(hipEventRecord(ev[1], cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.spectrum_q, spectrum_q.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.aligned_rt, aligned.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.predicted_rt, pred_rt.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.delta_rt_model, d_rt.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.predicted_ims, pred_ims.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipMemcpyAsync(out.delta_ims_model, d_ims.p, (size_t)n * 4, hipMemcpyDeviceToHost, cx.stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(cx.stream));
     if (out.alignments) std::copy(al.begin(), al.end(), out.alignments);
     float ms = 0.0f;
-    RS_TRY(hipEventElapsedTime(&ms, ev.start, ev.stop));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     out.device_ms = ms;
     return true;
 }
@@ -1568,14 +1515,15 @@ int rescore_on_device(int device, const SageRescoreInput& in, SageRescoreOutput&
         err = "sage_hip_rescore: hipSetDevice failed";
         return SAGE_HIP_ERR_NO_DEVICE;
     }
-    if (!cx.check(hipStreamCreateWithFlags(&cx.stream, hipStreamNonBlocking), "hipStreamCreate")) {
+    Stream stream;
+    if (!cx.check(stream.create(), "hipStreamCreate")) {
         err = cx.err;
         return cx.code;
     }
+    cx.stream = stream.s;
     scratch_begin(device, cx.stream);
     const bool ok = rescore_impl(cx, in, out);
     (void)hipStreamSynchronize(cx.stream);
-    (void)hipStreamDestroy(cx.stream);
     if (!ok) {
         err = cx.err;
         return cx.code ? cx.code : SAGE_HIP_ERR_HIP;
@@ -1592,14 +1540,15 @@ int predict_rt_on_device(int device, const SageRtInput& in, SageRtOutput& out, s
         err = "sage_hip_predict_rt: hipSetDevice failed";
         return SAGE_HIP_ERR_NO_DEVICE;
     }
-    if (!cx.check(hipStreamCreateWithFlags(&cx.stream, hipStreamNonBlocking), "hipStreamCreate")) {
+    Stream stream;
+    if (!cx.check(stream.create(), "hipStreamCreate")) {
         err = cx.err;
         return cx.code;
     }
+    cx.stream = stream.s;
     scratch_begin(device, cx.stream);
     const bool ok = predict_rt_impl(cx, in, out);
     (void)hipStreamSynchronize(cx.stream);
-    (void)hipStreamDestroy(cx.stream);
     if (!ok) {
         err = cx.err;
         return cx.code ? cx.code : SAGE_HIP_ERR_HIP;

@@ -1,6 +1,6 @@
 // tmt.hip — isobaric reporter-ion extraction on the device: find_reporter_ions (sage tmt.rs:193-214), i.e.
 // select_most_intense_peak(masses, intensities, label, tolerance, Some(-PROTON)) (spectrum.rs:134-159) for every label of every
-// spectrum.  sage_hip_tmt (capi.hip) feeds it either the resident ProcessedSpectrum arrays of process_kernel (MS level 2) or
+// spectrum.  tmt_on_device (below) feeds it either the resident ProcessedSpectrum arrays of process_kernel (MS level 2) or
 // the raw peaks as read (other levels: mass = mz - PROTON, computed here).
 //
 // Order-free selection.  Over peaks sorted stably by mass (total_cmp), the reference's scan keeps the LAST peak
@@ -20,6 +20,7 @@
 
 #include "core.h"
 #include "device_types.h"
+#include "hip_host.h"
 
 namespace sagehip {
 
@@ -83,8 +84,8 @@ __global__ __launch_bounds__(64 * TMT_WAVES) void tmt_extract_kernel(uint32_t n,
     }
 }
 
-}  // namespace
-
+// reporter-ion extraction, one wavefront per spectrum (peaks [off[i], off[i+1]); subtract_proton: the array holds raw m/z); lo / hi:
+// each label's window with the offset applied; region: [min lo, max hi].  out_*: [n * n_labels]
 void launch_tmt_extract(uint32_t n, const uint64_t* off, const float* mass_or_mz, const float* inten, bool subtract_proton,
                         const float* lo, const float* hi, uint32_t n_labels, float region_lo, float region_hi, float* out_int,
                         int32_t* out_idx, void* stream) {
@@ -92,6 +93,104 @@ void launch_tmt_extract(uint32_t n, const uint64_t* off, const float* mass_or_mz
     const uint32_t blocks = (n + TMT_WAVES - 1) / TMT_WAVES;
     hipLaunchKernelGGL(tmt_extract_kernel, dim3(blocks), dim3(64 * TMT_WAVES), 0, (hipStream_t)stream, n, off, mass_or_mz, inten,
                        subtract_proton ? 1 : 0, lo, hi, n_labels, region_lo, region_hi, out_int, out_idx);
+}
+
+// sage tmt.rs:314-352 quantify, minus the host-side row fields
+bool tmt_impl(Ctx& cx, int device, const SageTmtInput& in, SageTmtOutput& out) {
+    if ((in.n_batches && !in.batches) || (in.n_labels && !in.labels)) return cx.fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null array");
+    if (in.tolerance.kind < 0 || in.tolerance.kind > 2) return cx.fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: unknown tolerance kind");
+    const bool ms2 = in.level == 2;
+    const uint32_t L = in.n_labels;
+    uint64_t n_total = 0;
+    for (uint32_t b = 0; b < in.n_batches; ++b) {
+        const SageRawBatch& r = in.batches[b];
+        if (!r.n_spectra) continue;
+        if (!r.peak_off || (ms2 && !r.precursor_charge)) return cx.fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null spectrum array");
+        for (uint32_t i = 0; i < r.n_spectra; ++i) {
+            if (r.peak_off[i + 1] < r.peak_off[i]) return cx.fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: peak_off is not monotone");
+            if (r.peak_off[i + 1] - r.peak_off[i] > (uint64_t)INT32_MAX)
+                return cx.fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_tmt: a spectrum of more than 2^31 - 1 peaks (peak_index is i32)");
+        }
+        if (r.peak_off[r.n_spectra] && (!r.mz || !r.intensities)) return cx.fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: missing peak arrays");
+        n_total += r.n_spectra;
+    }
+    if (n_total && L && !out.intensity) return cx.fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null output array");
+    out.upload_ms = out.process_ms = out.extract_ms = out.device_ms = 0.0f;
+    if (!n_total || !L) return true;
+    // each label's window in f32 on the host: Tolerance::bounds, then + offset (-PROTON); the region is their union's hull
+    const sagecore::Tol tol{in.tolerance.kind, in.tolerance.lo, in.tolerance.hi};
+    std::vector<float> lo(L), hi(L);
+    float region_lo = INFINITY, region_hi = -INFINITY;
+    for (uint32_t k = 0; k < L; ++k) {
+        sagecore::offset_bounds(tol, in.labels[k], -sagecore::PROTON, lo[k], hi[k]);
+        if (lo[k] < region_lo) region_lo = lo[k];
+        if (hi[k] > region_hi) region_hi = hi[k];
+    }
+    HIP_TRY(hipSetDevice(device));
+    Stream stream;  // (destroyed after the events)
+    Events<4> ev;
+    HIP_TRY(stream.create());
+    HIP_TRY(ev.create());
+    cx.stream = stream.s;
+    DevBuf<float> dlo, dhi, dint;
+    DevBuf<int32_t> didx;
+    HIP_TRY(dlo.upload(lo.data(), L));
+    HIP_TRY(dhi.upload(hi.data(), L));
+    uint64_t row = 0;
+    for (uint32_t b = 0; b < in.n_batches; ++b) {
+        const SageRawBatch& r = in.batches[b];
+        const uint32_t n = r.n_spectra;
+        if (!n) continue;
+        const uint64_t total = r.peak_off[n], cells = (uint64_t)n * L;
+        HIP_TRY(dint.reserve(cells));
+        if (out.peak_index) HIP_TRY(didx.reserve(cells));
+        HIP_TRY(hipEventRecord(ev[0], cx.stream));
+        ProcessScratch w;
+        DevBuf<uint64_t> poff;
+        DevBuf<float> pm, pi, tic;
+        if (ms2) {  // the search's own preprocessing (min_peaks 0: every spectrum is quantified, runner.rs:334-359)
+            std::vector<uint32_t> counts;
+            std::vector<uint64_t> off;
+            if (!process_raw_on_device(cx, &r, in.take_top_n, in.deisotope, in.min_deisotope_mz, 0, w, poff, pm, pi, tic, counts, off))
+                return false;
+        } else {    // mass = mz - PROTON in the kernel; the raw peaks as given
+            HIP_TRY(poff.alloc((size_t)n + 1));
+            HIP_TRY(pm.alloc(total));
+            HIP_TRY(pi.alloc(total));
+            HIP_TRY(hipMemcpyAsync(poff.p, r.peak_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, cx.stream));
+            if (total) {
+                HIP_TRY(hipMemcpyAsync(pm.p, r.mz, total * 4, hipMemcpyHostToDevice, cx.stream));
+                HIP_TRY(hipMemcpyAsync(pi.p, r.intensities, total * 4, hipMemcpyHostToDevice, cx.stream));
+            }
+        }
+        HIP_TRY(hipEventRecord(ev[1], cx.stream));
+        launch_tmt_extract(n, poff.p, pm.p, pi.p, !ms2, dlo.p, dhi.p, L, region_lo, region_hi, dint.p, out.peak_index ? didx.p : nullptr,
+                           cx.stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[2], cx.stream));
+        HIP_TRY(hipMemcpyAsync(out.intensity + row * L, dint.p, cells * 4, hipMemcpyDeviceToHost, cx.stream));
+        if (out.peak_index) HIP_TRY(hipMemcpyAsync(out.peak_index + row * L, didx.p, cells * 4, hipMemcpyDeviceToHost, cx.stream));
+        HIP_TRY(hipEventRecord(ev[3], cx.stream));
+        HIP_TRY(hipStreamSynchronize(cx.stream));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        (ms2 ? out.process_ms : out.upload_ms) += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[1], ev[2]));
+        out.extract_ms += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[3]));
+        out.device_ms += ms;
+        row += n;
+    }
+    return true;
+}
+
+}  // namespace
+
+int tmt_on_device(int device, const SageTmtInput& in, SageTmtOutput& out, std::string& err) {
+    Ctx cx;
+    if (tmt_impl(cx, device, in, out)) return SAGE_HIP_OK;
+    err = cx.err;
+    return cx.code;
 }
 
 }  // namespace sagehip

@@ -9,14 +9,14 @@ values keep a random relative order, which the non-deisotoping heap makes visibl
   - equal m/z with different intensities;
 and, per spectrum, optionally a few coarse intensity levels (ties in the intensity sort and in the heap) and zero intensities.
 The peak counts sit on the kernel's edges: a wavefront (64), the bitonic sorts' power-of-two padding, the LDS / global-workspace
-split at PROCESS_LDS_PEAKS = 2 048 raw peaks (capi.hip), and a few spectra of 10 000 peaks or more."""
+split at PROCESS_LDS_PEAKS = 2 048 raw peaks (process.hip), and a few spectra of 10 000 peaks or more."""
 import numpy as np
 
 NEUTRON = np.float32(1.00335)
 # raw peak counts at the edges of process_kernel
 EDGE_COUNTS = (0, 1, 2, 63, 64, 65, 127, 128, 129, 2047, 2048, 2049, 4096, 4097)
 HUGE_COUNTS = (10000, 12289, 16385)
-LDS_PEAKS = 2048  # capi.hip: PROCESS_LDS_PEAKS
+LDS_PEAKS = 2048  # process.hip: PROCESS_LDS_PEAKS
 
 
 def peak_count(rng, huge=0.03):

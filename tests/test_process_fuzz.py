@@ -154,7 +154,7 @@ def test_device_processing_refuses_take_top_n_out_of_range(proc_world):
 
 @pytest.mark.gpu
 def test_device_processing_over_several_workspace_launches(proc_world):
-    """Global-workspace spectra whose slices exceed the 1 GiB workspace budget of one launch (capi.hip: the groups of
+    """Global-workspace spectra whose slices exceed the 1 GiB workspace budget of one launch (process.hip: the groups of
     launch_process_big): 50 spectra of ~1 M raw peaks (~51 M in all) between ordinary ones, sizes shuffled — each output at
     its own index, bit for bit.  (The heap path: deisotoping a million peaks is a serial walk of lane 0.)"""
     host, dev, _ = proc_world
