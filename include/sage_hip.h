@@ -326,6 +326,10 @@ void sage_hip_host_free(void* p);
  * first 4096 work items, out32[8*k + phase]: k = 0 narrow preliminary kernel, 1 rescoring kernel, 2 large-window count
  * kernel, 3 large-window replay kernel. */
 int sage_hip_debug_phase_cycles(SageScorer* scorer, unsigned long long* out32);
+/* Debug aid, same condition: what the rescoring kernels' prune dropped since the scorer was created. out4[0] candidates that could
+ * not reach min_matched_peaks any more, [1] their (ion, fragment charge) items, [2] scoring rounds that ended before the
+ * hyperscore because no candidate reached it, [3] rounds in which a passing candidate stood beside pruned ones. */
+int sage_hip_debug_prune_counters(SageScorer* scorer, unsigned long long* out4);
 
 /* ---- post-search rescoring --------------------------------------------------------------
  * The step that consumes the Feature records of ALL searched files (sage-cli runner.rs:536-541):

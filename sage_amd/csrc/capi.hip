@@ -844,6 +844,7 @@ static int scorer_init(SageScorer* sp, SageDeviceDb* db, const SageScorerParams*
     d.wcap = 1024;
     d.dbg_flags = 0;
     if (const char* e = getenv("SAGE_HIP_DEBUG_FLAGS")) d.dbg_flags = (uint32_t)atoi(e);
+    d.prune_min = (d.dbg_flags & 4096u) ? 0u : d.min_matched_peaks;  // (4096: tests and A/B runs switch the rescoring prune off)
     d.rescore_general = 0;
     if (const char* e = getenv("SAGE_HIP_RESCORE_GENERAL")) d.rescore_general = atoi(e) != 0 ? 1u : 0u;
     d.exact = 0;
@@ -951,8 +952,8 @@ static int scorer_init(SageScorer* sp, SageDeviceDb* db, const SageScorerParams*
     s->qmax = queries_per_spectrum(d);
     if (const char* e = getenv("SAGE_HIP_PHASE_CLOCKS")) {
         if (atoi(e) > 0) {
-            HIP_TRY(s->dbg.alloc(4096 * 32));
-            HIP_TRY(hipMemset(s->dbg.p, 0, 4096 * 32 * 8));
+            HIP_TRY(s->dbg.alloc(DBG_TOTAL_WORDS));  // (the phase block + the prune counters behind it: device_types.h)
+            HIP_TRY(hipMemset(s->dbg.p, 0, DBG_TOTAL_WORDS * 8));
         }
     }
     return SAGE_HIP_OK;
@@ -2325,6 +2326,19 @@ int sage_hip_debug_phase_cycles(SageScorer* s, unsigned long long* out32) {
     for (int k = 0; k < 32; k++) out32[k] = 0;
     for (size_t b = 0; b < 4096; b++)
         for (int k = 0; k < 32; k++) out32[k] += all[b * 32 + k];
+    return SAGE_HIP_OK;
+}
+
+// debugging aid: what the rescoring prune dropped so far — candidates, their (ion, charge) items, scoring rounds that left early,
+// rounds with a passing candidate beside pruned ones (kernels.hip: DBG_PRUNE_*)
+int sage_hip_debug_prune_counters(SageScorer* s, unsigned long long* out4) {
+    if (!s || !out4) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+    if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
+    std::vector<unsigned long long> all((size_t)DBG_BLOCKS * DBG_PRUNE_WORDS);
+    HIP_TRY(hipMemcpy(all.data(), s->dbg.p + (size_t)DBG_BLOCKS * 32, all.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < DBG_PRUNE_WORDS; k++) out4[k] = 0;
+    for (size_t b = 0; b < DBG_BLOCKS; b++)
+        for (uint32_t k = 0; k < DBG_PRUNE_WORDS; k++) out4[k] += all[b * DBG_PRUNE_WORDS + k];
     return SAGE_HIP_OK;
 }
 

@@ -77,6 +77,11 @@ __host__ __device__ inline size_t tm_lut_index(uint32_t t, uint32_t c, uint32_t 
            : TM_LUT_LAYOUT == 1 ? (size_t)c * n_tiles + t : (size_t)t * lut_stride + c;
 }
 
+// SAGE_HIP_PHASE_CLOCKS=1: DevWork::dbg holds DBG_BLOCKS rows of 32 words (phase cycles and byte counts, kernels.hip: PhaseClock)
+// and behind them DBG_BLOCKS rows of DBG_PRUNE_WORDS words: what the rescoring prune dropped (sage_hip_debug_prune_counters)
+constexpr uint32_t DBG_BLOCKS = 4096, DBG_PRUNE_WORDS = 4;
+constexpr size_t DBG_TOTAL_WORDS = (size_t)DBG_BLOCKS * (32 + DBG_PRUNE_WORDS);
+
 struct DevScorer {
     sagecore::Tol precursor_tol, fragment_tol;
     sagecore::PbmReach pbm_reach;  // pbm_reach_of(fragment_tol): the peak-presence bitmap's reach coefficients (core.h)
@@ -100,6 +105,8 @@ struct DevScorer {
     uint32_t wcap;       // candidate-slot capacity of the LDS counter array of the narrow kernel: spectra with a
                          // larger precursor window go to the tiled large-window kernel
     uint32_t dbg_flags;  // timing experiments only (SAGE_HIP_DEBUG_FLAGS)
+    uint32_t prune_min;  // min_matched_peaks for the rescoring kernels' prune (kernels.hip: score_candidates drops a candidate that cannot
+                         //    reach it any more, rescore_spectrum leaves when no candidate reached it); 0: both off (SAGE_HIP_DEBUG_FLAGS=4096)
     uint32_t rescore_general;  // 1: launch_rescore takes the general instance of rescore_kernel (CHIMERA == true) for every search
                                //    (SAGE_HIP_RESCORE_GENERAL=1, read at scorer creation: tests and A/B runs of the two routes); host only
     uint32_t xcd_chunk;  // consecutive schedule positions one XCD takes at a time (kernels.hip: xcd_position); 0: round-robin

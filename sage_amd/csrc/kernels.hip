@@ -46,10 +46,14 @@ constexpr uint32_t PROBE_TABLE_WORDS = 4 * PROBE_BATCH_WORDS + PROBE_TCS_WORDS;
 // optional per-phase cycle accounting (DevWork::dbg != null): every work item of a launch adds its clock deltas to slot
 // [item mod DBG_BLOCKS][kernel*8 + phase] (debug builds of the numbers only; atomics, so slightly perturbing);
 // kernel 0 = narrow preliminary, 1 = rescoring, 2 = large-window count, 3 = large-window replay
-constexpr uint32_t DBG_BLOCKS = 4096;
+// (DBG_BLOCKS: device_types.h)
 // Slots 26..31 of a row count the BYTES the kernels ask memory for (profiling runs only; bench.py reports them next to the
 // reference algorithm's bytes): 26 narrow kernel table words, 27 narrow kernel index cells, 28 rescoring ion masses + peaks,
 // 29 large-window table words, 30 large-window index cells, 31 candidate words written to the arena.
+// The rows behind the phase block (device_types.h: DBG_PRUNE_WORDS per work item mod DBG_BLOCKS) count what the rescoring prune
+// dropped (profiling runs only): candidates whose masks score_candidates cleared, their (ion, charge) items, scoring
+// rounds that left rescore_spectrum early, rounds in which a candidate that passes min_matched_peaks stood beside pruned ones.
+enum { DBG_PRUNE_CAND = 0, DBG_PRUNE_ITEMS = 1, DBG_PRUNE_EARLY = 2, DBG_PRUNE_MIXED = 3 };
 enum { DBG_NARROW_LUT = 26, DBG_NARROW_CELLS = 27, DBG_RESCORE = 28, DBG_TILE_LUT = 29, DBG_TILE_CELLS = 30, DBG_TILE_CAND = 31 };
 struct PhaseClock {
     unsigned long long* slot;
@@ -58,9 +62,29 @@ struct PhaseClock {
         if (slot) atomicAdd(&slot[which - row_base], n);
     }
     int row_base;
+    unsigned long long* prune;  // this work item's row of prune counters
+    uint32_t pruned_here;       // candidates the prune dropped in this scoring round (score_candidates -> rescore_spectrum)
+    __device__ __forceinline__ void pruned(uint64_t lanes, uint32_t items) {  // wave-uniform arguments
+        if (slot && lanes) {
+            pruned_here += (uint32_t)__popcll(lanes);
+            if ((threadIdx.x & 63u) == 0) {
+                atomicAdd(&prune[DBG_PRUNE_CAND], (unsigned long long)__popcll(lanes));
+                atomicAdd(&prune[DBG_PRUNE_ITEMS], (unsigned long long)items);
+            }
+        }
+    }
+    __device__ __forceinline__ void prune_outcome(bool left_early, bool any_pass) {  // once per scoring round
+        if (slot && (threadIdx.x & 63u) == 0) {
+            if (left_early) atomicAdd(&prune[DBG_PRUNE_EARLY], 1ull);
+            else if (any_pass && pruned_here) atomicAdd(&prune[DBG_PRUNE_MIXED], 1ull);
+        }
+        pruned_here = 0;
+    }
     __device__ __forceinline__ void start(unsigned long long* dbg, uint32_t blk, uint32_t kernel) {
         slot = dbg ? dbg + (size_t)(blk % DBG_BLOCKS) * 32 + kernel * 8 : nullptr;
         row_base = (int)kernel * 8;
+        prune = dbg ? dbg + (size_t)DBG_BLOCKS * 32 + (size_t)(blk % DBG_BLOCKS) * DBG_PRUNE_WORDS : nullptr;
+        pruned_here = 0;
         if (slot) t = clock64();
     }
     __device__ __forceinline__ void mark(int phase) {
@@ -81,6 +105,8 @@ struct PhaseClock {
 struct NoClock {
     static constexpr unsigned long long* slot = nullptr;
     __device__ __forceinline__ void bytes(int, unsigned long long) {}
+    __device__ __forceinline__ void pruned(uint64_t, uint32_t) {}
+    __device__ __forceinline__ void prune_outcome(bool, bool) {}
     __device__ __forceinline__ void start(unsigned long long*, uint32_t, uint32_t) {}
     __device__ __forceinline__ void mark(int) {}
     __device__ __forceinline__ void rebase(uint32_t) {}
@@ -3153,8 +3179,21 @@ __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevS
             if (nfz > 3) m1 = m2 = m3 = in_chunk;  // (charges above 3 are not filtered: every ion goes through)
         }
         pc.mark(6);  // (phase clocks: the bitmap filter)
-        // ---- chunks with many hits: the whole wavefront on one candidate at a time
-        const uint32_t hc = act && nfz <= 3 ? (uint32_t)(__popcll(m1) + __popcll(m2) + __popcll(m3)) : 0u;
+        // ---- PRUNE: a candidate on its LAST chunk whose matches so far plus every item the bitmap lets through stay below
+        //      min_matched_peaks fails scoring.rs:491 whatever its lookups find — the bitmap never drops a match, an item adds at
+        //      most 1 — and a candidate that fails contributes nothing to any result.  Its masks are cleared: the
+        //      cooperative path, the dense list and the walk below skip it by themselves.  Its Score stays partial; nothing reads
+        //      the Score of a candidate that does not pass.  (Fragment charges above 3 are not filtered and make more than three
+        //      items per ion: such a candidate is never pruned.  prune_min == 0: off.)
+        uint32_t hc = act && nfz <= 3 ? (uint32_t)(__popcll(m1) + __popcll(m2) + __popcll(m3)) : 0u;
+        {
+            const bool drop = hc != 0u && j0 + 64u >= nions && (mm & 0xFFFFu) + (mm >> 16) + hc < sc.prune_min;
+            if (pc.slot) pc.pruned(__ballot(drop), wave_sum(drop ? hc : 0u));
+            if (drop) {
+                m1 = m2 = m3 = 0ull;
+                hc = 0u;
+            }
+        }
         uint64_t bigs = (sc.dbg_flags & 32u) ? 0ull : __ballot(hc > COOP_MIN_HITS);  // (SAGE_HIP_DEBUG_FLAGS=32: tests switch it off)
         if ((uint32_t)__popcll(bigs) > COOP_MAX_LANES && !(sc.dbg_flags & 64u)) bigs = 0ull;  // (64: tests take every heavy lane)
         while (bigs) {
@@ -3439,6 +3478,7 @@ struct LateArgs {  // K = void
     __device__ __forceinline__ uint32_t report_psms() const { return sc.report_psms; }
     __device__ __forceinline__ uint32_t chimera() const { return sc.chimera; }
     __device__ __forceinline__ uint32_t min_matched_peaks() const { return sc.min_matched_peaks; }
+    __device__ __forceinline__ uint32_t prune_min() const { return sc.prune_min; }
     __device__ __forceinline__ int score_type() const { return sc.score_type; }
     __device__ __forceinline__ uint32_t xcd_chunk() const { return sc.xcd_chunk; }
     __device__ __forceinline__ uint32_t batch_n() const { return b.n; }
@@ -3469,6 +3509,7 @@ struct LateArgs<RescoreKernargs> {
     __device__ __forceinline__ uint32_t report_psms() const { return ka->sc.report_psms; }
     __device__ __forceinline__ uint32_t chimera() const { return ka->sc.chimera; }
     __device__ __forceinline__ uint32_t min_matched_peaks() const { return ka->sc.min_matched_peaks; }
+    __device__ __forceinline__ uint32_t prune_min() const { return ka->sc.prune_min; }
     __device__ __forceinline__ int score_type() const { return ka->sc.score_type; }
     __device__ __forceinline__ uint32_t xcd_chunk() const { return ka->sc.xcd_chunk; }
     __device__ __forceinline__ uint32_t batch_n() const { return ka->b.n; }
@@ -3585,6 +3626,19 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
         // ---- from here on: the arguments through `la`, the spectrum's scalars from R.hdr (see LateArgs) ----
         LateArgs<KA> la(db, sc, b, w, lnfact_table, lnfact_n, out, out_count);
         la.refresh();
+        // ---- nobody reached min_matched_peaks (scoring.rs:491): what the code below does with npass == 0 — no record, the round
+        //      loop ends, the count written behind it — without the logarithm, the ranking and the record path.  (A spectrum
+        //      whose logarithm the fast phase could not round used to go through the retry pass for the same empty result.)
+        {
+            const uint32_t prune_min = la.prune_min();  // (== min_matched_peaks, or 0: SAGE_HIP_DEBUG_FLAGS=4096)
+            const uint64_t can_pass = __ballot(valid && s.matched_b + s.matched_y >= prune_min);
+            const bool leave = prune_min != 0u && can_pass == 0ull;
+            pc.prune_outcome(leave, can_pass != 0ull);
+            if (leave) {
+                if (ACC && keep) return true;  // (quick_score: nothing kept)
+                break;
+            }
+        }
         const double lambda = (double)R.hdr[HDR_MATCHED] / (double)R.hdr[HDR_SCORED];  // scoring.rs:499
         double h = 0.0;
         bool pass = false;
