@@ -330,6 +330,10 @@ int sage_hip_debug_phase_cycles(SageScorer* scorer, unsigned long long* out32);
  * not reach min_matched_peaks any more, [1] their (ion, fragment charge) items, [2] scoring rounds that ended before the
  * hyperscore because no candidate reached it, [3] rounds in which a passing candidate stood beside pruned ones. */
 int sage_hip_debug_prune_counters(SageScorer* scorer, unsigned long long* out4);
+/* Debug aid, same condition: the trips of the rescoring kernels' peak-bitmap filter since the scorer was created. out4[0] 64-ion
+ * chunks that took the flat route (ions dealt to all lanes), [1] their trips of 8 ions, [2] the trips of 4 ions the per-lane
+ * filter would have made of those chunks, [3] the trips of 4 ions of the chunks that took the per-lane route. */
+int sage_hip_debug_filter_counters(SageScorer* scorer, unsigned long long* out4);
 
 /* ---- post-search rescoring --------------------------------------------------------------
  * The step that consumes the Feature records of ALL searched files (sage-cli runner.rs:536-541):

@@ -2336,9 +2336,22 @@ int sage_hip_debug_prune_counters(SageScorer* s, unsigned long long* out4) {
     if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
     std::vector<unsigned long long> all((size_t)DBG_BLOCKS * DBG_PRUNE_WORDS);
     HIP_TRY(hipMemcpy(all.data(), s->dbg.p + (size_t)DBG_BLOCKS * 32, all.size() * 8, hipMemcpyDeviceToHost));
-    for (uint32_t k = 0; k < DBG_PRUNE_WORDS; k++) out4[k] = 0;
+    for (uint32_t k = 0; k < 4; k++) out4[k] = 0;
     for (size_t b = 0; b < DBG_BLOCKS; b++)
-        for (uint32_t k = 0; k < DBG_PRUNE_WORDS; k++) out4[k] += all[b * DBG_PRUNE_WORDS + k];
+        for (uint32_t k = 0; k < 4; k++) out4[k] += all[b * DBG_PRUNE_WORDS + k];
+    return SAGE_HIP_OK;
+}
+// debugging aid: the trips of the bitmap filter in front of the prune (kernels.hip: DBG_FILTER_*) — 64-ion chunks that took the
+// flat route, their trips of 8 ions, the trips of 4 ions the per-lane filter would have made of those chunks, and the trips of 4
+// ions of the chunks that took the per-lane route
+int sage_hip_debug_filter_counters(SageScorer* s, unsigned long long* out4) {
+    if (!s || !out4) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+    if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
+    std::vector<unsigned long long> all((size_t)DBG_BLOCKS * DBG_PRUNE_WORDS);
+    HIP_TRY(hipMemcpy(all.data(), s->dbg.p + (size_t)DBG_BLOCKS * 32, all.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < 4; k++) out4[k] = 0;
+    for (size_t b = 0; b < DBG_BLOCKS; b++)
+        for (uint32_t k = 0; k < 4; k++) out4[k] += all[b * DBG_PRUNE_WORDS + 4 + k];
     return SAGE_HIP_OK;
 }
 

@@ -661,4 +661,49 @@ SAGE_HD void pbm_peak_span(float m, float D, uint32_t& b0, uint32_t& b1) {
     b1 = f1 > 0.0f ? (uint32_t)f1 : 0u;
 }
 
+// ---- the flat form of the bitmap filter (kernels.hip: score_candidates) ---------------------------------------
+// The per-lane filter walks a candidate's ions of a 64-ion chunk in its own lane; the wavefront waits for the longest candidate
+// and the lanes without a candidate idle.  The flat form cuts every filtered candidate's ions of the chunk into OCTETS of
+// consecutive ions — lane i owns flat_octets(n_here) of them, items start .. start + n - 1 of one list (start: the exclusive
+// prefix sum over the lanes) — and item t is worked by lane t % 64 in trip t / 64.  Bookkeeping, all of it in ONE byte per item and
+// charge of an area in LDS: the owner writes its lane number into bytes start .. start + n - 1 of the first charge's stripe; the
+// worker of item t reads its owner there, gets the owner's ion table through the crossbar (with the owner's start folded into the
+// offset: 8 flat_item_k(t, start) == 8 t - 8 start), tests ions 8 k .. 8 k + 7 of the chunk (k = flat_item_k) and overwrites
+// byte t of every charge's stripe with the eight bits; the owner
+// reads bytes start .. start + 7 of a stripe back as bits 0 .. 63 of that charge's mask (flat_mask_word: three aligned words, the
+// owner's start is not aligned) and cuts it to its ions as the per-lane filter does.  Nobody but the worker of item t touches
+// byte t between the owners' writes and their reads, so there is no synchronisation inside the trips.
+SAGE_HD uint32_t flat_octets(uint32_t n_here) { return (n_here + 7u) >> 3; }
+SAGE_HD uint32_t flat_item_k(uint32_t t, uint32_t owner_start) { return t - owner_start; }
+// The item's first ion in the ion table, the way the kernel finds it without a second trip through the crossbar for the owner's
+// start: the owner hands out flat_item_base(where its ions of this chunk begin, its start) and the worker of item t adds 8 t —
+// flat_item_ion(flat_item_base(at, start), t) == at + 8 flat_item_k(t, start).  Unsigned, modulo 2^64: the base of an owner with
+// a small table offset and a large start lies "below zero", so the sum is formed as an integer and the table indexed once.
+SAGE_HD uint64_t flat_item_base(uint64_t chunk_at, uint32_t owner_start) { return chunk_at - 8ull * owner_start; }
+SAGE_HD uint64_t flat_item_ion(uint64_t item_base, uint32_t t) { return item_base + 8ull * t; }
+// bytes between the stripes of two charges for a list of `total` items (the stripes start word-aligned)
+SAGE_HD uint32_t flat_stride(uint32_t total) { return (total + 3u) & ~3u; }
+// bytes of the area a list needs: the read-back of the last owner (start <= total - 1) reaches (start & ~3) + 11
+SAGE_HD uint32_t flat_area_bytes(uint32_t total, uint32_t ncharges) { return flat_stride(total) * ncharges + 12u; }
+// The wave-uniform choice of the route: ceil(total / 64) flat trips of 8 ions against `longest` (the most octets any lane owns,
+// what the per-lane filter's trip count follows) — the flat route also pays the owners' writes, the crossbar and the read-back,
+// FLAT_MARGIN trips' worth.
+#ifndef SAGE_FLAT_MARGIN
+#define SAGE_FLAT_MARGIN 1
+#endif
+constexpr uint32_t FLAT_MARGIN = SAGE_FLAT_MARGIN;
+SAGE_HD uint32_t flat_route_bar(uint32_t total) { return (total + 63u) / 64u + FLAT_MARGIN; }  // a lane that owns more: the route wins
+// (the choice, stated on the largest count; the kernel takes it without the maximum — one ballot of `count > flat_route_bar(total)`
+// over the lanes, which is true exactly when the largest count is above the bar)
+SAGE_HD bool flat_route_wins(uint32_t total, uint32_t longest) { return total != 0u && longest > flat_route_bar(total); }
+// 32 bits of an owner's mask from two neighbouring aligned words of its stripe: bytes (start & 3) .. (start & 3) + 3 of {hi, lo}
+SAGE_HD uint32_t flat_mask_word(uint32_t lo, uint32_t hi, uint32_t start) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbyte(hi, lo, start & 3u);
+#else
+    const uint32_t sh = (start & 3u) * 8u;
+    return sh ? (lo >> sh) | (hi << (32u - sh)) : lo;
+#endif
+}
+
 }  // namespace sagecore

@@ -54,6 +54,10 @@ constexpr uint32_t PROBE_TABLE_WORDS = 4 * PROBE_BATCH_WORDS + PROBE_TCS_WORDS;
 // dropped (profiling runs only): candidates whose masks score_candidates cleared, their (ion, charge) items, scoring
 // rounds that left rescore_spectrum early, rounds in which a candidate that passes min_matched_peaks stood beside pruned ones.
 enum { DBG_PRUNE_CAND = 0, DBG_PRUNE_ITEMS = 1, DBG_PRUNE_EARLY = 2, DBG_PRUNE_MIXED = 3 };
+// ... and, behind them in the same rows, the bitmap filter's trips (sage_hip_debug_filter_counters): 64-ion chunks that took the flat
+// route, their trips of 8 ions, the trips of 4 ions the per-lane filter would have made of them, and the trips of 4 ions of the
+// chunks that took the per-lane route
+enum { DBG_FILTER_FLAT_CHUNKS = 4, DBG_FILTER_FLAT_TRIPS = 5, DBG_FILTER_FLAT_WOULD = 6, DBG_FILTER_LANE_TRIPS = 7 };
 enum { DBG_NARROW_LUT = 26, DBG_NARROW_CELLS = 27, DBG_RESCORE = 28, DBG_TILE_LUT = 29, DBG_TILE_CELLS = 30, DBG_TILE_CAND = 31 };
 struct PhaseClock {
     unsigned long long* slot;
@@ -70,6 +74,17 @@ struct PhaseClock {
             if ((threadIdx.x & 63u) == 0) {
                 atomicAdd(&prune[DBG_PRUNE_CAND], (unsigned long long)__popcll(lanes));
                 atomicAdd(&prune[DBG_PRUNE_ITEMS], (unsigned long long)items);
+            }
+        }
+    }
+    __device__ __forceinline__ void filter_trips(bool flat, uint32_t flat_trips, uint32_t lane_trips) {  // wave-uniform, once per chunk
+        if (slot && (threadIdx.x & 63u) == 0) {
+            if (flat) {
+                atomicAdd(&prune[DBG_FILTER_FLAT_CHUNKS], 1ull);
+                atomicAdd(&prune[DBG_FILTER_FLAT_TRIPS], (unsigned long long)flat_trips);
+                atomicAdd(&prune[DBG_FILTER_FLAT_WOULD], (unsigned long long)lane_trips);
+            } else {
+                atomicAdd(&prune[DBG_FILTER_LANE_TRIPS], (unsigned long long)lane_trips);
             }
         }
     }
@@ -107,6 +122,7 @@ struct NoClock {
     __device__ __forceinline__ void bytes(int, unsigned long long) {}
     __device__ __forceinline__ void pruned(uint64_t, uint32_t) {}
     __device__ __forceinline__ void prune_outcome(bool, bool) {}
+    __device__ __forceinline__ void filter_trips(bool, uint32_t, uint32_t) {}
     __device__ __forceinline__ void start(unsigned long long*, uint32_t, uint32_t) {}
     __device__ __forceinline__ void mark(int) {}
     __device__ __forceinline__ void rebase(uint32_t) {}
@@ -3059,6 +3075,9 @@ struct RescoreLds {
     float* pi;            // [pcap] peak intensities
     uint8_t* rm;          // [pcap] chimera: peak selected by the winner
     uint8_t* rm2;         // [pcap]
+                          // (rm .. stage: also the flat bitmap filter's item bytes, rescore_flat_bytes(pcap) of them — rm and rm2, which
+                          //  remove_matched_peaks writes when the filter is done and clears before it reads, and FLAT_EXTRA_BYTES
+                          //  behind them; score_candidates finds the area from pm and pi)
     uint32_t* stage;      // [stage_records * 30] Feature records on their way out (written by their lanes, stored by the wavefront)
 };
 constexpr uint32_t FEATURE_WORDS = sizeof(SageFeature) / 4;
@@ -3074,10 +3093,18 @@ __host__ __device__ inline size_t rescore_scratch_bytes(bool quick) {
 constexpr uint32_t RESCORE_HDR_WORDS = 8;
 enum RescoreHdr { HDR_TIC = 0, HDR_MZP = 1, HDR_RT = 2, HDR_IMS = 3, HDR_FILE = 4, HDR_MATCHED = 5, HDR_SCORED = 6 };
 constexpr size_t RESCORE_HEAD_BYTES = RESCORE_HDR_WORDS * 4 + 64 * sizeof(uint2);  // hdr + meta, in front of the peaks
+// LDS the flat filter gets beyond rm / rm2: with C3's 150 peaks the default rescore_kernel stands at 5120 + 2560 = 7680 bytes, six
+// allocation units of 1280 — what it occupied before (7296 bytes) — and five wavefronts per SIMD
+constexpr uint32_t FLAT_EXTRA_BYTES = 384;
+__host__ __device__ inline uint32_t rescore_flat_bytes(uint32_t pcap) { return ((pcap * 2u + 7u) & ~7u) + FLAT_EXTRA_BYTES; }
 __host__ __device__ inline size_t rescore_fixed_bytes(const DevScorer& sc, const DevBatchView& b) {
-    const size_t n = RESCORE_HEAD_BYTES + (size_t)b.pcap * 8 + (((size_t)b.pcap * 2 + 7) & ~(size_t)7) + (size_t)stage_records(sc) * sizeof(SageFeature);
+    const size_t n = RESCORE_HEAD_BYTES + (size_t)b.pcap * 8 + rescore_flat_bytes(b.pcap) + (size_t)stage_records(sc) * sizeof(SageFeature);
     return (n + 15) & ~(size_t)15;
 }
+// Where rm / the flat filter's area begins, from the two peak arrays alone: pi == pm + pcap and the area starts behind pi's pcap
+// floats.  carve_rescore lays rm out with it and score_candidates finds the area with it — every caller hands score_candidates the
+// pm and pi of a carve_rescore —, so the layout is stated once.
+__device__ __forceinline__ uint8_t* rescore_flat_area(const float* pm, const float* pi) { return (uint8_t*)(pi + (pi - pm)); }
 __device__ __forceinline__ RescoreLds carve_rescore(unsigned char* scratch, unsigned char* fixed, const DevBatchView& b) {
     RescoreLds l;
     l.pbm = (uint32_t*)scratch;
@@ -3091,9 +3118,11 @@ __device__ __forceinline__ RescoreLds carve_rescore(unsigned char* scratch, unsi
     l.meta = (uint2*)(fixed + RESCORE_HDR_WORDS * 4);
     l.pm = (float*)(fixed + RESCORE_HEAD_BYTES);
     l.pi = l.pm + b.pcap;
-    l.rm = (uint8_t*)(l.pi + b.pcap);
+    l.rm = rescore_flat_area(l.pm, l.pi);  // (== pi + pcap: one function says where the area lies, for this carve and for the filter)
     l.rm2 = l.rm + b.pcap;
-    l.stage = (uint32_t*)(fixed + RESCORE_HEAD_BYTES + (size_t)b.pcap * 8 + (((size_t)b.pcap * 2 + 7) & ~(size_t)7));
+    // (rm is 8-byte aligned — `fixed` is 16-byte aligned in every kernel, the head and the peaks are multiples of 8 —, which the
+    // flat filter's word reads of its area rely on)
+    l.stage = (uint32_t*)(fixed + RESCORE_HEAD_BYTES + (size_t)b.pcap * 8 + rescore_flat_bytes(b.pcap));
     return l;
 }
 
@@ -3128,7 +3157,11 @@ __device__ __forceinline__ uint64_t lane_run(uint64_t v, uint32_t src_lane) { re
 #endif
 constexpr uint32_t DENSE_CAP = 384;  // items of the dense work list: 2 x 4 + 2 bytes each and a flag bit, inside the bitmap's 4 KB
 static_assert(DENSE_CAP % 64 == 0 && DENSE_CAP * 10 + DENSE_CAP / 8 <= PBM_WORDS * 4, "the dense work list fits the bitmap");
-template <class PC, bool LONG = false, bool FAST = false>
+#ifndef SAGE_FLAT_GENERAL
+#define SAGE_FLAT_GENERAL 0  // 1: the general (CHIMERA) instances of rescore_spectrum take the flat route of the filter too — measured, no gain,
+                             //    and 14 more scalar spills in rescore_kernel's; 0: they keep to the per-lane filter
+#endif
+template <class PC, bool LONG = false, bool FAST = false, bool FLAT = !LONG>
 __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevScorer& sc, const uint32_t* pbm, const uint32_t* plut,
                                                  const float* pm, const float* pi, const uint32_t P, const float inv_w,
                                                  const bool valid, const uint64_t ion_base, const uint32_t lm1, const uint32_t nfz,
@@ -3136,7 +3169,18 @@ __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevS
                                                  Score& s, PC& pc, const bool have_first = false, const float first0 = 0.f,
                                                  const float first1 = 0.f, const float first2 = 0.f, const float first3 = 0.f,
                                                  const bool dense_ok = false) {
-    // (have_first: the candidate's first four ions were requested by the caller, ahead of its LDS table builds)
+    // (have_first: the candidate's first four ions were requested by the caller, ahead of its LDS table builds.  A first chunk that
+    // takes the flat route does not use them: its workers load other candidates' ions, and the request is already under way.)
+    // The flat filter's area — RescoreLds::rm .. stage — is worked out from the two peak arrays where it is used
+    // (rescore_flat_area) instead of being carried here in registers.  CALLERS: with FLAT, pm and pi must be the pm / pi of a
+    // carve_rescore — pi == pm + pcap and rescore_flat_bytes(pcap) bytes behind pi's pcap floats that nothing else uses while
+    // the filter runs; a caller that carves its peaks otherwise instantiates FLAT == false.  (FLAT == false: an instance that keeps to the per-lane
+    // filter — LONG, rescore_big_kernel's second instance, where the flat route's registers cost a wavefront per SIMD, and the
+    // general instances of rescore_spectrum, which spill as it is: SAGE_FLAT_GENERAL.
+    // SAGE_HIP_DEBUG_FLAGS=8192: the per-lane filter for every chunk; 16384: tests take the flat route for every chunk whose bytes
+    // fit, whether it wins or not.)
+    static_assert(!(FLAT && LONG), "the flat route's worker offsets and tags are those of the one-register instances");
+    const bool flat_ok = FLAT && !(sc.dbg_flags & 8192u);
     const uint32_t lane = lane_id();
     typedef typename std::conditional<LONG, uint64_t, uint32_t>::type RunReg;
     constexpr bool DENSE = !LONG;  // (the tags of the dense work list hold ion indices below 2^15)
@@ -3149,7 +3193,88 @@ __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevS
         const bool act = j0 < nions;
         const uint32_t n_here = !act ? 0u : nions - j0 < 64u ? nions - j0 : 64u;
         uint64_t m1 = 0, m2 = 0, m3 = 0;
-        if (act) {
+        // ---- the FLAT route of the filter (core.h: flat_octets ...): the filtered candidates' ions of this chunk, cut into octets,
+        //      dealt to all 64 lanes — item t to lane t % 64 in trip t / 64 — instead of one lane per candidate behind the longest
+        //      one.  Taken (wave-uniform) when its bytes fit the area and its trips undercut the longest candidate's
+        //      (flat_route_wins); the masks are the per-lane filter's bit for bit.  Lanes that are not filtered (nfz > 3) or not
+        //      active own no items.
+        bool flat = false;
+        uint32_t flat_trips = 0;  // (the profiling instance's counters)
+        if (flat_ok) {
+            uint8_t* const flat_area = rescore_flat_area(pm, pi);
+            const uint32_t flat_cap = rescore_flat_bytes((uint32_t)(pi - pm));
+            const uint32_t cnt = act && nfz <= 3u ? flat_octets(n_here) : 0u;
+            const uint32_t incl = wave_incl_scan_dpp(cnt), start = incl - cnt;
+            const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            const uint32_t stride = flat_stride(T);
+            // (flat_route_wins(T, the lanes' largest count), without the maximum: some lane owns more octets than the bar)
+            if (T != 0u && flat_area_bytes(T, 1u + (any_fz2 ? 1u : 0u) + (any_fz3 ? 1u : 0u)) <= flat_cap &&
+                (__ballot(cnt > flat_route_bar(T)) != 0ull || (sc.dbg_flags & 16384u))) {
+                flat = true;
+                uint8_t* const a1 = flat_area;
+                uint8_t* const a2 = a1 + stride;
+                uint8_t* const a3 = a2 + (any_fz2 ? stride : 0u);
+                for (uint32_t k = 0; __ballot(k < cnt) != 0ull; k++)
+                    if (k < cnt) a1[start + k] = (uint8_t)lane;
+                lds_sync();
+                // (ions j0 + 8 (t - start) .. of the owner's table: the owner folds its start into the offset it hands out)
+                const uint64_t ion_at = flat_item_base(ion_base + j0, start);
+                for (uint32_t base = 0; base < T; base += WAVE) {
+                    const uint32_t t = base + lane;
+                    const bool on = t < T;
+                    // (the item's owner and its ion table: through the crossbar — every lane takes part)
+                    const uint32_t src = (on ? (uint32_t)a1[t] : 0u) << 2;
+                    const uint64_t ib = ((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute((int)src, (int)(uint32_t)(ion_at >> 32)) << 32) |
+                                        (uint32_t)__builtin_amdgcn_ds_bpermute((int)src, (int)(uint32_t)ion_at);
+                    if (on) {
+                        // (the ion table is padded by 8: an octet may reach past the candidate's last ion, the owner masks those bits)
+                        const float* __restrict__ q = db.ions + flat_item_ion(ib, t);  // (the owner's ion j0 + 8 flat_item_k(t, its start))
+                        const float i0 = q[0], i1 = q[1], i2 = q[2], i3 = q[3], i4 = q[4], i5 = q[5], i6 = q[6], i7 = q[7];
+                        const uint32_t x0 = pbm_index(i0), x1 = pbm_index(i1), x2 = pbm_index(i2), x3 = pbm_index(i3);
+                        const uint32_t x4 = pbm_index(i4), x5 = pbm_index(i5), x6 = pbm_index(i6), x7 = pbm_index(i7);
+#define SAGE_FLAT_BYTE(F)                                                                                             \
+    (uint8_t)(pbm_bit(F(x0)) | (pbm_bit(F(x1)) << 1) | (pbm_bit(F(x2)) << 2) | (pbm_bit(F(x3)) << 3) | (pbm_bit(F(x4)) << 4) | \
+              (pbm_bit(F(x5)) << 5) | (pbm_bit(F(x6)) << 6) | (pbm_bit(F(x7)) << 7))
+#define SAGE_FLAT_C1(X) (X)
+#define SAGE_FLAT_C2(X) ((X) >> 1)
+#define SAGE_FLAT_C3(X) (__umulhi((X), 0xAAAAAAABu) >> 1)
+                        a1[t] = SAGE_FLAT_BYTE(SAGE_FLAT_C1);
+                        if (any_fz2) a2[t] = SAGE_FLAT_BYTE(SAGE_FLAT_C2);
+                        if (any_fz3) a3[t] = SAGE_FLAT_BYTE(SAGE_FLAT_C3);
+#undef SAGE_FLAT_C3
+#undef SAGE_FLAT_C2
+#undef SAGE_FLAT_C1
+#undef SAGE_FLAT_BYTE
+                    }
+                }
+                lds_sync();
+                if (cnt != 0u) {  // bytes start .. start + 7 of a stripe: bits 0 .. 63 of that charge's mask (cut to the chunk below)
+                    const uint32_t at = start & ~3u;
+                    {
+                        const uint32_t* const wp = (const uint32_t*)(a1 + at);
+                        const uint32_t w0 = wp[0], w1 = wp[1], w2 = wp[2];
+                        m1 = (uint64_t)flat_mask_word(w0, w1, start) | ((uint64_t)flat_mask_word(w1, w2, start) << 32);
+                    }
+                    if (any_fz2 && nfz >= 2u) {
+                        const uint32_t* const wp = (const uint32_t*)(a2 + at);
+                        const uint32_t w0 = wp[0], w1 = wp[1], w2 = wp[2];
+                        m2 = (uint64_t)flat_mask_word(w0, w1, start) | ((uint64_t)flat_mask_word(w1, w2, start) << 32);
+                    }
+                    if (any_fz3 && nfz >= 3u) {
+                        const uint32_t* const wp = (const uint32_t*)(a3 + at);
+                        const uint32_t w0 = wp[0], w1 = wp[1], w2 = wp[2];
+                        m3 = (uint64_t)flat_mask_word(w0, w1, start) | ((uint64_t)flat_mask_word(w1, w2, start) << 32);
+                    }
+                }
+            }
+            flat_trips = (T + 63u) / 64u;
+        }
+        if (pc.slot) {  // (profiling instance: this chunk's trips, and the per-lane filter's for the same chunk)
+            uint32_t would = act ? (n_here + 3u) >> 2 : 0u;
+            for (int o = 32; o; o >>= 1) { const uint32_t v = (uint32_t)__shfl_xor((int)would, o, 64); would = v > would ? v : would; }
+            pc.filter_trips(flat, flat_trips, would);
+        }
+        if (act && !flat) {  // ---- the PER-LANE route: every candidate's lane walks its own ions, four per trip
             // (the ion table is padded by 8: reading past the candidate's last ion is harmless, those bits are masked below)
             const float* __restrict__ q = my + j0;
             float n0, n1, n2, n3;
@@ -3172,6 +3297,8 @@ __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevS
                     m3 |= (uint64_t)t3 << r;
                 }
             }
+        }
+        if (act) {
             const uint64_t in_chunk = n_here >= 64u ? ~0ull : (1ull << n_here) - 1ull;
             m1 &= in_chunk;
             m2 = nfz >= 2 ? m2 & in_chunk : 0ull;
@@ -3620,7 +3747,7 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
         s.ppm_difference = 0.0f;
         s.longest_b = s.longest_y = 0;
         pc.mark(5);  // (... the peak table and the bitmap)
-        score_candidates<PC, false, FAST>(db, sc, pbm, plut, pm, pi, P, inv_w, valid, ion_base, lm1, nfz, any_fz2, any_fz3, nterm_mask, sym_tol,
+        score_candidates<PC, false, FAST, SAGE_FLAT_GENERAL || !CHIMERA>(db, sc, pbm, plut, pm, pi, P, inv_w, valid, ion_base, lm1, nfz, any_fz2, any_fz3, nterm_mask, sym_tol,
                                           s, pc, SAGE_ION_PREFETCH && round == 0, first0, first1, first2, first3, !CHIMERA || !sc.chimera);
         pc.mark(1);  // (... the lanes' own hits)
         // ---- from here on: the arguments through `la`, the spectrum's scalars from R.hdr (see LateArgs) ----
