@@ -576,8 +576,8 @@ int sage_hip_db_create(const SageDbView* v, int device, SageDeviceDb** out) {
         max_ions = std::max<uint32_t>(max_ions, (uint32_t)cnt);
         info[i] = (uint32_t)len | ((uint32_t)(v->decoy[i] ? 1 : 0) << 16) | ((uint32_t)v->missed_cleavages[i] << 24);
     }
-    uint32_t tile_shift = 15;
-    if (const char* e = getenv("SAGE_HIP_TILE_SHIFT")) tile_shift = (uint32_t)std::min(15, std::max(11, atoi(e)));
+    uint32_t tile_shift = TILE_SHIFT_MAX;
+    if (const char* e = getenv("SAGE_HIP_TILE_SHIFT")) tile_shift = (uint32_t)std::min((int)TILE_SHIFT_MAX, std::max(11, atoi(e)));
     const uint64_t n_tiles = std::max<uint64_t>(1, (np + (1ull << tile_shift) - 1) >> tile_shift);
     // 1/256 Da cells.  The scale is a power of two, so `m/z * scale` is exact in f32 and a fragment-tolerance window
     // [lo, hi] maps to the cell range [floor(lo*scale), floor(hi*scale)] with no safety margin.
@@ -617,7 +617,7 @@ int sage_hip_db_create(const SageDbView* v, int device, SageDeviceDb** out) {
                                                                 v->min_ion_index, d->ion_off.p, d->pm_off.p, d->ions.p, d->pm_frag.p, nullptr);
         if (be == hipSuccess)
             be = (hipError_t)build_tile_copy_on_device(d->pm_frag.p, nf, tile_shift, (uint32_t)n_tiles, d_tile_off.p, lut_scale,
-                                                       d->tm_frag.p, d->tm_lut, &lut_stride, nullptr, TM_LUT_LAYOUT);
+                                                       d->tm_frag.p, d->tm_lut, &lut_stride, nullptr);
         if (be != hipSuccess) return fail(status_of(be), std::string("device index build: ") + hipGetErrorString(be));
         host_pm_off.swap(pm_off);
         HIP_TRY(d->pep_info.upload(info.data(), np));
@@ -664,13 +664,12 @@ int sage_hip_db_create(const SageDbView* v, int device, SageDeviceDb** out) {
             if (tm[i].fragment_mz > max_mz && std::isfinite(tm[i].fragment_mz)) max_mz = tm[i].fragment_mz;
         lut_stride = (uint32_t)std::min<double>(std::ceil((double)max_mz * lut_scale) + 3.0, 64.0e6);
         if ((double)n_tiles * lut_stride > 4.0e9) return fail(SAGE_HIP_ERR_UNSUPPORTED, "tile position table larger than 16 GB");
-        // (rows beyond the last tile — padding of the quad layout — are empty tiles at the end of the array)
-        std::vector<uint32_t> lut((size_t)tm_lut_rows((uint32_t)n_tiles) * lut_stride, (uint32_t)tile_off[n_tiles]);
+        std::vector<uint32_t> lut((size_t)n_tiles * lut_stride, (uint32_t)tile_off[n_tiles]);
         parallel_for(n_tiles, 1, [&](size_t tb, size_t te, unsigned) {
             for (size_t t = tb; t < te; t++) {
                 uint64_t pos = tile_off[t];
                 const uint64_t tend = tile_off[t + 1];
-                auto cell = [&](uint32_t c) -> uint32_t& { return lut[tm_lut_index((uint32_t)t, c, (uint32_t)n_tiles, lut_stride)]; };
+                auto cell = [&](uint32_t c) -> uint32_t& { return lut[tm_lut_index((uint32_t)t, c, lut_stride)]; };
                 for (uint32_t c = 0; c < lut_stride; c++) {
                     const double edge = (double)c / (double)lut_scale;
                     // NaN and m/z beyond the table (non-finite or > 250 kDa) compare false and stay in the last cell's run

@@ -32,7 +32,7 @@ struct DevDbView {
     // (the last cell of a tile is its end position), row-major: lut[t][c].  (Round 4 measured the transposed layout, lut[c][t] —
     // the words one fragment-tolerance window needs from the ~100 consecutive tiles of a precursor window share cache lines:
     // same kernel time, 16 % MORE HBM traffic on C4 (2.48 against 2.13 MB per spectrum: a tile's windows no longer share the
-    // tile's row) — TM_LUT_TRANSPOSED keeps both layouts buildable.)  A (peak window, tile) lookup is two table reads and a
+    // tile's row).)  A (peak window, tile) lookup is two table reads and a
     // short contiguous run of entries; the tile's candidate counters fit in LDS.
     const SageTheoretical* tm_frag;  // [nf + 2]
     const uint32_t* tm_lut;          // [n_tiles * lut_stride]
@@ -58,24 +58,10 @@ struct DevDbView {
     uint32_t n_kinds;
 };
 
-// Layout of the large tiles' position table (tm_lut).  0: row-major, lut[t][c].  1: transposed, lut[c][t] (round 4's experiment:
-// the words one window needs from consecutive tiles share lines — and are evicted from L2 before the next tile asks).  2: QUADS,
-// lut[t / 4][c][t % 4] (round 5): the words of a cell for four consecutive tiles are one aligned 16-byte load, so the count
-// kernel reads a window's table words once per FOUR tiles (kernels.hip: issue_lut) — a quarter of the table's line requests.
-// The table has tm_lut_rows(n_tiles) rows; rows beyond n_tiles describe empty tiles.
-#ifndef SAGE_TM_LUT_TRANSPOSED
-#define SAGE_TM_LUT_TRANSPOSED 0
-#endif
-#ifndef SAGE_TM_LUT_QUAD
-#define SAGE_TM_LUT_QUAD 0
-#endif
-constexpr int TM_LUT_LAYOUT = SAGE_TM_LUT_QUAD != 0 ? 2 : SAGE_TM_LUT_TRANSPOSED != 0 ? 1 : 0;
-constexpr bool TM_LUT_TRANSPOSED = TM_LUT_LAYOUT == 1;
-__host__ __device__ inline uint32_t tm_lut_rows(uint32_t n_tiles) { return TM_LUT_LAYOUT == 2 ? (n_tiles + 3u) & ~3u : n_tiles; }
-__host__ __device__ inline size_t tm_lut_index(uint32_t t, uint32_t c, uint32_t n_tiles, uint32_t lut_stride) {
-    return TM_LUT_LAYOUT == 2 ? (((size_t)(t >> 2) * lut_stride + c) << 2) + (t & 3u)
-           : TM_LUT_LAYOUT == 1 ? (size_t)c * n_tiles + t : (size_t)t * lut_stride + c;
-}
+// Layout of the large tiles' position table (tm_lut): row-major, lut[t][c], n_tiles rows.  (The transposed layout, lut[c][t], of
+// round 4 and the quads of tiles, lut[t / 4][c][t % 4], of round 5 measured no better: DESIGN.md 4.2.)
+constexpr uint32_t TILE_SHIFT_MAX = 15;  // the large tiles hold at most 2^15 peptides (the count kernel's scan: 64 slots per thread)
+__host__ __device__ inline size_t tm_lut_index(uint32_t t, uint32_t c, uint32_t lut_stride) { return (size_t)t * lut_stride + c; }
 
 // SAGE_HIP_PHASE_CLOCKS=1: DevWork::dbg holds DBG_BLOCKS rows of 32 words (phase cycles and byte counts, kernels.hip: PhaseClock)
 // and behind them DBG_BLOCKS rows of DBG_PRUNE_WORDS words: what the rescoring prune dropped (words 0..3, sage_hip_debug_prune_counters)

@@ -123,7 +123,7 @@ hipError_t with_scratch(Call&& call) {
 // A tile-major copy of the peptide-major list for tiles of 2^tile_shift peptides + its position table (lut_stride cells per tile)
 int build_tile_copy_on_device(const SageTheoretical* d_pm_frag, uint64_t nf, uint32_t tile_shift, uint32_t n_tiles,
                               const uint64_t* d_tile_off, float lut_scale, SageTheoretical* d_tm_frag, DevBuf<uint32_t>& lut,
-                              uint32_t* lut_stride_out, void* stream, int layout = 0);
+                              uint32_t* lut_stride_out, void* stream);
 // lut[n_tiles][lut_stride] (row-major, as build_tile_copy_on_device makes it) -> its succinct form
 int build_succinct_lut_on_device(const uint32_t* d_lut, uint32_t n_tiles, uint32_t lut_stride, DevBuf<sagecore::LutWord>& l1,
                                  DevBuf<uint32_t>& pos, uint32_t* words_out, void* stream);

@@ -105,30 +105,17 @@ __global__ __launch_bounds__(256) void decode_kernel(uint64_t nf, uint32_t tile_
 }
 
 // the position table of a tile-major copy: entry (t, c) = first position of tile t whose m/z is >= c / scale (c == 0: the tile's
-// start, c == last: its end).  Row-major, lut[t][c] — the small tiles of the narrow kernel, where a window meets one or two tiles —
-// or TRANSPOSED, lut[c][t] — the large tiles of the open-search kernel, where ONE window is looked up in the ~100 consecutive
-// tiles of a precursor window: the words of consecutive tiles then share a cache line (32 tiles per 128 bytes) instead of
-// costing a line each.
-template <int LAYOUT>  // device_types.h: TM_LUT_LAYOUT (0 row-major, 1 transposed, 2 quads of tiles)
+// start, c == last: its end).  Row-major, lut[t][c] (device_types.h: tm_lut_index), for the small tiles of the narrow kernel and the
+// large ones of the open-search kernel alike.
 __global__ __launch_bounds__(256) void lut_kernel(uint32_t n_tiles, uint32_t lut_stride, float lut_scale,
                                                   const uint64_t* __restrict__ tile_off, const SageTheoretical* __restrict__ tm,
                                                   uint32_t* __restrict__ lut) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t rows = LAYOUT == 2 ? (n_tiles + 3u) & ~3u : n_tiles;
-    if (gid >= (uint64_t)rows * lut_stride) return;
-    uint32_t t, c;
-    if (LAYOUT == 2) {
-        t = (uint32_t)((gid >> 2) / lut_stride) * 4u + (uint32_t)(gid & 3u);
-        c = (uint32_t)((gid >> 2) % lut_stride);
-    } else if (LAYOUT == 1) {
-        c = (uint32_t)(gid / n_tiles);
-        t = (uint32_t)(gid - (uint64_t)c * n_tiles);
-    } else {
-        t = (uint32_t)(gid / lut_stride);
-        c = (uint32_t)(gid - (uint64_t)t * lut_stride);
-    }
+    if (gid >= (uint64_t)n_tiles * lut_stride) return;
+    const uint32_t t = (uint32_t)(gid / lut_stride);
+    const uint32_t c = (uint32_t)(gid - (uint64_t)t * lut_stride);
     static_assert(sizeof(SageTheoretical) == 8, "m/z is every second float of the entry array");
-    // (a row beyond the last tile — padding of the last quad — is an empty tile at the end of the array)
+    // (t < n_tiles follows from the bound on gid, which the compiler does not see: dropping the select changes the kernel's code)
     lut[gid] = t < n_tiles ? sagecore::lut_entry(&tm[0].fragment_mz, 2, tile_off[t], tile_off[t + 1], c, lut_stride, lut_scale)
                            : (uint32_t)tile_off[n_tiles];
 }
@@ -264,7 +251,7 @@ int sort_entries_on_device(const SageTheoretical* src, uint64_t nf, uint32_t til
 // the table is allocated here (its width depends on the largest fragment m/z).
 int build_tile_copy_on_device(const SageTheoretical* d_pm_frag, uint64_t nf, uint32_t tile_shift, uint32_t n_tiles,
                               const uint64_t* d_tile_off, float lut_scale, SageTheoretical* d_tm_frag, DevBuf<uint32_t>& lut,
-                              uint32_t* lut_stride_out, void* stream_, int layout) {
+                              uint32_t* lut_stride_out, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     // largest finite fragment m/z -> table width
     DevBuf<uint32_t> d_max;
@@ -284,15 +271,10 @@ int build_tile_copy_on_device(const SageTheoretical* d_pm_frag, uint64_t nf, uin
     if ((double)n_tiles * lut_stride > 4.0e9) return (int)hipErrorInvalidValue;
     SortScratch keys;
     if (int e = sort_entries_on_device(d_pm_frag, nf, tile_shift, d_tm_frag, keys, stream)) return e;
-    const uint64_t lut_n = (uint64_t)(layout == 2 ? (n_tiles + 3u) & ~3u : n_tiles) * lut_stride;
+    const uint64_t lut_n = (uint64_t)n_tiles * lut_stride;
     HIP_TRY(lut.alloc(lut_n));
     const dim3 lut_grid((uint32_t)((lut_n + 255) / 256));
-    if (layout == 2)
-        hipLaunchKernelGGL(lut_kernel<2>, lut_grid, dim3(256), 0, stream, n_tiles, lut_stride, lut_scale, d_tile_off, d_tm_frag, lut.p);
-    else if (layout == 1)
-        hipLaunchKernelGGL(lut_kernel<1>, lut_grid, dim3(256), 0, stream, n_tiles, lut_stride, lut_scale, d_tile_off, d_tm_frag, lut.p);
-    else
-        hipLaunchKernelGGL(lut_kernel<0>, lut_grid, dim3(256), 0, stream, n_tiles, lut_stride, lut_scale, d_tile_off, d_tm_frag, lut.p);
+    hipLaunchKernelGGL(lut_kernel, lut_grid, dim3(256), 0, stream, n_tiles, lut_stride, lut_scale, d_tile_off, d_tm_frag, lut.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     *lut_stride_out = lut_stride;

@@ -28,15 +28,67 @@ namespace sagehip {
 
 namespace {
 
+// ---- build-time tuning constants --------------------------------------------------------------------------------------------------
+// Every -D knob of the kernels, each defined here and nowhere else (scripts/variants.sh builds variants; DESIGN.md 8a lists them).
+#ifndef SAGE_PRELIM_WAVES
+#define SAGE_PRELIM_WAVES 5  // wavefronts per SIMD of prelim_kernel; 0: leave the occupancy to the compiler (A/B on C3: 5 > 6 > 7 > 8)
+#endif
+#ifndef SAGE_RESCORE_WAVES
+#define SAGE_RESCORE_WAVES 5  // ... of rescore_kernel (A/B on C3 with the cooperative matching: 5 > 6)
+#endif
+#ifndef SAGE_NARROW_WAVES
+#define SAGE_NARROW_WAVES 5  // ... of the fused narrow kernel
+#endif
+#ifndef SAGE_PROBE_PER_LANE
+#define SAGE_PROBE_PER_LANE 2   // windows whose table reads a lane of the probe kernel keeps in flight (x 64 lanes = one batch); 2 measured best on C3 (LDS footprint vs loads in flight)
+#endif
+#ifndef SAGE_PROBE_CELLS
+#define SAGE_PROBE_CELLS 4      // 16-byte index cells a lane keeps in flight per pass over the flattened runs
+#endif
+#ifndef SAGE_TILE8_CELLS
+#define SAGE_TILE8_CELLS 2  // cells a thread of the u8 count kernel keeps in flight (round 6, after the rank locate: 2 spill 7 vector registers instead of 18 — C5 41.8 -> 40.8 ms, C4 unchanged; 3 before)
+#endif
+#ifndef SAGE_MARK_BLOCKS8
+#define SAGE_MARK_BLOCKS8 96   // blocks of 64 flattened cells the count kernel's run-start marks cover at a time, u8 instance (tile_mark_blocks)
+#endif
+#ifndef SAGE_MARK_BLOCKS16
+#define SAGE_MARK_BLOCKS16 40  // ... u16 instance, which has the LDS of two workgroups per compute unit to fit
+#endif
+#ifndef SAGE_COOP_MIN_HITS
+#define SAGE_COOP_MIN_HITS 12  // rescore_kernel: hits in a 64-ion chunk above which the wavefront matches the candidate together (8 / 12 / 16: 2.225 / 2.19 / 2.202 ms)
+#endif
+#ifndef SAGE_COOP_MAX_LANES
+#define SAGE_COOP_MAX_LANES 2  // ... when at most this many candidates of the spectrum are that heavy
+#endif
+// Two switches whose other side no document records (only the notes here): left as they are.
+#ifndef SAGE_CNT_MODE
+#define SAGE_CNT_MODE 0  // prelim_kernel's kept window counts (measurement variants: 1 = the row header only, 2 = the counts only)
+#endif
+#ifndef SAGE_SCAN_SKIP
+#define SAGE_SCAN_SKIP 1  // (a wavefront without candidate bits in a tile skips the prefix sum of the scan: C4 -0.4 %, C5 -0.6 %)
+#endif
+#if SAGE_NARROW_WAVES
+#define SAGE_NARROW_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(SAGE_NARROW_WAVES, SAGE_NARROW_WAVES)))
+#else
+#define SAGE_NARROW_WAVES_ATTR
+#endif
+#if SAGE_PRELIM_WAVES
+#define SAGE_PRELIM_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(SAGE_PRELIM_WAVES, SAGE_PRELIM_WAVES)))
+#else
+#define SAGE_PRELIM_WAVES_ATTR
+#endif
+#if SAGE_RESCORE_WAVES
+#define SAGE_RESCORE_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(SAGE_RESCORE_WAVES, SAGE_RESCORE_WAVES)))
+#else
+#define SAGE_RESCORE_WAVES_ATTR
+#endif
+
 constexpr uint32_t WAVE = 64;
 // LDS words the in-line tie replay of rescore_spectrum may overwrite: the peak bitmap and the peak table behind it (both dead by
 // then).  A row of window counts holds (potential + 1) / 2 words, potential <= wcap: capi.hip switches fast ties off for a wcap
 // whose rows would not fit, and the kernel checks every row again.
 constexpr uint32_t FAST_TIE_WORDS = PBM_WORDS + PLUT_BINS;
 constexpr uint32_t CNT_ROW_HEADER = 4;  // DevWork::cnt_store: words in front of a row's counts (keeps them 16-byte aligned)
-#ifndef SAGE_PROBE_PER_LANE
-#define SAGE_PROBE_PER_LANE 2   // windows whose table reads a lane of the probe kernel keeps in flight (x 64 lanes = one batch); 2 measured best on C3 (LDS footprint vs loads in flight)
-#endif
 constexpr uint32_t PROBE_BATCH_WORDS = SAGE_PROBE_PER_LANE * 64;
 // the run table of a batch: run first / end entry, window lo / hi (PROBE_BATCH_WORDS words each) and the first cell of every run, padded
 // with sentinels to a power of two (the owner search halves it)
@@ -129,20 +181,6 @@ struct NoClock {
 };
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-
-// Staggered start (experiment, -DSAGE_STAGGER_NS=<ns per slot>): the first generation of a per-spectrum kernel's wavefronts — five
-// per SIMD, all launched within microseconds — runs its phases in lockstep (every wavefront waits on memory, then every one wants
-// the vector ALU), which is part of what a "cold start" costs; workgroup b of the first 5 x 1024 is held back by (b / 1024) slots.
-#ifndef SAGE_STAGGER_NS
-#define SAGE_STAGGER_NS 0
-#endif
-__device__ __forceinline__ void staggered_start(uint32_t blk) {
-    if (SAGE_STAGGER_NS > 0 && blk >= 1024u && blk < 5u * 1024u) {
-        const uint32_t slot = blk / 1024u;
-        const long long until = (long long)__builtin_amdgcn_s_memtime() + (long long)slot * (SAGE_STAGGER_NS * 2);  // (s_memtime counts shader clocks here: ~2 per ns)
-        while ((long long)__builtin_amdgcn_s_memtime() < until) __builtin_amdgcn_s_sleep(32);
-    }
-}
 
 // XCD-aware schedule position.  Workgroup b of a launch is observed to run on XCD b % 8 (MI355X_MICROARCH.md, "Workgroup
 // dispatch"; a speed matter only, nothing here depends on it), each XCD with a private 4 MiB L2.  The per-spectrum kernels walk
@@ -695,10 +733,7 @@ __device__ __forceinline__ Window query_window(const float* __restrict__ pep_mon
     if (lut && plo >= 0.0f && phi >= plo && phi * inv_w < (float)bins) {
         const uint32_t b0 = uni((uint32_t)(plo * inv_w)), b1 = uni((uint32_t)(phi * inv_w));  // (the scaling is exact: floor)
         const uint32_t l0 = lut[b0], l1 = lut[b0 + 1], r0 = lut[b1], r1 = lut[b1 + 1];
-#ifndef SAGE_QUERY_ONE_TRIP
-#define SAGE_QUERY_ONE_TRIP 1
-#endif
-        if (SAGE_QUERY_ONE_TRIP && l1 - l0 < WAVE && r1 - r0 < WAVE) {
+        if (l1 - l0 < WAVE && r1 - r0 < WAVE) {
             // Both brackets fit a wavefront (the usual case: a bin of 1/128 Da): ONE trip to pep_mono instead of four in a row — the
             // two partition points from two reads in flight together, and the edge rule's two masses (below) out of the same
             // registers: lanes of `vl` hold [l0 - 1, l0 + 63), lanes of `vr` [r0, r0 + 64); `left` is l0 - 1 .. l1 - 1 and `right`
@@ -806,46 +841,17 @@ __device__ __forceinline__ bool fast_select(const PrelimLds& L, const Counters& 
 //                    reads + ~10-20 entries).  Cost ~ peaks x fragment charges, independent of the window: best from
 //                    ~100 candidates up.
 // The C ABI picks per batch from the mean window size (capi.hip: sage_hip_batch_upload).
-// Build-time knobs, with the values measured best on MI355X (scripts/variants.sh, scripts/ab_libs.sh; C3: 26.3 -> 29.8 M
+// The build-time knobs (the block at the head of this file) hold the values measured best on MI355X (scripts/variants.sh,
+// scripts/ab_libs.sh; C3: 26.3 -> 29.8 M
 // spectra/s).  Both per-spectrum kernels are bound by dependent memory / LDS round trips, so resident wavefronts matter more
 // than registers per wavefront: capping the VGPR budget at 6 waves per SIMD (80 VGPRs, a handful of spills outside the inner
 // loops) and keeping LDS per wavefront under 160 KB / 24 buys ~10 %; past 6 waves nothing more comes.
-#ifndef SAGE_PRELIM_WAVES
-#define SAGE_PRELIM_WAVES 5  // 0: leave the occupancy to the compiler (A/B on C3: 5 > 6 > 7 > 8)
-#endif
-#ifndef SAGE_RESCORE_WAVES
-#define SAGE_RESCORE_WAVES 5  // (A/B on C3 with the cooperative matching: 5 > 6)
-#endif
-#ifndef SAGE_PROBE_PER_LANE
-#define SAGE_PROBE_PER_LANE 2   // windows whose table reads a lane of the probe kernel keeps in flight (x 64 lanes = one batch); 2 measured best on C3 (LDS footprint vs loads in flight)
-#endif
-#ifndef SAGE_PROBE_CELLS
-#define SAGE_PROBE_CELLS 4      // 16-byte index cells a lane keeps in flight per pass over the flattened runs
-#endif
 constexpr uint32_t PROBE_PER_LANE = SAGE_PROBE_PER_LANE;
 constexpr uint32_t PROBE_BATCH = PROBE_PER_LANE * 64;
 constexpr uint32_t PROBE_CELLS = SAGE_PROBE_CELLS;
 constexpr uint32_t NO_WINDOW = 0xFFFFFFFFu;
 static_assert(PROBE_BATCH == PROBE_BATCH_WORDS && PROBE_BATCH <= 512, "the run table's layout (carve_prelim) is the kernel's");
 static_assert(PROBE_TCS_WORDS - PROBE_BATCH <= WAVE, "one sentinel per lane pads the run starts");
-#ifndef SAGE_NARROW_WAVES
-#define SAGE_NARROW_WAVES 5  // the fused narrow kernel
-#endif
-#if SAGE_NARROW_WAVES
-#define SAGE_NARROW_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(SAGE_NARROW_WAVES, SAGE_NARROW_WAVES)))
-#else
-#define SAGE_NARROW_WAVES_ATTR
-#endif
-#if SAGE_PRELIM_WAVES
-#define SAGE_PRELIM_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(SAGE_PRELIM_WAVES, SAGE_PRELIM_WAVES)))
-#else
-#define SAGE_PRELIM_WAVES_ATTR
-#endif
-#if SAGE_RESCORE_WAVES
-#define SAGE_RESCORE_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(SAGE_RESCORE_WAVES, SAGE_RESCORE_WAVES)))
-#else
-#define SAGE_RESCORE_WAVES_ATTR
-#endif
 // ---- arguments where they are used ---------------------------------------------------------------------------------------------
 // The per-spectrum kernels take ~100 scalar registers' worth of arguments (four views) and have 100 scalar registers.  Loaded at
 // the kernel's entry — where the compiler puts kernarg loads — most of them are written to spill lanes at once and read back
@@ -1073,13 +1079,9 @@ __device__ __forceinline__ PrelimResult prelim_spectrum(const DevDbView& db_, co
                     float* const tlo = (float*)(L.ptab + 2 * PROBE_BATCH);
                     float* const thi = (float*)(L.ptab + 3 * PROBE_BATCH);
                     if (PROBE_TCS_WORDS > PROBE_BATCH && lane < PROBE_TCS_WORDS - PROBE_BATCH) tcs[PROBE_BATCH + lane] = NO_WINDOW;  // (never rewritten)
-#ifndef SAGE_PROBE_SYM
-#define SAGE_PROBE_SYM 1      // a symmetric ppm tolerance: one division per window (core.h: tol_bounds_sym, the same bits)
-#endif
-#ifndef SAGE_PROBE_FASTDIV
-#define SAGE_PROBE_FASTDIV 1  // ... and that division in the short form where every lane's dividend is in its proven range
-#endif
-                    const bool sym_ppm = SAGE_PROBE_SYM && (av.sc().tol_mode & TOL_SYM) != 0u && ftol.kind == 0;
+                    // a symmetric ppm tolerance: one division per window (core.h: tol_bounds_sym, the same bits), and that division in
+                    // the short form where every lane's dividend is in its proven range
+                    const bool sym_ppm = (av.sc().tol_mode & TOL_SYM) != 0u && ftol.kind == 0;
                     auto window_of = [&](uint32_t pr, float& flo, float& fhi) {
                         flo = 1.0f; fhi = 0.0f;  // (no such window: empty)
                         const bool has = pr < nprobe;
@@ -1095,7 +1097,7 @@ __device__ __forceinline__ PrelimResult prelim_spectrum(const DevDbView& db_, co
                             // and the whole wavefront takes the IEEE sequence for this batch
                             const float x = center * ftol.hi, ax = __builtin_fabsf(x);
                             float d;
-                            if (SAGE_PROBE_FASTDIV && __ballot(has && !(ax >= FAST_DIV_LO && ax <= FAST_DIV_HI)) == 0ull) d = div_1e6_fast(x);
+                            if (__ballot(has && !(ax >= FAST_DIV_LO && ax <= FAST_DIV_HI)) == 0ull) d = div_1e6_fast(x);
                             else d = x / 1000000.0f;
                             if (has) { flo = center + -d; fhi = center + d; }
                         } else if (has) {
@@ -1106,10 +1108,7 @@ __device__ __forceinline__ PrelimResult prelim_spectrum(const DevDbView& db_, co
                         const LutWord* __restrict__ l1 = tm2_l1 + (size_t)t * lut2_words;
                         // table reads of up to PROBE_BATCH windows, PROBE_PER_LANE per lane, all in flight together; window q of the
                         // flattened order (lane-major) is window pbase + (q % PPL) * 64 + q / PPL.  The reads of batch b + 1 are
-                        // issued before the cells of batch b are walked (SAGE_PROBE_PIPELINE): one round trip less per further batch.
-#ifndef SAGE_PROBE_PIPELINE
-#define SAGE_PROBE_PIPELINE 1
-#endif
+                        // issued before the cells of batch b are walked: one round trip less per further batch.
                         uint32_t np0[PROBE_PER_LANE], np1[PROBE_PER_LANE];
                         float nlo[PROBE_PER_LANE], nhi[PROBE_PER_LANE];
                         // The table in succinct form (core.h: LutWord): a window's run is [pos[rank(icl)], pos[rank(ich)]), the ranks from
@@ -1137,9 +1136,8 @@ __device__ __forceinline__ PrelimResult prelim_spectrum(const DevDbView& db_, co
                                 }
                             }
                         };
-                        if (SAGE_PROBE_PIPELINE) issue(0);
+                        issue(0);
                         for (uint32_t pbase = 0; pbase < nprobe; pbase += PROBE_BATCH) {
-                            if (!SAGE_PROBE_PIPELINE) issue(pbase);
                             uint32_t rp0[PROBE_PER_LANE], rp1[PROBE_PER_LANE];
 #pragma unroll
                             for (uint32_t i = 0; i < PROBE_PER_LANE; i++) {
@@ -1147,7 +1145,7 @@ __device__ __forceinline__ PrelimResult prelim_spectrum(const DevDbView& db_, co
                                 tlo[lane * PROBE_PER_LANE + i] = nlo[i];  // (the previous batch's cells are done: wave_sync below)
                                 thi[lane * PROBE_PER_LANE + i] = nhi[i];
                             }
-                            if (SAGE_PROBE_PIPELINE && pbase + PROBE_BATCH < nprobe) issue(pbase + PROBE_BATCH);
+                            if (pbase + PROBE_BATCH < nprobe) issue(pbase + PROBE_BATCH);
                             uint32_t tot = 0;
 #pragma unroll
                             for (uint32_t i = 0; i < PROBE_PER_LANE; i++) tot += rp1[i] > rp0[i] ? ((rp1[i] - 1) >> 1) - (rp0[i] >> 1) + 1 : 0;
@@ -1330,7 +1328,6 @@ __global__ __launch_bounds__(64) SAGE_PRELIM_WAVES_ATTR void prelim_kernel(Preli
     typedef typename std::conditional<PROF, PhaseClock, NoClock>::type Clock;
     extern __shared__ __align__(16) unsigned char smem[];
     const uint32_t lane = lane_id();
-    staggered_start(blockIdx.x);
     const PrelimLds L = carve_prelim(smem, sc, b, BIGK && HUGE ? w.hugebuf + (size_t)blockIdx.x * w.huge_stride : nullptr);
 
     uint32_t n_batch = b.n;
@@ -1359,9 +1356,6 @@ __global__ __launch_bounds__(64) SAGE_PRELIM_WAVES_ATTR void prelim_kernel(Preli
             // (address translation).  A row: {left, potential, -, -} then the u16 counts, two per word.
             const bool keep = !r.deferred && si.z0 == si.z1 && ka->sc.min_isotope_err == ka->sc.max_isotope_err;
             uint32_t* __restrict__ row = w_cnt_store + (size_t)pos * ka->w.cnt_stride;
-#ifndef SAGE_CNT_MODE
-#define SAGE_CNT_MODE 0  // (measurement variants: 1 = the row header only, 2 = the counts only)
-#endif
             if (keep && SAGE_CNT_MODE != 1)
                 for (uint32_t i = lane; i < (r.q_potential + 1) / 2; i += WAVE) row[CNT_ROW_HEADER + i] = L.cnt[i];
             if (lane == 0 && SAGE_CNT_MODE != 2) {
@@ -1479,12 +1473,6 @@ constexpr uint32_t TILE_QW_MAX = 64;  // queries per spectrum whose windows are 
 // blocks of 64 flattened cells the run-start marks of a unit cover at a time (a unit with more cells re-marks, a rare and slow path):
 // the u8 instance keeps 3 cells per thread in flight (1 536 per round, 24 blocks), the u16 one 4 (2 048, 32 blocks) and has the LDS of
 // two workgroups per compute unit to fit
-#ifndef SAGE_MARK_BLOCKS8
-#define SAGE_MARK_BLOCKS8 96
-#endif
-#ifndef SAGE_MARK_BLOCKS16
-#define SAGE_MARK_BLOCKS16 40
-#endif
 __host__ __device__ constexpr uint32_t tile_mark_blocks(bool cnt8) { return cnt8 ? SAGE_MARK_BLOCKS8 : SAGE_MARK_BLOCKS16; }
 // `wing`: the windows of the spectrum live in a global-memory workspace instead (tile_count_wing_kernel: spectra whose peaks x
 // fragment charges do not fit a compute unit's LDS next to the counters)
@@ -1559,24 +1547,8 @@ __device__ __forceinline__ void tile_count_body(const TileParams& kp, unsigned c
     constexpr uint32_t CSH = C8 ? 2 : 1;            // slot -> word
     constexpr uint32_t CBITS = C8 ? 8 : 16;         // bits per counter
     constexpr uint32_t CMAX = C8 ? 0xFFu : 0xFFFFu;
-#ifndef SAGE_TILE8_CELLS
-#define SAGE_TILE8_CELLS 2  // (round 6, after the rank locate: 2 cells per thread in flight spill 7 vector registers instead of 18 — C5 41.8 -> 40.8 ms, C4 unchanged; 3 before)
-#endif
-// Round 5 experiments on the count kernel's instruction count (it executes vector instructions 80 % of its SIMDs' time), A/B'd on C4
-// / C5 (scripts/experiments/r05_lab/gpu_r5q.sh, gpu_r5r.sh): the owner wavefront of a cell by BISECTION over the running totals (14
-// instructions instead of 35) and both index ranges of an entry as one unsigned compare each — 20 % SLOWER on C4 (58.0 -> 69.6 ms:
-// the selects spill, scratch 128 -> 160 bytes per lane); a linear walk over the running totals (21 instructions) with the old
-// predicates: -1 % (57.0 ms), the default now; with the one-compare ranges: 0.  Fewer instructions buy nothing here unless the
-// register allocation holds still.
-#ifndef SAGE_HIT_RANGES
-#define SAGE_HIT_RANGES 1  // (round 6, with the arguments out of the registers: the allocation holds still — 64 / 18 spills either way —, C4 -1 %, C5 -0.7 %)
-#endif
-#ifndef SAGE_SCAN_SKIP
-#define SAGE_SCAN_SKIP 1  // (a wavefront without candidate bits in a tile skips the prefix sum of the scan: C4 -0.4 %, C5 -0.6 %)
-#endif
-#ifndef SAGE_LOCATE_LINEAR
-#define SAGE_LOCATE_LINEAR 1
-#endif
+    // (How a cell finds its owner and how SAGE_HIT tests an entry's two index ranges were settled by A/B in rounds 5 and 6 — fewer
+    // instructions buy nothing here unless the register allocation holds still: DESIGN.md 4.2.)
     // cells a thread keeps in flight: the u8 instance runs 6 wavefronts per SIMD in 80 VGPRs, the u16 one 4 in 128
     constexpr uint32_t CPT = C8 ? SAGE_TILE8_CELLS : CELLS_PER_THREAD;
     // Arguments where they are used (the ArgRef idea of prelim_kernel): the four views are ~110 scalar registers' worth of pointers
@@ -1778,30 +1750,7 @@ __device__ __forceinline__ void tile_count_body(const TileParams& kp, unsigned c
                 const uint32_t nb = nprobe ? (nprobe + TILE_THREADS - 1) / TILE_THREADS : 1;  // units per tile (1 up to 512 windows)
                 const uint32_t n_units = (t1 - t0 + 1) * nb;
                 uint32_t np0 = 0, np1 = 0;  // table values of this thread's window in the NEXT unit (in flight)
-                // Quad layout of the table (device_types.h: TM_LUT_LAYOUT == 2), one unit per tile (up to 512 windows — every
-                // configuration of BASELINE.json): a thread reads the two table words of its window for FOUR consecutive tiles
-                // with two 16-byte loads when the walk enters a quad of tiles, and hands them out tile by tile (x is the tile
-                // about to be published; publish rotates).  The table's line requests — most of this kernel's HBM traffic: one
-                // line per (window, tile), against ~0.3 for the index entries themselves — fall to a quarter.
-                constexpr bool QUAD = TM_LUT_LAYOUT == 2;
-                uint4 qa = make_uint4(0u, 0u, 0u, 0u), qb = qa;
-                const bool quads = QUAD && nb == 1;
                 auto issue_lut = [&](uint32_t u) {
-                    if (quads) {
-                        const uint32_t t = t0 + u;
-                        if (u >= n_units || (u != 0 && (t & 3u) != 0)) return;  // (inside a quad: the words are there already)
-                        float lo, hi;
-                        uint32_t icl, ich;
-                        probe_bounds(tid, lo, hi);
-                        probe_cells(lo, hi, icl, ich);
-                        qa = qb = make_uint4(0u, 0u, 0u, 0u);
-                        if (tid < nprobe && first < end && lo <= hi) {
-                            const uint4* __restrict__ lut4 = (const uint4*)ka->db.tm_lut + (size_t)(t >> 2) * ka->db.lut_stride;
-                            qa = lut4[icl];
-                            qb = lut4[ich];
-                        }
-                        return;
-                    }
                     np0 = np1 = 0;
                     if (u >= n_units) return;
                     const uint32_t t = t0 + u / nb, pr = (u % nb) * TILE_THREADS + tid;
@@ -1810,8 +1759,8 @@ __device__ __forceinline__ void tile_count_body(const TileParams& kp, unsigned c
                     probe_bounds(pr, lo, hi);
                     probe_cells(lo, hi, icl, ich);
                     if (pr < nprobe && first < end && lo <= hi) {
-                        np0 = ka->db.tm_lut[tm_lut_index(t, icl, ka->db.n_tiles, ka->db.lut_stride)];
-                        np1 = ka->db.tm_lut[tm_lut_index(t, ich, ka->db.n_tiles, ka->db.lut_stride)];
+                        np0 = ka->db.tm_lut[tm_lut_index(t, icl, ka->db.lut_stride)];
+                        np1 = ka->db.tm_lut[tm_lut_index(t, ich, ka->db.lut_stride)];
                     }
                 };
                 // cells of the CURRENT unit in flight — named scalars, not arrays (arrays captured by the lambdas below end up in
@@ -1870,10 +1819,8 @@ __device__ __forceinline__ void tile_count_body(const TileParams& kp, unsigned c
 // and whether it just reached the tile's pruning threshold (then its bit in the candidate bitmap is set — a count crosses
 // the threshold once).  The scan after the tile only has to visit the set bits.
 #define SAGE_HIT(I, H, PEP, MZ, JJ)                                                                                  \
-    /* (SAGE_HIT_RANGES=1: an empty slot has p0 == p1 and lo > hi; both ranges as one unsigned compare each) */       \
-    hit##I##H = SAGE_HIT_RANGES ? ((JJ) - p0_##I < pl_##I && (MZ) >= lo_##I && (MZ) <= hi_##I && (PEP) - first < span_fe) \
-                                : (cpr##I != NONE32 && (JJ) >= p0_##I && (JJ) < p1_##I && (MZ) >= lo_##I && (MZ) <= hi_##I && \
-                                   (PEP) >= first && (PEP) < end);                                                  \
+    /* (an empty slot has p0 == p1 and lo > hi; both ranges as one unsigned compare each) */                          \
+    hit##I##H = (JJ) - p0_##I < pl_##I && (MZ) >= lo_##I && (MZ) <= hi_##I && (PEP) - first < span_fe;                \
     x##I##H = hit##I##H ? (PEP) - tb_ : 0u;                                                                          \
     /* no hit: add 0 to a counter word of this thread's own (distinct addresses, no branch, nothing changes) */       \
     old##I##H = atomicAdd(&l_cnt[hit##I##H ? x##I##H >> CSH : tid & idle_mask], hit##I##H ? 1u << ((x##I##H & (SPW - 1u)) * CBITS) : 0u);
@@ -1915,17 +1862,6 @@ __device__ __forceinline__ void tile_count_body(const TileParams& kp, unsigned c
                 // run lies in the unit's flattened cell list and which of the non-empty runs it is; its marks (locate).  The caller
                 // has made sure nobody still reads the previous unit's run table.
                 auto publish_totals = [&](uint32_t u) {
-                    if (quads) {
-                        if (u == 0)  // (a walk that starts inside a quad: bring its first tile to the front)
-                            for (uint32_t r = 0; r < (t0 & 3u); r++) {
-                                qa = make_uint4(qa.y, qa.z, qa.w, 0u);
-                                qb = make_uint4(qb.y, qb.z, qb.w, 0u);
-                            }
-                        np0 = qa.x;
-                        np1 = qb.x;
-                        qa = make_uint4(qa.y, qa.z, qa.w, 0u);
-                        qb = make_uint4(qb.y, qb.z, qb.w, 0u);
-                    }
                     const uint32_t ncell = np1 > np0 ? ((np1 - 1) >> 1) - (np0 >> 1) + 1 : 0;
                     const uint32_t total = wave_sum_dpp(ncell);
                     const uint64_t nzm = __ballot(ncell != 0u);
@@ -2082,13 +2018,14 @@ __device__ __forceinline__ void tile_count_body(const TileParams& kp, unsigned c
                     const uint32_t span_v = we > vs ? we - vs : 0u;
                     uint32_t spt_v = spt;
                     while (spt_v > SPW && (spt_v >> 1) * TILE_THREADS >= span_v) spt_v >>= 1;
-                    const uint32_t x0 = vs + tid * spt_v;  // this thread's first slot (a multiple of spt_v: bits never straddle a word)
+                    // this thread's first slot: a multiple of min(spt_v, 32), since vs is one of 32 — a thread's bits never straddle a
+                    // word unless spt_v == 64 and vs % 64 == 32, and that case reads two words below
+                    const uint32_t x0 = vs + tid * spt_v;
+                    static_assert((1u << TILE_SHIFT_MAX) / TILE_THREADS <= 64, "spt <= 64: a thread's slots fit the scan's 64-bit mask");
+                    static_assert((32 / SPW) % 4 == 0, "vs / SPW is a multiple of 4 words: the 16-byte counter clears below are aligned");
                     // (a window that covers the tile — every tile but the two ends of an open search's window — keeps round 5's forms:
                     // thread tid owns [tid * spt, (tid + 1) * spt), one 8-byte read, 16-byte clears)
-#ifndef SAGE_TILE_WHOLE_FAST
-#define SAGE_TILE_WHOLE_FAST 1
-#endif
-                    const bool whole_tile = SAGE_TILE_WHOLE_FAST && vs == 0u && spt_v == spt;
+                    const bool whole_tile = vs == 0u && spt_v == spt;
                     uint64_t mask = 0;
                     if (whole_tile) {
                         if (tid * spt < TS) {
@@ -2206,7 +2143,7 @@ __device__ __forceinline__ void tile_count_body(const TileParams& kp, unsigned c
                             else if (((tid * spt) & 31u) == 0) l_bm[(tid * spt) >> 5] = zr;
                         }
                     } else if (x0 < TS) {
-                        const uint32_t w_lo = x0 / SPW;                                   // (x0 is a multiple of spt_v >= SPW)
+                        const uint32_t w_lo = x0 / SPW;  // (x0 is a multiple of SPW: vs is one of 32, spt_v a power of two >= SPW)
                         const uint32_t w_n = x0 + spt_v <= TS ? spt_v / SPW : (TS - x0) / SPW;  // (the last piece may end with the tile)
                         if (spt_v / SPW >= 4 && w_n == spt_v / SPW) {
                             for (uint32_t i = 0; i < w_n; i += 4) *(uint4*)(l_cnt + w_lo + i) = make_uint4(zr, zr, zr, zr);
@@ -2338,43 +2275,24 @@ __device__ __forceinline__ void for_each_candidate_batch(const DevWork& w, const
             tb = (uint32_t)__shfl((int)r.tile_base, (int)own, 64);
             e = k < total ? w.arena[at + (k - first)] : 0u;
         };
-#ifndef SAGE_CAND_FETCH_DEPTH
-#define SAGE_CAND_FETCH_DEPTH 3  // fetches of 64 words in flight (round 6: 1 -> 3; the consumers do little per word, a fetch is a round trip to HBM)
-#endif
-        if (SAGE_CAND_FETCH_DEPTH > 1) {
-            // DEPTH fetches in flight, issued in ascending order (the owner carry goes from fetch to fetch), consumed in the same order
-            // (named scalars, not arrays: an array captured by `fetch` would live in scratch memory)
-#if SAGE_CAND_FETCH_DEPTH == 6
-#define SAGE_FETCH_SLOTS(X) X(0) X(1) X(2) X(3) X(4) X(5)
-#elif SAGE_CAND_FETCH_DEPTH == 4
-#define SAGE_FETCH_SLOTS(X) X(0) X(1) X(2) X(3)
-#else
+        // DEPTH fetches of 64 words in flight (round 6: 1 -> 3; the consumers do little per word, a fetch is a round trip to HBM), issued
+        // in ascending order (the owner carry goes from fetch to fetch), consumed in the same order
+        // (named scalars, not arrays: an array captured by `fetch` would live in scratch memory)
 #define SAGE_FETCH_SLOTS(X) X(0) X(1) X(2)
-#endif
-            constexpr uint32_t DEPTH = SAGE_CAND_FETCH_DEPTH == 6 ? 6 : SAGE_CAND_FETCH_DEPTH == 4 ? 4 : 3;
+        constexpr uint32_t DEPTH = 3;
 #define SAGE_FETCH_FIRST(I) uint32_t e##I = 0, t##I = 0; if (I * WAVE < total) fetch(I * WAVE, e##I, t##I);
-            SAGE_FETCH_SLOTS(SAGE_FETCH_FIRST)
+        SAGE_FETCH_SLOTS(SAGE_FETCH_FIRST)
 #undef SAGE_FETCH_FIRST
-            for (uint32_t base = 0; base < total; base += DEPTH * WAVE) {
+        for (uint32_t base = 0; base < total; base += DEPTH * WAVE) {
 #define SAGE_FETCH_TURN(I)                                                                        \
     if (base + I * WAVE < total) {                                                                \
         f(e##I, t##I);                                                                            \
         if (base + (DEPTH + I) * WAVE < total) fetch(base + (DEPTH + I) * WAVE, e##I, t##I);      \
     }
-                SAGE_FETCH_SLOTS(SAGE_FETCH_TURN)
+            SAGE_FETCH_SLOTS(SAGE_FETCH_TURN)
 #undef SAGE_FETCH_TURN
-            }
-#undef SAGE_FETCH_SLOTS
-        } else {
-            uint32_t e = 0, tb = 0, e_next = 0, tb_next = 0;
-            if (total) fetch(0, e, tb);
-            for (uint32_t base = 0; base < total; base += WAVE) {
-                if (base + WAVE < total) fetch(base + WAVE, e_next, tb_next);
-                f(e, tb);
-                e = e_next;
-                tb = tb_next;
-            }
         }
+#undef SAGE_FETCH_SLOTS
     }
 }
 
@@ -2939,12 +2857,6 @@ __device__ __forceinline__ void build_peak_lut(uint32_t* plut, float& inv_w, con
 }
 // The peak-presence bitmap that filters score_candidate's lookups (core.h: peak_bitmap_params / _span / _bin, shared with the
 // host so that the CPU suite can test that the filter never drops a match).
-#ifndef SAGE_COOP_MIN_HITS
-#define SAGE_COOP_MIN_HITS 12
-#endif
-#ifndef SAGE_COOP_MAX_LANES
-#define SAGE_COOP_MAX_LANES 2
-#endif
 // rescore_kernel: hits in a 64-ion chunk above which the wavefront matches the candidate together — when at most
 // COOP_MAX_LANES candidates of the spectrum are that heavy (with many heavy candidates — an open search keeps the 50 best of a
 // million — every lane is busy anyway and the lanes work on their own)
@@ -3152,31 +3064,22 @@ __device__ __forceinline__ uint64_t lane_run(uint64_t v, uint32_t src_lane) { re
 // LONG: the two Run states of a candidate in 64-bit registers (ion indices beyond 1023: core.h) — rescore_big_kernel's second
 // instance; every other caller keeps the one-register form.  FAST: the short divisions (core.h: div_const_fast) — an instance of
 // rescore_kernel the host picks when it has bounded the dividends.
-#ifndef SAGE_DENSE_HITS
-#define SAGE_DENSE_HITS 1  // 1: the lanes' own hits of a round's last chunk through a dense work list in the bitmap's bytes
-#endif
+// the lanes' own hits of a round's last chunk go through a dense work list in the bitmap's bytes
 constexpr uint32_t DENSE_CAP = 384;  // items of the dense work list: 2 x 4 + 2 bytes each and a flag bit, inside the bitmap's 4 KB
 static_assert(DENSE_CAP % 64 == 0 && DENSE_CAP * 10 + DENSE_CAP / 8 <= PBM_WORDS * 4, "the dense work list fits the bitmap");
-#ifndef SAGE_FLAT_GENERAL
-#define SAGE_FLAT_GENERAL 0  // 1: the general (CHIMERA) instances of rescore_spectrum take the flat route of the filter too — measured, no gain,
-                             //    and 14 more scalar spills in rescore_kernel's; 0: they keep to the per-lane filter
-#endif
 template <class PC, bool LONG = false, bool FAST = false, bool FLAT = !LONG>
 __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevScorer& sc, const uint32_t* pbm, const uint32_t* plut,
                                                  const float* pm, const float* pi, const uint32_t P, const float inv_w,
                                                  const bool valid, const uint64_t ion_base, const uint32_t lm1, const uint32_t nfz,
                                                  const bool any_fz2, const bool any_fz3, const uint32_t nterm_mask, const bool sym_tol,
-                                                 Score& s, PC& pc, const bool have_first = false, const float first0 = 0.f,
-                                                 const float first1 = 0.f, const float first2 = 0.f, const float first3 = 0.f,
-                                                 const bool dense_ok = false) {
-    // (have_first: the candidate's first four ions were requested by the caller, ahead of its LDS table builds.  A first chunk that
-    // takes the flat route does not use them: its workers load other candidates' ions, and the request is already under way.)
+                                                 Score& s, PC& pc, const bool dense_ok = false) {
     // The flat filter's area — RescoreLds::rm .. stage — is worked out from the two peak arrays where it is used
     // (rescore_flat_area) instead of being carried here in registers.  CALLERS: with FLAT, pm and pi must be the pm / pi of a
     // carve_rescore — pi == pm + pcap and rescore_flat_bytes(pcap) bytes behind pi's pcap floats that nothing else uses while
     // the filter runs; a caller that carves its peaks otherwise instantiates FLAT == false.  (FLAT == false: an instance that keeps to the per-lane
     // filter — LONG, rescore_big_kernel's second instance, where the flat route's registers cost a wavefront per SIMD, and the
-    // general instances of rescore_spectrum, which spill as it is: SAGE_FLAT_GENERAL.
+    // general instances of rescore_spectrum, which spill as it is: measured, no gain, and 14 more scalar spills in rescore_kernel's —
+    // DESIGN.md 4.3.
     // SAGE_HIP_DEBUG_FLAGS=8192: the per-lane filter for every chunk; 16384: tests take the flat route for every chunk whose bytes
     // fit, whether it wins or not.)
     static_assert(!(FLAT && LONG), "the flat route's worker offsets and tags are those of the one-register instances");
@@ -3277,9 +3180,7 @@ __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevS
         if (act && !flat) {  // ---- the PER-LANE route: every candidate's lane walks its own ions, four per trip
             // (the ion table is padded by 8: reading past the candidate's last ion is harmless, those bits are masked below)
             const float* __restrict__ q = my + j0;
-            float n0, n1, n2, n3;
-            if (have_first && j0 == 0) { n0 = first0; n1 = first1; n2 = first2; n3 = first3; }
-            else { n0 = q[0]; n1 = q[1]; n2 = q[2]; n3 = q[3]; }
+            float n0 = q[0], n1 = q[1], n2 = q[2], n3 = q[3];
             for (uint32_t r = 0; r < n_here; r += 4) {
                 const float i0 = n0, i1 = n1, i2 = n2, i3 = n3;
                 n0 = q[r + 4]; n1 = q[r + 5]; n2 = q[r + 6]; n3 = q[r + 7];  // next trip's ions, in flight under this trip's tests
@@ -3385,7 +3286,6 @@ TM = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
             }
         }
         pc.mark(7);  // (... the heavy candidates, wavefront-wide)
-#if SAGE_DENSE_HITS
         // ---- everybody else, DENSE: the lanes' hits of the LAST chunk of a scoring round no other round follows go through
         //      select_most_intense_peak 64 at a time instead of lane by lane behind the lane with the most hits.  The work list lives in
         //      the bitmap's bytes — dead by now: the filter above was its last reader (no later chunk, and only a chimera search
@@ -3468,7 +3368,6 @@ TM = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
                 continue;
             }
         }
-#endif
         // ---- everybody else: the lane walks its own hits
         uint64_t any = m1 | m2 | m3;
         if (!any) continue;
@@ -3708,20 +3607,12 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
         float inv_w;
         build_peak_lut(plut, inv_w, pm, P);
         // (built once: after remove_matched_peaks the bitmap is a superset of the remaining peaks' bins — still conservative)
-#ifndef SAGE_ION_PREFETCH
-#define SAGE_ION_PREFETCH 0  // 1: the candidates' first ions are requested between the two table builds (A/B: see DESIGN.md 4.3)
-#endif
-        float first0 = 0.f, first1 = 0.f, first2 = 0.f, first3 = 0.f;
         if (round == 0 && valid) {
             // ions per kind = peptide length - 1 (ion_series.rs:68-85; the ion table holds n_kinds * (L - 1) values per peptide): from
             // the peptide's record, not as (ion_off[pep + 1] - ion_off[pep]) / n_kinds — a 64-bit division per candidate
             const uint32_t plen = pep_rec & 0xFFFFu;
             lm1 = db.n_kinds && plen ? plen - 1u : 0u;
             R.meta[lane] = make_uint2(pep_rec, __float_as_uint(pep_mass));  // (for the Feature record of a reporting lane)
-            if (SAGE_ION_PREFETCH && lm1 && nfz) {
-                const float* __restrict__ q = db.ions + ion_base;  // (padded by 8: harmless past a short candidate's end)
-                first0 = q[0]; first1 = q[1]; first2 = q[2]; first3 = q[3];
-            }
         }
         if (round == 0) build_peak_bitmap(pbm, pm, P, sc.pbm_reach);
         lds_sync();
@@ -3735,7 +3626,8 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
             uint32_t longest = SAGE_N_ITEMS;
             for (int o = 32; o; o >>= 1) { const uint32_t v = (uint32_t)__shfl_xor((int)longest, o, 64); longest = v > longest ? v : longest; }
             const uint32_t nvalid = (uint32_t)__popcll(__ballot(valid));
-            (void)items; (void)longest; (void)nvalid;  // (slots 5..7 now hold phases)
+            // (slots 5..7 now hold phases.  Nothing reads these, and still the profiling instance's code is not the same without them: they stay)
+            (void)items; (void)longest; (void)nvalid;
         }
         }
         Score s;
@@ -3747,8 +3639,8 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
         s.ppm_difference = 0.0f;
         s.longest_b = s.longest_y = 0;
         pc.mark(5);  // (... the peak table and the bitmap)
-        score_candidates<PC, false, FAST, SAGE_FLAT_GENERAL || !CHIMERA>(db, sc, pbm, plut, pm, pi, P, inv_w, valid, ion_base, lm1, nfz, any_fz2, any_fz3, nterm_mask, sym_tol,
-                                          s, pc, SAGE_ION_PREFETCH && round == 0, first0, first1, first2, first3, !CHIMERA || !sc.chimera);
+        score_candidates<PC, false, FAST, !CHIMERA>(db, sc, pbm, plut, pm, pi, P, inv_w, valid, ion_base, lm1, nfz, any_fz2, any_fz3, nterm_mask, sym_tol,
+                                                    s, pc, !CHIMERA || !sc.chimera);
         pc.mark(1);  // (... the lanes' own hits)
         // ---- from here on: the arguments through `la`, the spectrum's scalars from R.hdr (see LateArgs) ----
         LateArgs<KA> la(db, sc, b, w, lnfact_table, lnfact_n, out, out_count);
@@ -3888,9 +3780,6 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
                             wh32_init(hp, c ? (c << 16) | lane : 0u, k);
                         }
                         wh32_build(hp, k);
-#ifndef SAGE_TIE_REPLAY_PAR
-#define SAGE_TIE_REPLAY_PAR 1  // the offers' root replacement by all lanes at once (wh32_replace_root with its per-lane path masks)
-#endif
                         const HeapPath path = heap_path_of_lane();
                         for (uint32_t base = k; base < potential; base += WAVE) {
                             const uint32_t i = base + lane;
@@ -3901,8 +3790,7 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
                                 const uint32_t bit = (uint32_t)__ffsll((long long)mask) - 1;
                                 mask &= mask - 1;
                                 const uint32_t vv = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)__builtin_amdgcn_readfirstlane(bit));
-                                if (SAGE_TIE_REPLAY_PAR) wh32_offer_par(hp, k, vv, path);
-                                else wh32_offer(hp, k, vv);
+                                wh32_offer_par(hp, k, vv, path);  // (the root replacement by all lanes at once: wh32_replace_root with its per-lane path masks)
                             }
                         }
                         hl = hp.h;
@@ -4206,7 +4094,6 @@ __global__ __launch_bounds__(64) SAGE_RESCORE_WAVES_ATTR void rescore_kernel(Res
     extern __shared__ __align__(16) unsigned char smem[];
     const uint32_t lane = lane_id();
     if (blockIdx.x >= b.n) return;
-    staggered_start(blockIdx.x);
     uint32_t n_batch = b.n;
     if (b.n_dev) {  // retry pass: device-side count
         n_batch = *b.n_dev < n_batch ? *b.n_dev : n_batch;
@@ -4229,12 +4116,10 @@ __global__ __launch_bounds__(64) SAGE_RESCORE_WAVES_ATTR void rescore_kernel(Res
     const uint32_t tot_m = w.totals[2 * spec], tot_s = w.totals[2 * spec + 1];
     const uint64_t p0 = b.sched ? ((uint64_t)uni(rec.w) << 32) | uni(rec.z) : b.peak_off[spec];
     const uint32_t P = b.sched ? uni(rec.y) : (uint32_t)(b.peak_off[spec + 1] - p0);
-#ifndef SAGE_EARLY_PEAKS
-#define SAGE_EARLY_PEAKS 1  // with schedule records: the first 192 peaks requested HERE, in front of the branches on the status
-#endif
+    // With schedule records: the first 192 peaks requested HERE, in front of the branches on the status
     // (the compiler does not move a load above the early returns below, so the peaks used to wait for the status to arrive)
     float em0 = 0.f, em1 = 0.f, em2 = 0.f, ei0 = 0.f, ei1 = 0.f, ei2 = 0.f;
-    const bool early = SAGE_EARLY_PEAKS && b.sched != nullptr;
+    const bool early = b.sched != nullptr;
     if (early) {
         const float* __restrict__ gm = b.masses + p0;
         const float* __restrict__ gi = b.intensities + p0;

@@ -5,7 +5,7 @@ route wherever its bytes fit (16384) and the per-lane filter alone (8192).
 
 The flat route belongs to the instance without chimera rounds (and to rescore_big_kernel's short-list instance); the general
 instance — chimera searches, SAGE_HIP_RESCORE_GENERAL=1 — keeps to the per-lane filter under every setting (kernels.hip:
-SAGE_FLAT_GENERAL), and must give the same records.
+rescore_spectrum instantiates score_candidates with FLAT = !CHIMERA), and must give the same records.
 
 The cases cannot pass vacuously: the counters of the profiling instance (SAGE_HIP_PHASE_CLOCKS=1, sage_hip_debug_filter_counters)
 must show flat chunks and trips where the route is meant to be taken, none with 8192, and fewer flat trips than the per-lane
