@@ -1125,10 +1125,12 @@ __global__ __launch_bounds__(RB) void row_mean_kernel(double* __restrict__ mat, 
                                                       double* __restrict__ mean_rts) {
     const uint32_t r = blockIdx.x * RB + threadIdx.x;
     if (r >= n_rows) return;
+    // every file that SAW the peptide counts (:70-75), also when its entry is a NaN (0 / 0 with max_rt == 0, a NaN rt): the mean
+    // is then NaN and the row is dropped.  A file that did not see it still holds the all-ones fill, which no division produces.
     double sum = 0.0, len = 0.0;
     for (uint32_t k = 0; k < n_files; ++k) {
         const double v = mat[(uint64_t)r * n_files + k];
-        if (v == v) {
+        if (__double_as_longlong(v) != -1ll) {
             sum += v;
             len += 1.0;
         }
