@@ -334,6 +334,10 @@ int sage_hip_debug_prune_counters(SageScorer* scorer, unsigned long long* out4);
  * chunks that took the flat route (ions dealt to all lanes), [1] their trips of 8 ions, [2] the trips of 4 ions the per-lane
  * filter would have made of those chunks, [3] the trips of 4 ions of the chunks that took the per-lane route. */
 int sage_hip_debug_filter_counters(SageScorer* scorer, unsigned long long* out4);
+/* Debug aid, same condition: the cooperative path of the rescoring kernels (a candidate with many hits in a 64-ion chunk is matched
+ * by the whole wavefront) since the scorer was created. out2[0] chunks of candidates taken that way, [1] the (ion, fragment charge)
+ * matches added up for them. */
+int sage_hip_debug_heavy_counters(SageScorer* scorer, unsigned long long* out2);
 
 /* ---- post-search rescoring --------------------------------------------------------------
  * The step that consumes the Feature records of ALL searched files (sage-cli runner.rs:536-541):

@@ -2354,6 +2354,19 @@ int sage_hip_debug_filter_counters(SageScorer* s, unsigned long long* out4) {
     return SAGE_HIP_OK;
 }
 
+// debugging aid: the cooperative path behind the prune (kernels.hip: DBG_HEAVY_*) — chunks of heavy candidates the wavefront took
+// together, and the (ion, charge) matches it added up for them
+int sage_hip_debug_heavy_counters(SageScorer* s, unsigned long long* out2) {
+    if (!s || !out2) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+    if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
+    std::vector<unsigned long long> all((size_t)DBG_BLOCKS * DBG_PRUNE_WORDS);
+    HIP_TRY(hipMemcpy(all.data(), s->dbg.p + (size_t)DBG_BLOCKS * 32, all.size() * 8, hipMemcpyDeviceToHost));
+    out2[0] = out2[1] = 0;
+    for (size_t b = 0; b < DBG_BLOCKS; b++)
+        for (uint32_t k = 0; k < 2; k++) out2[k] += all[b * DBG_PRUNE_WORDS + 8 + k];
+    return SAGE_HIP_OK;
+}
+
 int sage_hip_host_alloc(uint64_t bytes, void** out) {
     if (!out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
     HIP_TRY(hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault));

@@ -421,6 +421,69 @@ SAGE_HD void run_matched_packed(uint64_t& r, uint32_t index) {
 }
 SAGE_HD uint32_t run_longest_packed(uint64_t r) { return (uint32_t)(r >> 42); }
 
+// The same update for MANY matches at once: `S` has bit t set where ion idx0 + t matched, and the state afterwards is what
+// run_matched_packed(r, idx0 + t) for every set bit t in ascending order leaves (an ion matched at several fragment charges calls
+// it several times: `last == index` returns, so once per ion is the same).  What the sequence implies:
+//   - only the FIRST set bit can be ignored — when it is `last` (next - 1, or the fresh state's 0): after any call, ignored or
+//     not, `last` is that call's index, below every later one;
+//   - the first run of consecutive bits behind it extends the carried length iff next == its first index, else it starts at 1;
+//   - longest = max(carried, that first run, the longest run of set bits in the rest) — `x &= x << 1` until nothing is left;
+//   - next / length are those of the last run; an empty S leaves r alone.
+// The cooperative path of kernels.hip: score_candidates takes a heavy candidate's runs from its hit ballots this way (wave-uniform,
+// a handful of scalar instructions per run instead of a dozen per match).  tests/test_run_mask_emulation.py holds both widths to the
+// sequential form, exhaustively below 2^16.
+template <uint32_t BITS, class R>
+SAGE_HD void run_matched_mask_fields(R& r, uint64_t S, uint32_t idx0) {
+    constexpr uint32_t FIELD = (1u << BITS) - 1u;
+    if (!S) return;
+    const uint32_t next = (uint32_t)r & FIELD, length = (uint32_t)(r >> BITS) & FIELD;
+    uint32_t longest = (uint32_t)(r >> (2u * BITS));
+    if ((next ? next - 1u : 0u) == idx0 + (uint32_t)__builtin_ctzll(S)) {  // self.last == index
+        S &= S - 1ull;
+        if (!S) return;
+    }
+    const uint32_t t0 = (uint32_t)__builtin_ctzll(S);
+    const uint64_t from_t0 = S >> t0;
+    const uint32_t n0 = ~from_t0 ? (uint32_t)__builtin_ctzll(~from_t0) : 64u;  // the first run: bits t0 .. t0 + n0 - 1
+    uint32_t nl = next == idx0 + t0 ? length + n0 : n0, end = t0 + n0;
+    if (nl > longest) longest = nl;
+    const uint64_t rest = end >= 64u ? 0ull : S & (~0ull << end);
+    if (rest) {
+        uint32_t best = 0;
+        for (uint64_t x = rest; x; x &= x << 1) best++;  // (the longest run of set bits)
+        if (best > longest) longest = best;
+        const uint32_t lz = (uint32_t)__builtin_clzll(rest);
+        const uint64_t from_top = ~(rest << lz);
+        nl = from_top ? (uint32_t)__builtin_clzll(from_top) : 64u;  // the last run: nl bits down from bit 63 - lz
+        end = 64u - lz;
+    }
+    r = (R)(idx0 + end) | ((R)nl << BITS) | ((R)longest << (2u * BITS));
+}
+SAGE_HD void run_matched_mask(uint32_t& r, uint64_t S, uint32_t idx0) { run_matched_mask_fields<10>(r, S, idx0); }
+SAGE_HD void run_matched_mask(uint64_t& r, uint64_t S, uint32_t idx0) { run_matched_mask_fields<21>(r, S, idx0); }
+
+// The KIND SEGMENTS of a 64-ion chunk: bit t of the chunk at ion j0 is ion j0 + t of a table of `lm1` ions per kind, so the chunk
+// falls into bit ranges [lo, lo + len) of one kind each — the first may have begun in the previous chunk (idx0 = j0 mod lm1), the
+// others start at index 0; lm1 == 1 gives one-bit segments.  kind_seg_first / kind_seg_next walk them in order (no division: j0
+// is a few kinds at most); a caller stops when no bit of its masks is left, which happens before `kind` reaches the table's
+// number of kinds, since the masks reach no further than the candidate's ions.  Held to the `while (idx >= lm1)` walk of every
+// ion by tests/test_run_mask_emulation.py.
+struct KindSeg {
+    uint32_t lo, len, idx0, kind;
+};
+SAGE_HD KindSeg kind_seg_first(uint32_t j0, uint32_t lm1) {
+    KindSeg g = {0u, 0u, j0, 0u};
+    while (g.idx0 >= lm1) { g.idx0 -= lm1; g.kind++; }
+    g.len = lm1 - g.idx0 < 64u ? lm1 - g.idx0 : 64u;
+    return g;
+}
+SAGE_HD KindSeg kind_seg_next(const KindSeg& g, uint32_t lm1) {
+    const uint32_t lo = g.lo + g.len;  // (64: behind the chunk — an empty segment, kind_seg_mask 0)
+    const uint32_t len = lm1 < 64u - lo ? lm1 : 64u - lo;
+    return KindSeg{lo, len, 0u, g.kind + 1u};
+}
+SAGE_HD uint64_t kind_seg_mask(const KindSeg& g) { return g.len >= 64u ? ~0ull : ((1ull << g.len) - 1ull) << (g.lo & 63u); }
+
 // ---- Score (scoring.rs:17-30) -------------------------------------------------------------------
 struct Score {
     uint32_t peptide;

@@ -110,6 +110,9 @@ enum { DBG_PRUNE_CAND = 0, DBG_PRUNE_ITEMS = 1, DBG_PRUNE_EARLY = 2, DBG_PRUNE_M
 // route, their trips of 8 ions, the trips of 4 ions the per-lane filter would have made of them, and the trips of 4 ions of the
 // chunks that took the per-lane route
 enum { DBG_FILTER_FLAT_CHUNKS = 4, DBG_FILTER_FLAT_TRIPS = 5, DBG_FILTER_FLAT_WOULD = 6, DBG_FILTER_LANE_TRIPS = 7 };
+// ... and the cooperative path behind the prune (sage_hip_debug_heavy_counters): the chunks of heavy candidates the wavefront took
+// together, and the (ion, charge) matches it added up for them
+enum { DBG_HEAVY_CHUNKS = 8, DBG_HEAVY_ITEMS = 9 };
 enum { DBG_NARROW_LUT = 26, DBG_NARROW_CELLS = 27, DBG_RESCORE = 28, DBG_TILE_LUT = 29, DBG_TILE_CELLS = 30, DBG_TILE_CAND = 31 };
 struct PhaseClock {
     unsigned long long* slot;
@@ -138,6 +141,12 @@ struct PhaseClock {
             } else {
                 atomicAdd(&prune[DBG_FILTER_LANE_TRIPS], (unsigned long long)lane_trips);
             }
+        }
+    }
+    __device__ __forceinline__ void heavy(uint32_t items) {  // wave-uniform, once per chunk of a heavy candidate
+        if (slot && (threadIdx.x & 63u) == 0) {
+            atomicAdd(&prune[DBG_HEAVY_CHUNKS], 1ull);
+            atomicAdd(&prune[DBG_HEAVY_ITEMS], (unsigned long long)items);
         }
     }
     __device__ __forceinline__ void prune_outcome(bool left_early, bool any_pass) {  // once per scoring round
@@ -175,6 +184,7 @@ struct NoClock {
     __device__ __forceinline__ void pruned(uint64_t, uint32_t) {}
     __device__ __forceinline__ void prune_outcome(bool, bool) {}
     __device__ __forceinline__ void filter_trips(bool, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void heavy(uint32_t) {}
     __device__ __forceinline__ void start(unsigned long long*, uint32_t, uint32_t) {}
     __device__ __forceinline__ void mark(int) {}
     __device__ __forceinline__ void rebase(uint32_t) {}
@@ -3222,7 +3232,8 @@ __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevS
                 hc = 0u;
             }
         }
-        uint64_t bigs = (sc.dbg_flags & 32u) ? 0ull : __ballot(hc > COOP_MIN_HITS);  // (SAGE_HIP_DEBUG_FLAGS=32: tests switch it off)
+        // (SAGE_HIP_DEBUG_FLAGS=32: tests switch it off; 32768: tests take a lane from its first hit)
+        uint64_t bigs = (sc.dbg_flags & 32u) ? 0ull : __ballot(hc > ((sc.dbg_flags & 32768u) ? 0u : COOP_MIN_HITS));
         if ((uint32_t)__popcll(bigs) > COOP_MAX_LANES && !(sc.dbg_flags & 64u)) bigs = 0ull;  // (64: tests take every heavy lane)
         while (bigs) {
             const uint32_t L = (uint32_t)__ffsll((long long)bigs) - 1;
@@ -3259,24 +3270,30 @@ TM = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
             uint32_t u_mm = (uint32_t)__builtin_amdgcn_readlane((int)mm, (int)L);
             RunReg u_b = lane_run(b_run, L);
             RunReg u_y = lane_run(y_run, L);
+            // Counts and runs come from the ballots, a kind segment at a time (core.h: kind_seg_first ..., run_matched_mask — pure
+            // functions of K1 / K2 / K3 and the candidate's length); what is left per match is its two readlanes and its two
+            // additions, on the reference's operands in the reference's (ion, charge) order.
             uint64_t anyK = K1 | K2 | K3;
-            while (anyK) {
-                const uint32_t bit = (uint32_t)__ffsll((long long)anyK) - 1;
-                anyK &= anyK - 1;
-                uint32_t kind_i = 0, idx = j0 + bit;
-                while (idx >= lm1_L) { idx -= lm1_L; kind_i++; }
-                const bool nterm = (nterm_mask >> kind_i) & 1u;
-#define SAGE_COOP_ADD(K, IT, TM)                                                   \
-    if ((K >> bit) & 1ull) {                                                       \
-        const float it = lane_valuef(IT, bit), tm = lane_valuef(TM, bit);          \
-        u_pp += tm;                                                                \
-        if (nterm) { u_mm += 1u; u_sb += it; run_matched_packed(u_b, idx); }       \
-        else       { u_mm += 0x10000u; u_sy += it; run_matched_packed(u_y, idx); } \
-    }
-                SAGE_COOP_ADD(K1, it1, tm1)
-                SAGE_COOP_ADD(K2, it2, tm2)
-                SAGE_COOP_ADD(K3, it3, tm3)
-#undef SAGE_COOP_ADD
+            if (pc.slot) pc.heavy((uint32_t)(__popcll(K1) + __popcll(K2) + __popcll(K3)));
+            for (KindSeg g = kind_seg_first(j0, lm1_L); anyK && g.lo < 64u; g = kind_seg_next(g, lm1_L)) {
+                const uint64_t seg = kind_seg_mask(g);
+                uint64_t S = anyK & seg;
+                if (!S) continue;
+                anyK ^= S;
+                const bool nterm = (nterm_mask >> g.kind) & 1u;
+                u_mm += (uint32_t)(__popcll(K1 & seg) + __popcll(K2 & seg) + __popcll(K3 & seg)) << (nterm ? 0u : 16u);
+                if (nterm) run_matched_mask(u_b, S >> g.lo, g.idx0);
+                else run_matched_mask(u_y, S >> g.lo, g.idx0);
+                float acc = nterm ? u_sb : u_sy;
+                do {
+                    const uint32_t bit = (uint32_t)__builtin_ctzll(S);
+                    S &= S - 1ull;
+                    if ((K1 >> bit) & 1ull) { acc += lane_valuef(it1, bit); u_pp += lane_valuef(tm1, bit); }
+                    if ((K2 >> bit) & 1ull) { acc += lane_valuef(it2, bit); u_pp += lane_valuef(tm2, bit); }
+                    if ((K3 >> bit) & 1ull) { acc += lane_valuef(it3, bit); u_pp += lane_valuef(tm3, bit); }
+                } while (S);
+                if (nterm) u_sb = acc;
+                else u_sy = acc;
             }
             if (lane == L) {
                 s.summed_b = u_sb; s.summed_y = u_sy; s.ppm_difference = u_pp;
