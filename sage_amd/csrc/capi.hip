@@ -60,12 +60,18 @@ T* carve(unsigned char*& cur, size_t count) {  // next 64-byte aligned array of 
 
 }  // namespace
 
+static uint64_t next_db_serial() {
+    static std::atomic<uint64_t> serial{0};
+    return ++serial;
+}
+
 struct SageHostDb {
     HostDb db;
 };
 
 struct SageDeviceDb {
     int device = 0;
+    uint64_t serial = next_db_serial();  // never reused: what a batch's stored precursor windows name their index by (WindowKey)
     DevBuf<float> pep_mono;
     DevBuf<uint32_t> pep_lut;  // position table of pep_mono (DevDbView::pep_lut)
     DevBuf<float> ions;
@@ -142,6 +148,7 @@ struct SageDeviceBatch {
     DevBuf<uint32_t> file_id, order, sort_a, sort_b, sort_idx;
     DevBuf<uint8_t> sort_tmp;
     DevBuf<uint4> sched;     // DevBatchView::sched (SAGE_HIP_NO_SCHED=1: not built — the kernels go through `order`)
+    WindowKey win_key{};     // resident batches: what the windows in the records' third uint4 were computed from (DevBatchView::sched_key)
     DevBuf<uint8_t> meta;    // streaming pipeline: the per-spectrum arrays in one block, the image of the staging block (one copy)
     uint32_t widest = 0xFFFFFFFFu;  // candidate slots of the batch's widest precursor window (exact_window_check; else unknown)
     bool maybe_wide = true;  // some precursor window may exceed the narrow kernel's LDS counters (estimated at upload; a wrong
@@ -1146,7 +1153,7 @@ static int check_match_counters(const SageScorer* s, uint32_t fzcap) {
 //     the staging block (copied by a few host threads).
 // The caller must have waited for d->up_done before (the staging block is being rewritten).  `probe`: narrow-kernel variant.
 static int stage_and_upload(SageScorer* s, SageDeviceBatch* d, const SageSpectrumBatch* b, uint32_t c0, uint32_t c1, bool peaks_locked,
-                            const WindowEstimate& est, hipStream_t up) {
+                            const WindowEstimate& est, hipStream_t up, uint32_t sched_stride = SCHED_RECORD) {
     const uint32_t probe = est.probe;
     d->maybe_wide = est.maybe_wide;
     const uint32_t n = c1 - c0;
@@ -1164,7 +1171,7 @@ static int stage_and_upload(SageScorer* s, SageDeviceBatch* d, const SageSpectru
     const size_t sort_bytes = schedule_temp_bytes(n);
     HIP_TRY(d->sort_tmp.reserve(sort_bytes));
     const bool use_sched = !getenv("SAGE_HIP_NO_SCHED");
-    if (use_sched) { HIP_TRY(d->sched.reserve(2 * (size_t)n)); }
+    if (use_sched) { HIP_TRY(d->sched.reserve((size_t)sched_stride * n)); }
     const bool has_kind = has_iso && s->iso_kind != nullptr;
     const size_t small = ((size_t)n + 1) * 8 + (size_t)n * (4 * 7 + 1 + (has_kind ? 1 : 0)) + 64 * 13;
     HIP_TRY(d->stage.reserve(small + (peaks_locked ? 0 : total * 8 + 128)));
@@ -1240,7 +1247,7 @@ static int stage_and_upload(SageScorer* s, SageDeviceBatch* d, const SageSpectru
         if (use_sched)
             schedule_records_on_device(n, d->order.p, (const uint64_t*)image(h_off), (const float*)image(h_mz), (const uint8_t*)image(h_z),
                                        (const float*)image(h_lo), (const float*)image(h_hi), (const uint8_t*)image(h_kind), d->sched.p,
-                                       s->side_stream);
+                                       sched_stride, s->side_stream);
         HIP_TRY(hipEventRecord(d->sort_done.e, s->side_stream));
         if (total && !peaks_first) {
             HIP_TRY(hipMemcpyAsync(d->masses.p, src_m, total * 4, hipMemcpyHostToDevice, up));
@@ -1268,6 +1275,7 @@ static int stage_and_upload(SageScorer* s, SageDeviceBatch* d, const SageSpectru
     v.file_id = (const uint32_t*)image(h_fid);
     v.order = d->order.p;
     v.sched = use_sched && n ? d->sched.p : nullptr;
+    v.sched_stride = sched_stride;
     v.probe = probe;
     v.pcap = pcap;
     v.fzcap = batch_fzcap(s->params, zmax, any_unknown);
@@ -1288,17 +1296,42 @@ static int check_batch_args(const SageSpectrumBatch* b) {
 // is dense where peptides are dense — e.g. the shard of a rank that owns the light end of the mass axis — and a "maybe" costs the
 // step ten empty launches, the second part's overlap, and a longer host turn-around (round 5: 0.75 against 0.69 ms per 62 500
 // C3 spectra).  The streaming pipeline keeps the estimate (it decides before the spectra are on the device).
+// A device batch may be scored by any handle; the windows in its records hold for a scorer with the uploading handle's index,
+// precursor tolerance, wide_window, isotope-error range, charge range and override only (every other scorer searches: enqueue_compute).
+static WindowKey window_key(const SageScorer* s) {
+    WindowKey k;
+    std::memset(&k, 0, sizeof k);  // (compared as bytes)
+    k.db_serial = s->db->serial;
+    k.precursor_tol.kind = s->dev.precursor_tol.kind;
+    k.precursor_tol.lo = s->dev.precursor_tol.lo;
+    k.precursor_tol.hi = s->dev.precursor_tol.hi;
+    k.wide_window = s->dev.wide_window;
+    k.min_precursor_charge = s->dev.min_precursor_charge;
+    k.max_precursor_charge = s->dev.max_precursor_charge;
+    k.override_precursor_charge = s->dev.override_precursor_charge;
+    k.min_isotope_err = s->dev.min_isotope_err;
+    k.max_isotope_err = s->dev.max_isotope_err;
+    return k;
+}
 static int exact_window_check(SageScorer* s, SageDeviceBatch* d, hipStream_t st) {
-    if (getenv("SAGE_HIP_ASSUME_NARROW") || d->n == 0) return SAGE_HIP_OK;  // (tests force the estimate's answer)
+    // (tests force the estimate's answer.  The records' third uint4 then stays unwritten — and unread: without a sched_key no
+    // scorer is told that the records hold windows, enqueue_compute)
+    if (getenv("SAGE_HIP_ASSUME_NARROW") || d->n == 0) return SAGE_HIP_OK;
     HIP_TRY(s->win_max.reserve(1));
     HIP_TRY(hipMemsetAsync(s->win_max.p, 0, 4, st));
-    launch_window_max(s->dev, d->view, s->db->view.pep_mono, s->db->view.np, s->win_max.p, st);
+    // (... and the window of every spectrum's first query stays in its schedule record: kernels.hip, window_max_kernel)
+    const bool keep_windows = d->view.sched && d->view.sched_stride == SCHED_RECORD_WINDOW;
+    launch_window_max(s->dev, d->view, s->db->view.pep_mono, s->db->view.np, s->win_max.p, keep_windows ? d->sched.p : nullptr, st);
     HIP_TRY(hipGetLastError());
     uint32_t widest = 0;
     HIP_TRY(hipMemcpyAsync(&widest, s->win_max.p, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     d->maybe_wide = widest > s->dev.wcap;
     d->widest = widest;
+    if (keep_windows) {
+        d->win_key = window_key(s);
+        d->view.sched_key = &d->win_key;
+    }
     return SAGE_HIP_OK;
 }
 
@@ -1314,7 +1347,7 @@ static int batch_upload(SageScorer* s, const SageSpectrumBatch* b, const uint8_t
     HIP_TRY(d->up_done.create(false));
     const uint32_t n = b->n_spectra;
     const WindowEstimate est = choose_probe(s, n, b->precursor_mz, b->precursor_charge, b->isolation_lo, b->isolation_hi, s->iso_kind);
-    rc = stage_and_upload(s, d.get(), b, 0, n, is_page_locked(b->masses) && is_page_locked(b->intensities), est, s->up_stream);
+    rc = stage_and_upload(s, d.get(), b, 0, n, is_page_locked(b->masses) && is_page_locked(b->intensities), est, s->up_stream, SCHED_RECORD_WINDOW);
     if (rc != SAGE_HIP_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s->up_stream));
     rc = exact_window_check(s, d.get(), s->up_stream);
@@ -1376,9 +1409,9 @@ static int batch_process_upload(SageScorer* s, const SageRawBatch* raw, const ui
                                            d->sort_idx.p, d->order.p, d->sort_tmp.p, sort_bytes, s->stream));
     const bool use_sched = !getenv("SAGE_HIP_NO_SCHED");
     if (use_sched) {
-        HIP_TRY(d->sched.alloc(2 * (size_t)n));
+        HIP_TRY(d->sched.alloc((size_t)SCHED_RECORD_WINDOW * n));
         schedule_records_on_device(n, d->order.p, d->peak_off.p, d->precursor_mz.p, d->charge.p, has_iso ? d->iso_lo.p : nullptr,
-                                   has_iso ? d->iso_hi.p : nullptr, has_kind ? d->iso_kind.p : nullptr, d->sched.p, s->stream);
+                                   has_iso ? d->iso_hi.p : nullptr, has_kind ? d->iso_kind.p : nullptr, d->sched.p, SCHED_RECORD_WINDOW, s->stream);
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     DevBatchView& v = d->view;
@@ -1398,6 +1431,7 @@ static int batch_process_upload(SageScorer* s, const SageRawBatch* raw, const ui
     v.file_id = raw->file_id ? d->file_id.p : nullptr;
     v.order = d->order.p;
     v.sched = use_sched && n ? d->sched.p : nullptr;
+    v.sched_stride = SCHED_RECORD_WINDOW;
     const WindowEstimate est = choose_probe(s, n, raw->precursor_mz, raw->precursor_charge, raw->isolation_lo, raw->isolation_hi, s->iso_kind);
     v.probe = est.probe;
     d->maybe_wide = est.maybe_wide;
@@ -1558,6 +1592,10 @@ static int enqueue_compute(SageScorer* s, const DevBatchView& view_in, OutSet& o
     DevScorer sc = s->dev;
     if (wide && !s->sched_desc_forced) sc.xcd_chunk &= 0x7FFFFFFFu;  // (heaviest-first is the narrow search's default: scorer_init)
     DevBatchView view = view_in;
+    {  // the records' windows are this scorer's only if they were computed from what it would compute them from
+        const WindowKey mine = window_key(s);
+        view.sched_win = view.sched && view.sched_stride == SCHED_RECORD_WINDOW && view.sched_key && std::memcmp(view.sched_key, &mine, sizeof mine) == 0;
+    }
     // (the stream variant of the preliminary kernels keeps a window per (peak, fragment charge) in LDS, the probe variant the peak
     // masses only: a batch of very large spectra is probed whatever the estimate said)
     if (!view.probe && (size_t)view.fzcap * view.pcap * 8 > 48 * 1024) view.probe = 1;
@@ -1624,6 +1662,7 @@ static int enqueue_compute(SageScorer* s, const DevBatchView& view_in, OutSet& o
     o.n = view.n;
     DevBatchView v2 = view;
     v2.sched = nullptr;  // (the retry list is not the schedule)
+    v2.sched_win = 0;
     v2.order = wset.retry.p + list_off;  // filled by the rescoring kernel of the first pass, in no particular order
     v2.n_dev = o.counters.p + CTR_RETRY;
     if (one_launch && ++wset.epoch == 0) wset.epoch = 1;
@@ -1886,7 +1925,7 @@ static int score_resident_locked(SageScorer* s, SageDeviceBatch* b, SageFeature*
             hipStream_t st = wy ? s->way_stream[wy - 1] : s->stream;
             DevBatchView v = b->view;
             v.order += start;
-            if (v.sched) v.sched += 2 * (size_t)start;
+            if (v.sched) v.sched += (size_t)v.sched_stride * start;
             v.n = end - start;
             OutSet& ow = s->outs[wy];
             if (wy == 0 && s->timed) HIP_TRY(hipEventRecord(s->way_begin.e, st));  // (SageTiming::total_ms: first part's start to last part's end)
@@ -1957,7 +1996,7 @@ static int score_resident_locked(SageScorer* s, SageDeviceBatch* b, SageFeature*
                     hipStream_t st = wy ? s->way_stream[wy - 1] : s->stream;
                     DevBatchView v = b->view;
                     v.order += start;
-                    if (v.sched) v.sched += 2 * (size_t)start;
+                    if (v.sched) v.sched += (size_t)v.sched_stride * start;
                     v.n = end - start;
                     uint32_t* const counts_to = (ways > 1) ? count_view : o.out_count.p;
                     rc = enqueue_compute(s, v, ow, true, MODE_SCORE, st, rec, false, start, counts_to, 0, 2);

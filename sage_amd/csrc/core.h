@@ -124,6 +124,36 @@ SAGE_HD int64_t order_key64(double d) {
     return u.i ^ (int64_t)(((uint64_t)(u.i >> 63)) >> 1);
 }
 
+// IndexedDatabase::query (database.rs:402-425) of one precursor window [plo, phi] over the ascending peptide masses: [left, right]
+// candidate slots — the two partition points in the order_key total order, left = a ? a - 1 : 0 — and the [first, end) peptide
+// range after the edge rule of database.rs:526-531.  One thread, two plain binary searches: what a resident batch's upload runs per
+// query (kernels.hip: window_max_kernel) and, wavefront-wide, what query_window finds again.
+struct Window {
+    uint32_t left, right, first, end;
+};
+SAGE_HD Window scalar_query_window(const float* pep_mono, uint32_t np, float plo, float phi) {
+    const int32_t klo = order_key(plo), khi = order_key(phi);
+    uint32_t a = 0, e = np;  // first index with key >= klo
+    while (a < e) {
+        const uint32_t m = a + ((e - a) >> 1);
+        if (order_key(pep_mono[m]) < klo) a = m + 1; else e = m;
+    }
+    Window q;
+    q.left = a ? a - 1 : 0;
+    uint32_t c = q.left;
+    e = np;  // first index with key > khi, from `left` on (an inverted window gives right == left)
+    while (c < e) {
+        const uint32_t m = c + ((e - c) >> 1);
+        if (order_key(pep_mono[m]) <= khi) c = m + 1; else e = m;
+    }
+    q.right = c;
+    q.first = q.left;
+    q.end = q.right;
+    if (q.left < np && !(pep_mono[q.left] >= plo)) q.first = q.left + 1;
+    if (q.right < np && pep_mono[q.right] <= phi) q.end = q.right + 1;
+    return q;
+}
+
 // scoring.rs:239-247 — exclusive upper bound of the fragment charge loop; user < 0 == None
 SAGE_HD uint32_t max_fragment_charge(int user, uint32_t precursor_charge) {
     uint32_t inner = user >= 0 ? (uint32_t)((user + 1) & 0xFF) : precursor_charge;

@@ -127,11 +127,27 @@ struct DevBatchView {
     uint32_t probe;             // narrow kernel variant: 1 = per-peak table lookups (large windows), 0 = peptide-major stream
     uint32_t pcap;              // max peaks per spectrum in this batch
     uint32_t fzcap;             // max (max_fragment_charge - 1) over the charges this batch can use
-    const uint4* sched;         // may be null.  [2 n] what a block needs of the spectrum it scores, IN SCHEDULE ORDER: record b =
+    const uint4* sched;         // may be null.  [sched_stride n] what a block needs of the spectrum it scores, IN SCHEDULE ORDER: record b =
                                 //     {order[b], peaks, peak_off lo, hi}, {charge, precursor m/z, isolation lo, hi (NaN: none)} — one
                                 //     trip to a line its neighbours share instead of order[b] and then five random reads.  The
                                 //     charge word carries (SAGE_TOL_* of the isolation window) ^ SAGE_TOL_DA in bits 8-15: 0 for Da
     const uint8_t* iso_kind;    // may be null (every window Da): SAGE_TOL_* of isolation_lo / hi (MGF `TOLU=ppm`)
+    uint32_t sched_stride;      // uint4 per record of `sched`: SCHED_RECORD, or SCHED_RECORD_WINDOW for a resident batch, whose upload leaves {left, right, first,
+                                //     end} of the spectrum's FIRST precursor-window query (kernels.hip: window_max_kernel) in the third
+    uint32_t sched_win;         // 1: the third uint4 is there AND belongs to the scorer of this launch (capi.hip: WindowKey): the
+                                //     preliminary kernel takes the window from it instead of searching
+    const struct WindowKey* sched_key;  // host only: what the records' windows were computed from (null: no windows)
+};
+// uint4 per schedule record (DevBatchView::sched_stride): the two every record has, and those of a resident batch, whose third
+// holds the window of the spectrum's first precursor-window query
+constexpr uint32_t SCHED_RECORD = 2, SCHED_RECORD_WINDOW = 3;
+// What a precursor window depends on besides the spectrum: a batch's stored windows hold for a scorer with the same key only
+// (a device batch may be scored by any handle).
+struct WindowKey {
+    uint64_t db_serial;  // SageDeviceDb::serial
+    sagecore::Tol precursor_tol;
+    uint32_t wide_window, min_precursor_charge, max_precursor_charge, override_precursor_charge;
+    int min_isotope_err, max_isotope_err;
 };
 
 struct DevWork {  // per-spectrum outputs of the preliminary pass
@@ -275,7 +291,7 @@ int schedule_on_device(uint32_t n, const float* d_precursor_mz, const uint8_t* d
                        uint32_t* d_keys_b, uint32_t* d_idx, uint32_t* d_order, void* d_temp, size_t temp_bytes, void* stream);
 void schedule_records_on_device(uint32_t n, const uint32_t* d_order, const uint64_t* d_peak_off, const float* d_precursor_mz,
                                 const uint8_t* d_charge, const float* d_iso_lo, const float* d_iso_hi, const uint8_t* d_iso_kind,
-                                uint4* d_sched, void* stream);
+                                uint4* d_sched, uint32_t stride, void* stream);
 // process.hip (process_raw_on_device: hip_host.h)
 size_t process_lds_bytes(uint32_t rcap, uint32_t rpow2);
 int process_kernel_prepare(size_t max_lds_bytes);
@@ -299,7 +315,8 @@ struct EpilogueParts {
     uint32_t n;
 };
 void launch_epilogue(const uint32_t* counts, uint32_t n, uint32_t* h_counts, const uint32_t* order, const EpilogueParts& parts, void* stream);
-void launch_window_max(const DevScorer& sc, const DevBatchView& b, const float* pep_mono, uint32_t np, uint32_t* out_max, void* stream);
+void launch_window_max(const DevScorer& sc, const DevBatchView& b, const float* pep_mono, uint32_t np, uint32_t* out_max, uint4* win_out,
+                       void* stream);
 void launch_quick_mark(const DevScorer& sc, const DevBatchView& b, const DevWork& w, uint8_t* keep, void* stream);
 void launch_annotate(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const SageFeature* feats,
                      const uint32_t* counts, const uint64_t* psm_off, const DevFragments& out, void* stream);

@@ -383,15 +383,15 @@ __global__ __launch_bounds__(256) void schedule_keys_kernel(uint32_t n, const fl
 __global__ __launch_bounds__(256) void schedule_records_kernel(uint32_t n, const uint32_t* __restrict__ order, const uint64_t* __restrict__ peak_off,
                                                                const float* __restrict__ precursor_mz, const uint8_t* __restrict__ charge,
                                                                const float* __restrict__ iso_lo, const float* __restrict__ iso_hi,
-                                                               const uint8_t* __restrict__ iso_kind, uint4* __restrict__ sched) {
+                                                               const uint8_t* __restrict__ iso_kind, uint4* __restrict__ sched, uint32_t stride) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
     const uint32_t i = order[k];
     const uint64_t p0 = peak_off[i];
     const uint32_t nan_bits = 0x7FC00000u;
-    sched[2 * (size_t)k] = make_uint4(i, (uint32_t)(peak_off[i + 1] - p0), (uint32_t)p0, (uint32_t)(p0 >> 32));
+    sched[(size_t)stride * k] = make_uint4(i, (uint32_t)(peak_off[i + 1] - p0), (uint32_t)p0, (uint32_t)(p0 >> 32));
     const uint32_t kind_bits = iso_kind ? (uint32_t)(iso_kind[i] ^ 2u) << 8 : 0u;  // (DevBatchView::sched: 0 for Da windows)
-    sched[2 * (size_t)k + 1] = make_uint4(charge[i] | kind_bits, __float_as_uint(precursor_mz[i]), iso_lo && iso_hi ? __float_as_uint(iso_lo[i]) : nan_bits,
+    sched[(size_t)stride * k + 1] = make_uint4(charge[i] | kind_bits, __float_as_uint(precursor_mz[i]), iso_lo && iso_hi ? __float_as_uint(iso_lo[i]) : nan_bits,
                                           iso_lo && iso_hi ? __float_as_uint(iso_hi[i]) : nan_bits);
 }
 }  // namespace
@@ -415,10 +415,10 @@ int schedule_on_device(uint32_t n, const float* d_precursor_mz, const uint8_t* d
 
 void schedule_records_on_device(uint32_t n, const uint32_t* d_order, const uint64_t* d_peak_off, const float* d_precursor_mz,
                                 const uint8_t* d_charge, const float* d_iso_lo, const float* d_iso_hi, const uint8_t* d_iso_kind,
-                                uint4* d_sched, void* stream) {
+                                uint4* d_sched, uint32_t stride, void* stream) {
     if (n == 0) return;
     hipLaunchKernelGGL(schedule_records_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, d_order, d_peak_off,
-                       d_precursor_mz, d_charge, d_iso_lo, d_iso_hi, d_iso_kind, d_sched);
+                       d_precursor_mz, d_charge, d_iso_lo, d_iso_hi, d_iso_kind, d_sched, stride);
 }
 
 }  // namespace sagehip

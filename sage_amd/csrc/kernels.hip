@@ -84,6 +84,7 @@ namespace {
 #endif
 
 constexpr uint32_t WAVE = 64;
+constexpr uint32_t NO_WINDOW = 0xFFFFFFFFu;
 // LDS words the in-line tie replay of rescore_spectrum may overwrite: the peak bitmap and the peak table behind it (both dead by
 // then).  A row of window counts holds (potential + 1) / 2 words, potential <= wcap: capi.hip switches fast ties off for a wcap
 // whose rows would not fit, and the kernel checks every row again.
@@ -658,9 +659,13 @@ struct SpecInfo {
     uint32_t P, z0, z1, nfz_max;
     float mzp;
     Tol iso_tol;
+    Window win;    // the spectrum's FIRST precursor-window query (charge z0, the first isotope error), from the schedule record
+    bool has_win;  // ... when the record carries it (DevBatchView::sched_win); else prelim_spectrum searches (query_window)
 };
 __device__ __forceinline__ SpecInfo load_spec(const DevScorer& sc, const DevBatchView& b, uint32_t spec) {
     SpecInfo s;
+    s.win = Window{0u, 0u, 0u, 0u};
+    s.has_win = false;
     s.p0 = uni64(b.peak_off[spec]);
     s.P = (uint32_t)(uni64(b.peak_off[spec + 1]) - s.p0);
     const uint32_t zraw = uni(b.precursor_charge[spec]);
@@ -694,9 +699,14 @@ __device__ __forceinline__ SpecInfo load_spec(const DevScorer& sc, const DevBatc
 // The same from the batch's schedule records (DevBatchView::sched): record `pos` holds what load_spec reads of spectrum order[pos] — one
 // trip, to a line the neighbouring blocks of the XCD share, instead of order[pos] and then five reads at random places.
 __device__ __forceinline__ SpecInfo load_spec_sched(const DevScorer& sc, const DevBatchView& b, uint32_t pos, uint32_t& spec) {
-    const uint4 r0 = b.sched[2 * (size_t)pos], r1 = b.sched[2 * (size_t)pos + 1];
+    const uint4* __restrict__ rec = b.sched + (size_t)b.sched_stride * pos;
+    const uint4 r0 = rec[0], r1 = rec[1];
+    uint4 r2 = make_uint4(NO_WINDOW, 0u, 0u, 0u);
+    if (b.sched_win) r2 = rec[2];  // (the same trip: the three reads are in flight together)
     spec = uni(r0.x);
     SpecInfo s;
+    s.win = Window{uni(r2.x), uni(r2.y), uni(r2.z), uni(r2.w)};
+    s.has_win = s.win.left != NO_WINDOW;  // (NO_WINDOW: a spectrum without a query — z0 > z1)
     s.p0 = ((uint64_t)uni(r0.w) << 32) | uni(r0.z);
     s.P = uni(r0.y);
     const uint32_t zraw = uni(r1.x) & 0xFFu;
@@ -727,9 +737,7 @@ __device__ __forceinline__ SpecInfo load_spec_sched(const DevScorer& sc, const D
 
 // IndexedDatabase::query (database.rs:402-425) by one wavefront: [left, right] candidate slots and the
 // [first, end) peptide range after the edge rule of database.rs:526-531
-struct Window {
-    uint32_t left, right, first, end;
-};
+// (Window: core.h, next to the one-thread form of the same search — scalar_query_window)
 // `lut` (DevDbView::pep_lut, may be null): the table of pep_mono's partition points at multiples of 1 / inv_w.  Both bounds of an
 // ordinary window (0 <= plo <= phi inside the table) then lie in the one or two bins the table brackets them with: two scalar
 // reads and one wave-wide read each, the same partition points as the full search finds (which everything else still takes).
@@ -859,7 +867,6 @@ __device__ __forceinline__ bool fast_select(const PrelimLds& L, const Counters& 
 constexpr uint32_t PROBE_PER_LANE = SAGE_PROBE_PER_LANE;
 constexpr uint32_t PROBE_BATCH = PROBE_PER_LANE * 64;
 constexpr uint32_t PROBE_CELLS = SAGE_PROBE_CELLS;
-constexpr uint32_t NO_WINDOW = 0xFFFFFFFFu;
 static_assert(PROBE_BATCH == PROBE_BATCH_WORDS && PROBE_BATCH <= 512, "the run table's layout (carve_prelim) is the kernel's");
 static_assert(PROBE_TCS_WORDS - PROBE_BATCH <= WAVE, "one sentinel per lane pads the run starts");
 // ---- arguments where they are used ---------------------------------------------------------------------------------------------
@@ -942,15 +949,24 @@ __device__ __forceinline__ PrelimResult prelim_spectrum(const DevDbView& db_, co
             if (lane < P) pk0 = masses[lane];
             if (lane + WAVE < P) pk1 = masses[lane + WAVE];
             if (lane + 2 * WAVE < P) pk2 = masses[lane + 2 * WAVE];
-            if (si.z0 <= si.z1) {  // (the same expressions as in the query loops below)
-                const bool fold0 = av.sc().min_isotope_err != av.sc().max_isotope_err;
-                iso_first = fold0 ? av.sc().min_isotope_err : 0;
+        }
+        if (si.z0 <= si.z1) {  // (the same expressions as in the query loops below)
+            const bool fold0 = av.sc().min_isotope_err != av.sc().max_isotope_err;
+            iso_first = fold0 ? av.sc().min_isotope_err : 0;
+            // A resident batch's record holds this window, searched once at its upload: no trip in front of the peaks' staging.
+            // (SAGE_HIP_DEBUG_FLAGS=65536: search anyway — the route the tests compare with)
+            if (si.has_win && !(av.sc().dbg_flags & 65536u)) {
+                q_first = si.win;
+                have_first = true;
+            } else if (PROBE) {
                 const float precursor_mass = si.mzp * (float)si.z0;
                 const Tol ptol = av.sc().wide_window ? tol_scaled(si.iso_tol, (float)si.z0) : SAGE_LOAD_TOL(av.sc().precursor_tol);
                 const float center = precursor_mass - (float)iso_first * NEUTRON;  // scoring.rs:344
                 q_first = query_window<true>(av.db().pep_mono, av.db().np, ptol, center, av.db().pep_lut, av.db().pep_lut_bins, av.db().pep_lut_inv_w);
                 have_first = true;
             }
+        }
+        if (PROBE) {
             if (lane < P) L.win_lo[lane] = pk0;
             if (lane + WAVE < P) L.win_lo[lane + WAVE] = pk1;
             if (lane + 2 * WAVE < P) L.win_lo[lane + 2 * WAVE] = pk2;
@@ -4120,7 +4136,7 @@ __global__ __launch_bounds__(64) SAGE_RESCORE_WAVES_ATTR void rescore_kernel(Res
     // (with schedule records — DevBatchView::sched — the block's spectrum and its peak range come in one trip, and the peaks are
     // requested beside the status and the list instead of behind peak_off[spec])
     uint4 rec = make_uint4(0u, 0u, 0u, 0u);
-    if (b.sched) rec = b.sched[2 * (size_t)pos];
+    if (b.sched) rec = b.sched[(size_t)b.sched_stride * pos];
     const uint32_t spec = b.sched ? uni(rec.x) : b.order ? b.order[pos] : pos;
     // Everything that hangs on `spec` alone is requested together, ahead of the first use: the spectrum's status, the whole row
     // of its preliminary list (unconditionally — the array is padded by a wavefront — so that the load does not wait for the
@@ -4685,13 +4701,17 @@ void launch_epilogue(const uint32_t* counts, uint32_t n, uint32_t* h_counts, con
 }
 // The largest candidate-slot count (scoring.rs:351: right - left + 1 of IndexedDatabase::query, database.rs:402-425) any
 // precursor-window query of the batch will see — what decides whether the large-window kernels have to be launched at all
-// (slots beyond DevScorer::wcap).  One THREAD per spectrum, two plain binary searches over the peptide masses per query: the
-// same partition points in the same total order as query_window's.
+// (slots beyond DevScorer::wcap).  One THREAD per schedule position, two plain binary searches over the peptide masses per query
+// (core.h: scalar_query_window): the same partition points in the same total order as query_window's.
+// `win_out` (may be null): the third uint4 of the batch's schedule records.  The window of the spectrum's FIRST query — the one
+// prelim_spectrum wants ahead of everything else — stays there, so that no scoring step searches it again (NO_WINDOW: the spectrum
+// has no query).  Same expressions, same translation unit, same bits as prelim_spectrum's.
 __global__ __launch_bounds__(256) void window_max_kernel(DevScorer sc, DevBatchView b, const float* __restrict__ pep_mono, uint32_t np,
-                                                         uint32_t* __restrict__ out_max) {
-    const uint32_t spec = blockIdx.x * blockDim.x + threadIdx.x;
+                                                         uint32_t* __restrict__ out_max, uint4* __restrict__ win_out, uint32_t win_stride) {
+    const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t widest = 0;
-    if (spec < b.n) {
+    if (pos < b.n) {
+        const uint32_t spec = b.order ? b.order[pos] : pos;
         const uint32_t zraw = b.precursor_charge[spec];
         const bool ranged = sc.wide_window || zraw == 0 || sc.override_precursor_charge;  // scoring.rs:423, 437, 442
         const uint32_t z0 = ranged ? sc.min_precursor_charge : zraw, z1 = ranged ? sc.max_precursor_charge : zraw;
@@ -4707,35 +4727,33 @@ __global__ __launch_bounds__(256) void window_max_kernel(DevScorer sc, DevBatchV
         }
         const bool fold = sc.min_isotope_err != sc.max_isotope_err;
         const int isoA = fold ? sc.min_isotope_err : 0, isoB = fold ? sc.max_isotope_err : 0;
+        Window first{NO_WINDOW, 0u, 0u, 0u};
+        if (win_out && z0 <= z1 && z0 == 0) {  // (a charge range from 0: prelim_spectrum queries it, the maximum below never counted it)
+            float plo, phi;
+            tol_bounds(sc.wide_window ? tol_scaled(iso_tol, 0.0f) : sc.precursor_tol, mzp * 0.0f - (float)isoA * NEUTRON, plo, phi);
+            first = scalar_query_window(pep_mono, np, plo, phi);
+        }
         for (uint32_t z = z0; z <= z1 && z != 0; z++) {
             const Tol ptol = sc.wide_window ? tol_scaled(iso_tol, (float)z) : sc.precursor_tol;
             for (int iso = isoA; iso <= isoB; iso++) {
                 float plo, phi;
                 tol_bounds(ptol, mzp * (float)z - (float)iso * NEUTRON, plo, phi);
-                const int32_t klo = order_key(plo), khi = order_key(phi);
-                uint32_t a = 0, e = np;  // first index with key >= klo
-                while (a < e) {
-                    const uint32_t m = a + ((e - a) >> 1);
-                    if (order_key(pep_mono[m]) < klo) a = m + 1; else e = m;
-                }
-                const uint32_t left = a ? a - 1 : 0;
-                uint32_t c = left;
-                e = np;  // first index with key > khi
-                while (c < e) {
-                    const uint32_t m = c + ((e - c) >> 1);
-                    if (order_key(pep_mono[m]) <= khi) c = m + 1; else e = m;
-                }
-                const uint32_t potential = c - left + 1;  // (right - left + 1; an inverted window gives <= 2)
+                const Window q = scalar_query_window(pep_mono, np, plo, phi);
+                const uint32_t potential = q.right - q.left + 1;  // (an inverted window gives 1)
                 widest = potential > widest ? potential : widest;
+                if (z == z0 && iso == isoA) first = q;
             }
         }
+        if (win_out) win_out[(size_t)win_stride * pos + 2] = make_uint4(first.left, first.right, first.first, first.end);
     }
     widest = (uint32_t)wave_max_i64((long long)widest);
     if ((threadIdx.x & 63u) == 0 && widest) atomicMax(out_max, widest);
 }
-void launch_window_max(const DevScorer& sc, const DevBatchView& b, const float* pep_mono, uint32_t np, uint32_t* out_max, void* stream) {
+void launch_window_max(const DevScorer& sc, const DevBatchView& b, const float* pep_mono, uint32_t np, uint32_t* out_max, uint4* win_out,
+                       void* stream) {
     if (b.n == 0) return;
-    hipLaunchKernelGGL(window_max_kernel, dim3((b.n + 255) / 256), dim3(256), 0, (hipStream_t)stream, sc, b, pep_mono, np, out_max);
+    hipLaunchKernelGGL(window_max_kernel, dim3((b.n + 255) / 256), dim3(256), 0, (hipStream_t)stream, sc, b, pep_mono, np, out_max,
+                       win_out, b.sched_stride);
 }
 void launch_quick_mark(const DevScorer& sc, const DevBatchView& b, const DevWork& w, uint8_t* keep, void* stream) {
     if (b.n == 0) return;
