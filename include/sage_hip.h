@@ -338,6 +338,10 @@ int sage_hip_debug_filter_counters(SageScorer* scorer, unsigned long long* out4)
  * by the whole wavefront) since the scorer was created. out2[0] chunks of candidates taken that way, [1] the (ion, fragment charge)
  * matches added up for them. */
 int sage_hip_debug_heavy_counters(SageScorer* scorer, unsigned long long* out2);
+/* Debug aid (no condition): *out = 1 if the first pass of the scorer's last scoring step handed its preliminary lists to the
+ * rescoring kernel in rows by schedule position, 0 if in the arrays indexed by spectrum (SAGE_HIP_DEBUG_FLAGS=131072 at scorer
+ * creation forces the latter; so does every step that is not the plain narrow search with schedule records). */
+int sage_hip_debug_handover_route(SageScorer* scorer, uint32_t* out);
 
 /* ---- post-search rescoring --------------------------------------------------------------
  * The step that consumes the Feature records of ALL searched files (sage-cli runner.rs:536-541):

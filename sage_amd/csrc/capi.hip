@@ -108,9 +108,12 @@ struct WorkSet {
     DevBuf<uint32_t> arena;
     // cheap ties (device_types.h: DevWork::cnt_store): the window counts of every narrow single-query spectrum
     DevBuf<uint32_t> cnt_store;
+    // the hand-over rows of a narrow first pass (device_types.h: DevWork::hand), one per schedule position
+    DevBuf<uint64_t> hand;
     DevBuf<float> winbuf;   // tile_count_wing_kernel's windows (DevWork::winbuf), when a batch needs them
     DevBuf<unsigned char> hugebuf;  // the wide-list kernels' lists in global memory (DevWork::hugebuf), when a configuration needs them
     uint32_t cap_tie = 0;
+    uint32_t cap_hand = 0;  // rows `hand` holds
     uint32_t cap_n = 0;     // spectra the narrow-path buffers hold
     uint32_t cap_wide = 0;  // spectra the large-window buffers hold (0 on the second compute lane, always)
 };
@@ -212,6 +215,9 @@ struct SageScorer {
     bool fast_ties = true;      // one reported PSM, no chimera: ties at the top settled by rescore_kernel from stored window counts
                                 // (SAGE_HIP_NO_FAST_TIES=1: every tie through the exact retry pass, as in round 3)
     uint32_t cnt_stride = 0;    // words per spectrum of WorkSet::cnt_store
+    bool hand_rows = true;      // the narrow first pass hands its lists over in schedule order (DevWork::hand) where enqueue_compute
+                                // allows it (SAGE_HIP_DEBUG_FLAGS=131072, read at scorer creation: always by spectrum)
+    bool last_hand = false;     // ... and the last first pass enqueued did (sage_hip_debug_handover_route)
     uint32_t qmax = 1;
     WorkSet ws;                 // the working set (lane 0)
     WorkSet ws2;                // a second one: the streaming pipeline scores two chunks of a narrow batch side by side (lane 1)
@@ -850,6 +856,7 @@ static int scorer_init(SageScorer* sp, SageDeviceDb* db, const SageScorerParams*
     d.wcap = 1024;
     d.dbg_flags = 0;
     if (const char* e = getenv("SAGE_HIP_DEBUG_FLAGS")) d.dbg_flags = (uint32_t)atoi(e);
+    s->hand_rows = (d.dbg_flags & 131072u) == 0u;  // (131072: tests and A/B runs keep the hand-over arrays indexed by spectrum)
     d.prune_min = (d.dbg_flags & 4096u) ? 0u : d.min_matched_peaks;  // (4096: tests and A/B runs switch the rescoring prune off)
     d.rescore_general = 0;
     if (const char* e = getenv("SAGE_HIP_RESCORE_GENERAL")) d.rescore_general = atoi(e) != 0 ? 1u : 0u;
@@ -1480,6 +1487,12 @@ static uint64_t arena_entries_for(const SageScorer* s, uint32_t n) {
     return e;
 }
 
+// The scorer's narrow first pass may hand its lists over in rows by schedule position (DevWork::hand): the production kernels with a
+// list and its header in one row of a word per lane.  (Which launches do: enqueue_compute.)
+static bool hand_rows_possible(const SageScorer* s) {
+    return s->hand_rows && s->dev.kmax <= HAND_LIST_MAX && !s->dev.big_path && !s->fused && !s->one_launch && !s->exact_always;
+}
+
 // The device working set of a launch of n spectra.  `lane`: which of the scorer's two sets (the streaming pipeline's second compute
 // lane never takes the large-window path, so it never owns that path's buffers — the candidate arena alone is 64 KiB per
 // spectrum).  `wide`: the large-window kernels will be launched (lane 0 only).  `st`: the stream the kernels will run on.
@@ -1511,6 +1524,20 @@ static int ensure_work(SageScorer* s, uint32_t n, int lane, bool wide, hipStream
         } else {
             HIP_TRY(e);
             w.cap_tie = n;
+        }
+    }
+    if (!wide && hand_rows_possible(s) && n > w.cap_hand) {
+        // (512 bytes per spectrum.  Like the count rows, the search does not need them: out of memory HERE keeps the arrays by spectrum)
+        const hipError_t e = w.hand.reserve((size_t)n * HAND_ROW_WORDS);
+        if (e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            s->hand_rows = false;
+        } else {
+            HIP_TRY(e);
+            // (zeroed once: a row no kernel of this scorer has written yet reads as an empty list, never as peptide indices)
+            HIP_TRY(hipMemsetAsync(w.hand.p, 0, w.hand.bytes(), st));
+            HIP_TRY(hipStreamSynchronize(st));
+            w.cap_hand = n;
         }
     }
     if (wide && lane == 0 && n > w.cap_wide) {
@@ -1675,6 +1702,14 @@ static int enqueue_compute(SageScorer* s, const DevBatchView& view_in, OutSet& o
     if (fast_ties) {  // (each part of a step owns the rows / entries [list_off, list_off + n) of these arrays)
         w1.cnt_store = wset.cnt_store.p + (size_t)list_off * s->cnt_stride;  // (rows by schedule position within the part)
     }
+    // The first pass's hand-over in schedule order (DevWork::hand), one trip earlier for rescore_kernel: where the pass is
+    // prelim_kernel then rescore_kernel and nothing else — no large-window kernels behind prelim_kernel (they write and read the
+    // arrays by spectrum), schedule records to read the row beside, a list and its header in 64 words.  Every other launch sequence
+    // — the retry pass, quick_score and initial_hits (not `production`), SAGE_HIP_NO_SCHED=1 — keeps the arrays by spectrum.
+    const bool hand_on = production && !fused && !one_launch && !wide && !huge && view.sched != nullptr && hand_rows_possible(s) &&
+                         (uint64_t)list_off + view.n <= wset.cap_hand;
+    if (hand_on) w1.hand = wset.hand.p + (size_t)list_off * HAND_ROW_WORDS;  // (rows by schedule position within the part)
+    if (phase != 2) s->last_hand = hand_on;
     if (wing) w1.winbuf = w2.winbuf = wset.winbuf.p;
     o.huge = huge;
     if (huge) {
@@ -2403,6 +2438,14 @@ int sage_hip_debug_heavy_counters(SageScorer* s, unsigned long long* out2) {
     out2[0] = out2[1] = 0;
     for (size_t b = 0; b < DBG_BLOCKS; b++)
         for (uint32_t k = 0; k < 2; k++) out2[k] += all[b * DBG_PRUNE_WORDS + 8 + k];
+    return SAGE_HIP_OK;
+}
+
+// debugging aid: 1 if the last first pass this scorer enqueued handed its preliminary lists over in rows by schedule position
+// (DevWork::hand), 0 if in the arrays by spectrum
+int sage_hip_debug_handover_route(SageScorer* s, uint32_t* out) {
+    if (!s || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+    *out = s->last_hand ? 1u : 0u;
     return SAGE_HIP_OK;
 }
 

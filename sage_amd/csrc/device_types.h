@@ -194,7 +194,17 @@ struct DevWork {  // per-spectrum outputs of the preliminary pass
     uint32_t qmax;
     uint32_t tile_shift;   // log2 of the peptides per tile (the readers of the candidate directories need it)
     unsigned long long* dbg;  // optional [2][8] per-phase cycle accumulators (null in production)
+    // The hand-over of a narrow first pass in SCHEDULE order (null: off — cand / cand_len / totals / status by spectrum, as every other
+    // route).  [n * HAND_ROW_WORDS] one 512-byte row per schedule position of the launch: prelim_kernel writes the row of every
+    // position, rescore_kernel reads it beside the schedule record instead of behind it.
+    uint64_t* hand;
 };
+// A row of DevWork::hand: the packed PreScore list in words 0 .. kmax - 1 (what goes to `cand` on the other routes), then
+// {status, stored} and {matched_peaks, scored_candidates} — low word first — in the last two words.  One word per lane.
+constexpr uint32_t HAND_ROW_WORDS = 64, HAND_HEAD_WORD = 62, HAND_TOTALS_WORD = 63, HAND_LIST_MAX = HAND_HEAD_WORD;
+static_assert(HAND_LIST_MAX <= HAND_HEAD_WORD && HAND_HEAD_WORD < HAND_TOTALS_WORD && HAND_TOTALS_WORD < HAND_ROW_WORDS && HAND_ROW_WORDS == 64,
+              "the list and the two header words fit a row of one word per lane");
+static_assert(HAND_ROW_WORDS * sizeof(uint64_t) % 128 == 0, "rows keep the array's 128-byte alignment");
 
 enum { ST_OK = 0, ST_DEFERRED = 1, ST_OVERFLOW = 2, ST_RETRY = 3,
        ST_DONE = 4,

@@ -1389,6 +1389,20 @@ __global__ __launch_bounds__(64) SAGE_PRELIM_WAVES_ATTR void prelim_kernel(Preli
                 row[1] = keep ? r.q_potential : 0u;  // (0: no counts kept — several queries, or a large window)
             }
         }
+        uint64_t* const w_hand = BIGK ? nullptr : ka->w.hand;
+        if (w_hand) {
+            // The hand-over in schedule order (DevWork::hand): ONE store per lane into the 512-byte row of this position — the list,
+            // and status / length / totals in the last two words — instead of four 4-byte stores at random addresses and a list row
+            // that straddles the lines of unrelated spectra.  EVERY position writes its WHOLE row, a deferred or overflowed spectrum's
+            // too (length 0 / its status), the words behind the list as empty entries: rescore_kernel never meets a word of an
+            // earlier step, and the four lines of a row are written in full.
+            const uint32_t st = r.deferred ? (uint32_t)ST_DEFERRED : r.ok ? (r.untrimmed ? (uint32_t)ST_OK_ORDERED : (uint32_t)ST_OK) : (uint32_t)ST_OVERFLOW;
+            const uint32_t stored = r.deferred ? 0u : (r.stored < HAND_LIST_MAX ? r.stored : HAND_LIST_MAX);
+            uint64_t v = lane < stored ? L.listB[lane] : PRESCORE_EMPTY;
+            if (lane == HAND_HEAD_WORD) v = (uint64_t)stored << 32 | st;
+            if (lane == HAND_TOTALS_WORD) v = r.deferred ? 0ull : (uint64_t)r.scored << 32 | r.matched;
+            w_hand[(size_t)pos * HAND_ROW_WORDS + lane] = v;
+        }
         if (r.deferred) {
             if (lane == 0) {
                 ka->w.status[spec] = ST_DEFERRED;
@@ -1402,14 +1416,14 @@ __global__ __launch_bounds__(64) SAGE_PRELIM_WAVES_ATTR void prelim_kernel(Preli
             }
             continue;
         }
-        if (lane == 0) {
-            if (!r.ok) atomicAdd(ka->w.n_deferred + CTR_LIST_OVERFLOW, 1u);
-            ka->w.status[spec] = r.ok ? (r.untrimmed ? ST_OK_ORDERED : ST_OK) : ST_OVERFLOW;
-            ka->w.cand_len[spec] = r.stored;
-            ka->w.totals[2 * spec] = r.matched;
-            ka->w.totals[2 * spec + 1] = r.scored;
-        }
-        {
+        if (lane == 0 && !r.ok) atomicAdd(ka->w.n_deferred + CTR_LIST_OVERFLOW, 1u);
+        if (!w_hand) {  // by spectrum: every route but the narrow first pass in schedule order
+            if (lane == 0) {
+                ka->w.status[spec] = r.ok ? (r.untrimmed ? ST_OK_ORDERED : ST_OK) : ST_OVERFLOW;
+                ka->w.cand_len[spec] = r.stored;
+                ka->w.totals[2 * spec] = r.matched;
+                ka->w.totals[2 * spec + 1] = r.scored;
+            }
             uint64_t* __restrict__ dst = ka->w.cand + (size_t)spec * ka->sc.kmax;
             for (uint32_t i = lane; i < r.stored; i += WAVE) dst[i] = L.listB[i];
         }
@@ -3589,12 +3603,31 @@ struct LateArgs<RescoreKernargs> {
 // remove_matched_peaks, nothing of the candidates kept alive for a second round across score_candidates — which is what the
 // general form pays its spills for.  CHIMERA == true serves both kinds of search (sc.chimera decides at run time).
 // quick_score's k-select (`keep`) is compiled into ACC instances only: launch_rescore never hands `keep` to another one.
+// What rescore_spectrum needs of its lane's candidate from the database: three gathers, requested by the caller — as early as it
+// knows the candidate (rescore_kernel on hand-over rows: beside the first peaks, in front of the status checks) — and first looked
+// at behind rescore_spectrum's table builds, which run on LDS alone while they are on their way.
+struct CandGather {
+    uint64_t ion_base;  // ion_off[pep]
+    uint32_t pep_rec;   // pep_info[pep]
+    float pep_mass;     // pep_mono[pep]
+};
+__device__ __forceinline__ CandGather gather_candidate(const DevDbView& db, const uint64_t mine) {
+    CandGather g{0ull, 0u, 0.0f};
+    const uint32_t pep = prescore_peptide(mine);
+    if (pep != 0xFFFFFFFFu) {  // scoring.rs:489
+        g.ion_base = db.ion_off[pep];
+        g.pep_rec = db.pep_info[pep];
+        g.pep_mass = db.pep_mono[pep];
+    }
+    return g;
+}
+
 template <bool ACC, class KA, bool FAST = false, bool CHIMERA = true, class PC>
 __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const DevWork& w,
                                                  const double* __restrict__ lnfact_table, uint32_t lnfact_n,
                                                  SageFeature* __restrict__ out, uint32_t* __restrict__ out_count,
                                                  uint8_t* __restrict__ keep, const RescoreLds& R, const uint32_t spec, uint32_t P,
-                                                 const uint64_t mine, const uint32_t tot_matched, const uint32_t tot_scored,
+                                                 const uint64_t mine, const CandGather& cg, const uint32_t tot_matched, const uint32_t tot_scored,
                                                  const bool list_is_exact, const bool queue_on_tie, PC& pc) {
     // keep != nullptr: Scorer::quick_score with prefilter_low_memory (scoring.rs:270-289) instead of build_features
     const uint32_t lane = lane_id();
@@ -3607,15 +3640,12 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
     const uint32_t z = prescore_charge(mine);
     const int iso = prescore_iso(mine);
     const uint32_t nfz = max_fragment_charge(sc.max_fragment_charge, z) - 1;
-    uint64_t ion_base = 0;
     uint32_t lm1 = 0;
-    uint32_t pep_rec = 0;   // the candidate's record and mass: requested here, first looked at behind the table builds below, which
-    float pep_mass = 0.0f;  // run on LDS alone while these gathers are on their way
-    if (valid) {
-        ion_base = db.ion_off[pep];
-        pep_rec = db.pep_info[pep];
-        pep_mass = db.pep_mono[pep];
-    }
+    // the candidate's ion offset, record and mass: requested by the caller (gather_candidate), first looked at behind the table builds
+    // below, which run on LDS alone while these gathers are on their way
+    const uint64_t ion_base = cg.ion_base;
+    const uint32_t pep_rec = cg.pep_rec;
+    const float pep_mass = cg.pep_mass;
     // (registers are what this kernel is short of: what only the Feature record needs waits in LDS — R.meta, R.hdr — and nothing
     // is kept that two instructions recompute)
     if (lane == 0) {
@@ -4135,18 +4165,45 @@ __global__ __launch_bounds__(64) SAGE_RESCORE_WAVES_ATTR void rescore_kernel(Res
     const uint32_t pos = xcd_position(blockIdx.x, n_batch, sc.xcd_chunk);
     // (with schedule records — DevBatchView::sched — the block's spectrum and its peak range come in one trip, and the peaks are
     // requested beside the status and the list instead of behind peak_off[spec])
+    // The hand-over row of this schedule position (DevWork::hand; the narrow first pass with schedule records): requested BESIDE the
+    // record — both hang on `pos` alone — one word per lane, the list in the low lanes, {status, length} and the totals in the last
+    // two.  The chain of dependent round trips is then
+    //   {schedule record, hand-over row} -> {peaks, ion offsets, peptide records} -> ions.
+    const uint64_t* __restrict__ const hand = w.hand;
+    uint64_t row_word = 0;
+    if (hand) row_word = hand[(size_t)pos * HAND_ROW_WORDS + lane];
     uint4 rec = make_uint4(0u, 0u, 0u, 0u);
     if (b.sched) rec = b.sched[(size_t)b.sched_stride * pos];
+    uint32_t st, ncand, tot_m, tot_s;
+    uint64_t mine = PRESCORE_EMPTY;
+    CandGather cg{0ull, 0u, 0.0f};
+    if (hand) {
+        // The candidates' gathers as soon as the row is here, in front of the status checks: the row is this step's whatever the
+        // status (prelim_kernel writes every position's, length 0 for a spectrum it handed on), so its entries are peptides of this
+        // index.  (In front of the peak requests, too, which need the record: the row is a vector load, the record a scalar one, and
+        // the wait for the row — the only vector load in flight — does not wait for anything else.  Behind the peak requests, which
+        // sit in branches on the peak count, the same wait is for every peak to arrive: a trip of its own again.)
+        const uint64_t head = lane_value(row_word, HAND_HEAD_WORD), totals = lane_value(row_word, HAND_TOTALS_WORD);
+        st = (uint32_t)head;
+        ncand = (uint32_t)(head >> 32);
+        tot_m = (uint32_t)totals;
+        tot_s = (uint32_t)(totals >> 32);
+        mine = lane < ncand && lane < HAND_LIST_MAX ? row_word : PRESCORE_EMPTY;
+        cg = gather_candidate(db, mine);
+    }
     const uint32_t spec = b.sched ? uni(rec.x) : b.order ? b.order[pos] : pos;
-    // Everything that hangs on `spec` alone is requested together, ahead of the first use: the spectrum's status, the whole row
-    // of its preliminary list (unconditionally — the array is padded by a wavefront — so that the load does not wait for the
-    // list's length), the length, the totals, the peak range.  The chain of dependent round trips is then
+    // Without the rows, everything that hangs on `spec` alone is requested together, ahead of the first use: the spectrum's status,
+    // the whole row of its preliminary list (unconditionally — the array is padded by a wavefront — so that the load does not wait
+    // for the list's length), the length, the totals, the peak range.  One trip more:
     // schedule record -> {status, list, peaks} -> ion offsets -> ions (without the records: order -> {status, list, peak range} ->
     // {peaks, ion offsets} -> ions).
-    const uint32_t st = w.status[spec];
-    const uint64_t row_word = w.cand[(size_t)spec * sc.kmax + lane];
-    const uint32_t ncand = w.cand_len[spec];
-    const uint32_t tot_m = w.totals[2 * spec], tot_s = w.totals[2 * spec + 1];
+    if (!hand) {
+        st = w.status[spec];
+        row_word = w.cand[(size_t)spec * sc.kmax + lane];
+        ncand = w.cand_len[spec];
+        tot_m = w.totals[2 * spec];
+        tot_s = w.totals[2 * spec + 1];
+    }
     const uint64_t p0 = b.sched ? ((uint64_t)uni(rec.w) << 32) | uni(rec.z) : b.peak_off[spec];
     const uint32_t P = b.sched ? uni(rec.y) : (uint32_t)(b.peak_off[spec + 1] - p0);
     // With schedule records: the first 192 peaks requested HERE, in front of the branches on the status
@@ -4177,9 +4234,12 @@ __global__ __launch_bounds__(64) SAGE_RESCORE_WAVES_ATTR void rescore_kernel(Res
         R.pm[i] = b.masses[p0 + i];
         R.pi[i] = b.intensities[p0 + i];
     }
-    const uint64_t mine = lane < ncand ? row_word : PRESCORE_EMPTY;
+    if (!hand) {  // (by spectrum: a row that is only known to be this step's now, behind the status checks)
+        mine = lane < ncand ? row_word : PRESCORE_EMPTY;
+        cg = gather_candidate(db, mine);
+    }
     // (a list no trim touched is the reference's list already: equal hyperscores are ranked by it, no retry)
-    rescore_spectrum<ACC, RescoreKernargs, FAST, CHIMERA>(db, sc, b, w, lnfact_table, lnfact_n, out, out_count, keep, R, spec, P, mine, tot_m,
+    rescore_spectrum<ACC, RescoreKernargs, FAST, CHIMERA>(db, sc, b, w, lnfact_table, lnfact_n, out, out_count, keep, R, spec, P, mine, cg, tot_m,
                                                           tot_s, sc.exact != 0 || st == ST_OK_ORDERED, true, pc);
 }
 
@@ -4289,7 +4349,8 @@ __global__ __launch_bounds__(64) SAGE_PRELIM_WAVES_ATTR void search_kernel(DevDb
     const uint32_t tot_s = __hip_atomic_load(w.totals + 2 * spec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint64_t mine = lane < ncand ? __hip_atomic_load(w.cand + (size_t)spec * sc.kmax + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                        : PRESCORE_EMPTY;
-    const bool done = rescore_spectrum<true, void>(db, sc, b, w, lnfact_table, lnfact_n, out, out_count, nullptr, R, spec, P, mine, tot_m, tot_s,
+    const bool done = rescore_spectrum<true, void>(db, sc, b, w, lnfact_table, lnfact_n, out, out_count, nullptr, R, spec, P, mine,
+                                                   gather_candidate(db, mine), tot_m, tot_s,
                                        st == ST_OK_ORDERED, true, pc);
     if (done && lane == 0) w.status[spec] = ST_DONE;  // (a rescore_kernel behind the large-window kernels leaves it alone)
 }
@@ -4371,8 +4432,8 @@ __global__ __launch_bounds__(64) SAGE_NARROW_WAVES_ATTR void narrow_kernel(Resco
             pc.mark(4);
             pc.rebase(1);  // (the rescoring phase accounts under kernel 1)
             __syncthreads();  // the list is in registers: the preliminary phase's LDS is free
-            if (rescore_spectrum<true, RescoreKernargs>(db, sc, b, w, lnfact_table, lnfact_n, out, out_count, nullptr, R, spec, si.P, mine, r.matched,
-                                                        r.scored, exact || r.untrimmed, false, pc) ||
+            if (rescore_spectrum<true, RescoreKernargs>(db, sc, b, w, lnfact_table, lnfact_n, out, out_count, nullptr, R, spec, si.P, mine,
+                                                        gather_candidate(db, mine), r.matched, r.scored, exact || r.untrimmed, false, pc) ||
                 exact)
                 break;
             exact = true;  // equal hyperscores at a reported rank: once more, with bounded_min_heapify replayed (heap.rs:7-28)
