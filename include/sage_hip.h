@@ -343,6 +343,35 @@ int sage_hip_debug_heavy_counters(SageScorer* scorer, unsigned long long* out2);
  * creation forces the latter; so does every step that is not the plain narrow search with schedule records). */
 int sage_hip_debug_handover_route(SageScorer* scorer, uint32_t* out);
 
+/* Debug aid (no condition): the device database read back, so that tests can hold every table sage_hip_db_create derived
+ *  to a plain restatement, entry for entry.  The layout: the scalars the kernels address the tables with. */
+typedef struct SageDbLayout {
+    uint64_t np, nf;                 /* peptides; stored fragment entries (without the two padding entries of a copy) */
+    uint32_t tile_shift, n_tiles, lut_stride;
+    float lut_scale;
+    uint32_t tile2_shift, n_tiles2, lut2_stride;
+    float lut2_scale;
+    uint32_t lut2_words;
+    uint32_t pep_lut_bins;           /* 0: no peptide-mass table */
+    float pep_lut_inv_w;
+    uint32_t ion_lo_bits, ion_hi_bits; /* smallest / largest |ion| of the ion table as f32 bits (none: 0xFFFFFFFF, 0) */
+    uint32_t max_ions, max_len;
+    uint64_t tm2_pos_len;            /* elements of SAGE_DB_TM2_POS */
+} SageDbLayout;
+int sage_hip_debug_db_layout(SageDeviceDb* db, SageDbLayout* out);
+/* The tables: IONS f32 [ion_off[np]] (without the 8 floats of padding), ION_OFF / PM_OFF u64 [np + 1], PEP_INFO u32 [np], PEP_MONO f32
+ * [np], PEP_LUT u32 [pep_lut_bins + 1] (none: size 0), PM_FRAG / TM_FRAG / TM2_FRAG SageTheoretical [nf + 2] (the two padding
+ * entries included; PM_FRAG is made from the large-tile copy first if the build released it, and is the [nf] list as generated when
+ * SAGE_HIP_KEEP_PM_FRAG was set at creation), TM_LUT u32 [n_tiles * lut_stride], TM2_L1 {u32 bits, u32 rank} [n_tiles2 *
+ * lut2_words], TM2_POS u32 [tm2_pos_len]. */
+enum {
+    SAGE_DB_IONS = 0, SAGE_DB_ION_OFF = 1, SAGE_DB_PM_OFF = 2, SAGE_DB_PEP_INFO = 3, SAGE_DB_PEP_MONO = 4, SAGE_DB_PEP_LUT = 5,
+    SAGE_DB_PM_FRAG = 6, SAGE_DB_TM_FRAG = 7, SAGE_DB_TM2_FRAG = 8, SAGE_DB_TM_LUT = 9, SAGE_DB_TM2_L1 = 10, SAGE_DB_TM2_POS = 11
+};
+/* Copy table `table` to `out` (capacity `cap_bytes`); *out_bytes = the table's size.  out == NULL: the size only.  A table that
+ * does not exist: size 0, SAGE_HIP_OK.  An unknown id or a buffer smaller than the table: SAGE_HIP_ERR_INVALID. */
+int sage_hip_debug_db_table(SageDeviceDb* db, int table, void* out, uint64_t cap_bytes, uint64_t* out_bytes);
+
 /* ---- post-search rescoring --------------------------------------------------------------
  * The step that consumes the Feature records of ALL searched files (sage-cli runner.rs:536-541):
  *   spectrum_fdr  (runner.rs:281-292)  = ml::linear_discriminant::score_psms (linear_discriminant.rs:133-231: mass-error KDE,

@@ -246,6 +246,24 @@ class SagePostColumns(C.Structure):
                                          "aligned_rt", "predicted_rt", "delta_rt_model", "predicted_ims", "delta_ims_model")]
 
 
+class SageDbLayout(C.Structure):
+    _fields_ = [("np", C.c_uint64), ("nf", C.c_uint64), ("tile_shift", C.c_uint32), ("n_tiles", C.c_uint32), ("lut_stride", C.c_uint32),
+                ("lut_scale", C.c_float), ("tile2_shift", C.c_uint32), ("n_tiles2", C.c_uint32), ("lut2_stride", C.c_uint32),
+                ("lut2_scale", C.c_float), ("lut2_words", C.c_uint32), ("pep_lut_bins", C.c_uint32), ("pep_lut_inv_w", C.c_float),
+                ("ion_lo_bits", C.c_uint32), ("ion_hi_bits", C.c_uint32), ("max_ions", C.c_uint32), ("max_len", C.c_uint32),
+                ("tm2_pos_len", C.c_uint64)]
+
+
+# sage_hip_debug_db_table: name -> (SAGE_DB_* id, numpy dtype of an element)
+LUT_WORD_DTYPE = np.dtype([("bits", "<u4"), ("rank", "<u4")])
+DB_TABLES = {
+    "ions": (0, np.dtype("<f4")), "ion_off": (1, np.dtype("<u8")), "pm_off": (2, np.dtype("<u8")), "pep_info": (3, np.dtype("<u4")),
+    "pep_mono": (4, np.dtype("<f4")), "pep_lut": (5, np.dtype("<u4")), "pm_frag": (6, THEORETICAL_DTYPE),
+    "tm_frag": (7, THEORETICAL_DTYPE), "tm2_frag": (8, THEORETICAL_DTYPE), "tm_lut": (9, np.dtype("<u4")),
+    "tm2_l1": (10, LUT_WORD_DTYPE), "tm2_pos": (11, np.dtype("<u4")),
+}
+
+
 class SageHipError(RuntimeError):
     pass
 
@@ -305,6 +323,8 @@ def load():
         "sage_hip_debug_filter_counters": (C.c_int, [vp, c_u64_p]),
         "sage_hip_debug_heavy_counters": (C.c_int, [vp, c_u64_p]),
         "sage_hip_debug_handover_route": (C.c_int, [vp, c_u32_p]),
+        "sage_hip_debug_db_layout": (C.c_int, [vp, C.POINTER(SageDbLayout)]),
+        "sage_hip_debug_db_table": (C.c_int, [vp, C.c_int, vp, C.c_uint64, c_u64_p]),
         "sage_hip_host_alloc": (C.c_int, [C.c_uint64, C.POINTER(vp)]),
         "sage_hip_host_free": (None, [vp]),
         "sage_hip_rescore": (C.c_int, [C.c_int, C.POINTER(SageRescoreInput), C.POINTER(SageRescoreOutput)]),
@@ -354,7 +374,7 @@ EXPORTED_SYMBOLS = [
     "sage_hip_hostdb_peptide_info", "sage_hip_process_ms2", "sage_hip_device_count", "sage_hip_db_create", "sage_hip_db_destroy",
     "sage_hip_db_device_bytes", "sage_hip_scorer_create", "sage_hip_scorer_destroy", "sage_hip_scorer_clone", "sage_hip_score_batch",
     "sage_hip_batch_upload", "sage_hip_batch_free", "sage_hip_batch_process_upload", "sage_hip_batch_download", "sage_hip_score_resident", "sage_hip_initial_hits",
-    "sage_hip_last_timing", "sage_hip_scorer_set_timing_interval", "sage_hip_annotate_resident", "sage_hip_quick_score_resident", "sage_hip_debug_phase_cycles", "sage_hip_debug_prune_counters", "sage_hip_debug_filter_counters", "sage_hip_debug_heavy_counters", "sage_hip_debug_handover_route", "sage_hip_host_alloc", "sage_hip_host_free",
+    "sage_hip_last_timing", "sage_hip_scorer_set_timing_interval", "sage_hip_annotate_resident", "sage_hip_quick_score_resident", "sage_hip_debug_phase_cycles", "sage_hip_debug_prune_counters", "sage_hip_debug_filter_counters", "sage_hip_debug_heavy_counters", "sage_hip_debug_handover_route", "sage_hip_debug_db_layout", "sage_hip_debug_db_table", "sage_hip_host_alloc", "sage_hip_host_free",
     "sage_hip_rescore", "sage_hip_hostdb_competition_keys", "sage_hip_fasta_num_targets", "sage_hip_prefilter_chunk_size",
     "sage_hip_hostdb_build_chunk", "sage_hip_hostdb_merge_kept", "sage_hip_predict_rt", "sage_hip_hostdb_feature_peptides",
     "sage_hip_write_results", "sage_hip_mzml_read", "sage_hip_mzml_view", "sage_hip_mzml_check_searchable", "sage_hip_mzml_spectrum_id", "sage_hip_mzml_free",

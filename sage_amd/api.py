@@ -268,8 +268,9 @@ class IndexedDatabase:
 
 
 class DeviceDatabase:
-    def __init__(self, host: IndexedDatabase, device: int = 0, build_on_device: bool = False):
-        """build_on_device: ignore the host's fragments (if any) and generate the index from the peptide list on the GPU
+    def __init__(self, host, device: int = 0, build_on_device: bool = False):
+        """host: an IndexedDatabase, or any object with a `_view` (L.SageDbView, whose arrays it keeps alive) and `has_fragments`.
+        build_on_device: ignore the host's fragments (if any) and generate the index from the peptide list on the GPU
         (Parameters::build_from_peptides, database.rs:265-346); implied when the host database is peptides-only."""
         lib = L.load()
         self.host = host
@@ -283,6 +284,26 @@ class DeviceDatabase:
             view.n_fragments = 0
         L.check(lib.sage_hip_db_create(C.byref(view), device, C.byref(self._h)))
         self.device_bytes = int(lib.sage_hip_db_device_bytes(self._h))
+
+    def layout(self) -> dict:
+        """The scalars of the device layouts (sage_hip_debug_db_layout): tile shifts, table strides and scales, ..."""
+        out = L.SageDbLayout()
+        L.check(L.load().sage_hip_debug_db_layout(self._h, C.byref(out)))
+        return {name: getattr(out, name) for name, _ in L.SageDbLayout._fields_}
+
+    def table(self, name: str) -> np.ndarray:
+        """One table of the device database copied back from HBM (sage_hip_debug_db_table; names: L.DB_TABLES).  "pm_frag" makes
+        the peptide-major list again if the build released it."""
+        table, dtype = L.DB_TABLES[name]
+        lib = L.load()
+        size = C.c_uint64()
+        L.check(lib.sage_hip_debug_db_table(self._h, table, None, 0, C.byref(size)))
+        assert size.value % dtype.itemsize == 0, (name, size.value)
+        out = np.zeros(size.value // dtype.itemsize, dtype=dtype)
+        if size.value:
+            L.check(lib.sage_hip_debug_db_table(self._h, table, out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(size)))
+            assert size.value == out.nbytes
+        return out
 
     def close(self):
         if self._h:

@@ -2449,6 +2449,62 @@ int sage_hip_debug_handover_route(SageScorer* s, uint32_t* out) {
     return SAGE_HIP_OK;
 }
 
+// debugging aid: the scalars of the device database's layout (what DevDbView and SageDeviceDb hold beside the table pointers)
+int sage_hip_debug_db_layout(SageDeviceDb* db, SageDbLayout* out) {
+    if (!db || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+    const DevDbView& v = db->view;
+    std::memset(out, 0, sizeof *out);
+    out->np = v.np;
+    out->nf = v.nf;
+    out->tile_shift = v.tile_shift;
+    out->n_tiles = v.n_tiles;
+    out->lut_stride = v.lut_stride;
+    out->lut_scale = v.lut_scale;
+    out->tile2_shift = v.tile2_shift;
+    out->n_tiles2 = v.n_tiles2;
+    out->lut2_stride = v.lut2_stride;
+    out->lut2_scale = v.lut2_scale;
+    out->lut2_words = v.lut2_words;
+    out->pep_lut_bins = v.pep_lut_bins;
+    out->pep_lut_inv_w = v.pep_lut_inv_w;
+    out->ion_lo_bits = db->ion_lo_bits;
+    out->ion_hi_bits = db->ion_hi_bits;
+    out->max_ions = db->max_ions;
+    out->max_len = db->max_len;
+    out->tm2_pos_len = db->tm2_pos.n;
+    return SAGE_HIP_OK;
+}
+
+// debugging aid: one table of the device database, as it lies in HBM (include/sage_hip.h: SAGE_DB_*)
+int sage_hip_debug_db_table(SageDeviceDb* db, int table, void* out, uint64_t cap_bytes, uint64_t* out_bytes) {
+    if (!db || !out_bytes) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(db->device));
+    if (table == SAGE_DB_PM_FRAG)
+        if (int rc = ensure_pm_frag(db)) return rc;
+    const void* src = nullptr;
+    uint64_t bytes = 0;
+    switch (table) {
+        case SAGE_DB_IONS: src = db->ions.p; bytes = db->ions.bytes() - 8 * sizeof(float); break;  // (padded: sage_hip_db_create)
+        case SAGE_DB_ION_OFF: src = db->ion_off.p; bytes = db->ion_off.bytes(); break;
+        case SAGE_DB_PM_OFF: src = db->pm_off.p; bytes = db->pm_off.bytes(); break;
+        case SAGE_DB_PEP_INFO: src = db->pep_info.p; bytes = db->pep_info.bytes(); break;
+        case SAGE_DB_PEP_MONO: src = db->pep_mono.p; bytes = db->pep_mono.bytes(); break;
+        case SAGE_DB_PEP_LUT: src = db->pep_lut.p; bytes = db->pep_lut.bytes(); break;  // (never allocated: no table)
+        case SAGE_DB_PM_FRAG: src = db->pm_frag.p; bytes = db->pm_frag.bytes(); break;
+        case SAGE_DB_TM_FRAG: src = db->tm_frag.p; bytes = db->tm_frag.bytes(); break;
+        case SAGE_DB_TM2_FRAG: src = db->tm2_frag.p; bytes = db->tm2_frag.bytes(); break;
+        case SAGE_DB_TM_LUT: src = db->tm_lut.p; bytes = db->tm_lut.bytes(); break;
+        case SAGE_DB_TM2_L1: src = db->tm2_l1.p; bytes = db->tm2_l1.bytes(); break;
+        case SAGE_DB_TM2_POS: src = db->tm2_pos.p; bytes = db->tm2_pos.bytes(); break;
+        default: return fail(SAGE_HIP_ERR_INVALID, "sage_hip_debug_db_table: unknown table id");
+    }
+    *out_bytes = bytes;
+    if (!out || !bytes) return SAGE_HIP_OK;
+    if (cap_bytes < bytes) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_debug_db_table: buffer smaller than the table");
+    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+    return SAGE_HIP_OK;
+}
+
 int sage_hip_host_alloc(uint64_t bytes, void** out) {
     if (!out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
     HIP_TRY(hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault));

@@ -200,6 +200,12 @@ uint64_t emu_succinct_lut_mismatches(const float* mz, uint32_t n, float scale, u
     return bad;
 }
 
+// The row of one tile spanning positions [base, base + n) of the index (core.h: lut_entry for every cell), for the numpy restatement
+// of the tables (tests/index_reference.py) to be compared with: the same row emu_lut_windows and emu_succinct_lut_mismatches check.
+void emu_lut_row(const float* mz, uint32_t n, float scale, uint32_t stride, uint32_t base, uint32_t* row) {
+    for (uint32_t c = 0; c < stride; c++) row[c] = base + lut_entry(mz, 1, 0, n, c, stride, scale);
+}
+
 // Run::matched (scoring.rs:771-793) fed the same index sequence through core.h's four-field Run and the one-register form the
 // rescoring kernel keeps: returns the number of steps after which `longest` differs (0 = equivalent on this sequence).
 uint32_t emu_run_packed_mismatches(const uint32_t* indices, uint32_t n) {
