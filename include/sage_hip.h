@@ -680,6 +680,84 @@ int sage_hip_write_tmt(const char* path, const char* const* headers, uint32_t n_
 int sage_hip_hostdb_competition_keys(const SageHostDb* db, const uint32_t* peptide_idx, uint64_t n, uint32_t* peptide_key,
                                  uint32_t* n_peptide_keys, uint32_t* protein_key, uint32_t* n_protein_keys);
 
+/* ---- protein groups and picked protein-group FDR (sage-cli runner.rs:539-549: protein_grouping::generate_protein_groups, then
+ * fdr::picked_protein_group; crates/sage/src/protein_grouping.rs:59-386, fdr.rs:192-226).  Additive to ABI 6.
+ *   passes        protein_grouping != 0: one pass with threshold clamp(peptide_fdr, 0, 1), one with 1.0; then, and alone when
+ *                 protein_grouping == 0, the fallback for every feature still without groups: Peptide::proteins(..) and its length
+ *   one pass      device: the peptides of features with label != -1 && peptide_q < threshold (strict; NaN never), compacted in
+ *                 ascending order.  host: protein numbering, meta-peptides, groups, edges (sage_hip_group_graph_build).  device:
+ *                 the greedy set cover over the edges, then for every peptide of the run still without groups the covered groups
+ *                 among its proteins.  host: the strings, once per distinct peptide
+ *   competition   features with num_protein_groups == 1, keyed by the group string, side db[peptide].decoy, score
+ *                 discriminant_score: the gather per feature and Competition::assign_q_value at 1 % on the device (the code of
+ *                 sage_hip_rescore's picked competitions); protein_group_q stays 1.0 elsewhere
+ * The cover runs edge-parallel kernels while more live edges remain than SAGE_HIP_COVER_LDS_EDGES (read once per call; default
+ * 16384, at most 18432), then one workgroup finishes all remaining rounds with the edges in LDS. */
+typedef struct SageGroupInput {
+    uint64_t n;
+    const SageFeature* features;      /* host, [n]: label and peptide_idx are read */
+    const float* peptide_q;           /* [n] */
+    const float* discriminant_score;  /* [n] */
+    int32_t protein_grouping;         /* input.rs:382 default: 1 */
+    float peptide_fdr;                /* protein_grouping_peptide_fdr, input.rs:383 default: 0.01 */
+} SageGroupInput;
+
+typedef struct SageGroupStrings SageGroupStrings; /* the distinct protein_groups strings of one call, owned by the library */
+
+typedef struct SageGroupOutput {
+    /* caller-allocated host arrays [n], input order */
+    uint32_t* num_protein_groups;
+    float* protein_group_q;
+    uint32_t* string_id;              /* protein_groups of feature i = sage_hip_group_string(strings, string_id[i]) */
+    /* filled by the call */
+    SageGroupStrings* strings;        /* release with sage_hip_group_strings_free */
+    uint64_t n_strings;
+    uint64_t passing_protein_group;   /* target groups at 1 % (fdr.rs:105) */
+    uint32_t n_groups;                /* of the last pass (threshold 1.0); 0 when protein_grouping == 0 */
+    uint32_t n_meta_peptides;         /* of the last pass */
+    uint32_t cover_rounds;            /* add_largest_to_cover picks, summed over the passes */
+    float device_ms;                  /* HIP-event time of the call's device work, uploads and downloads included */
+    double host_graph_ms;             /* wall time of the host graph builder, summed over the passes */
+} SageGroupOutput;
+
+int sage_hip_protein_groups(int device, const SageHostDb* db, const SageGroupInput* in, SageGroupOutput* out);
+const char* sage_hip_group_string(const SageGroupStrings* strings, uint64_t id); /* NULL when id >= n_strings */
+void sage_hip_group_strings_free(SageGroupStrings* strings);
+
+/* The host graph builder alone (no device): ProteinGrouper::build (protein_grouping.rs:171-231) for the ascending, distinct
+ * peptide indices `peptides`.  The view's arrays belong to the handle. */
+typedef struct SageGroupGraph SageGroupGraph;
+typedef struct SageGroupGraphView {
+    uint32_t n_proteins, n_meta_peptides, n_groups;
+    uint64_t n_edges;
+    const uint32_t* protein_id;       /* [n_proteins] ProteinIx -> a protein of the database with that name (sage_hip_hostdb_protein_name) */
+    const uint8_t* protein_decoy;     /* [n_proteins] */
+    const uint64_t* group_off;        /* [n_groups + 1] into group_proteins */
+    const uint32_t* group_proteins;   /* ProteinIx, ascending inside a group */
+    const uint64_t* evidence_off;     /* [n_groups + 1] into evidence */
+    const uint32_t* evidence;         /* ascending meta-peptide indices of each group */
+    const uint32_t* edge_group;       /* [n_edges] */
+    const uint32_t* edge_meta;        /* [n_edges] */
+} SageGroupGraphView;
+int sage_hip_group_graph_build(const SageHostDb* db, const uint32_t* peptides, uint64_t n, SageGroupGraph** out);
+int sage_hip_group_graph_view(const SageGroupGraph* graph, SageGroupGraphView* out);
+void sage_hip_group_graph_free(SageGroupGraph* graph);
+/* name of protein `id` of the database (FASTA accession, without the decoy tag); returns the required buffer size including NUL */
+uint64_t sage_hip_hostdb_protein_name(const SageHostDb* db, uint64_t id, char* out, uint64_t cap);
+
+/* sage_hip_write_results with the three protein-group columns of results.sage.tsv (the .pin format has none of them).
+ * groups == NULL, or a NULL array in it: that column's default, as sage_hip_write_results writes it. */
+typedef struct SageGroupColumns {
+    const char* const* strings;          /* [n_strings] NUL-terminated protein_groups strings */
+    uint64_t n_strings;
+    const uint32_t* string_id;           /* [n] into strings, indexed like features */
+    const uint32_t* num_protein_groups;  /* [n] */
+    const float* protein_group_q;        /* [n] */
+} SageGroupColumns;
+int sage_hip_write_results_grouped(const char* path, int format, const SageHostDb* db, const SageFeature* features, uint64_t n,
+                                   const uint64_t* order, const uint64_t* psm_id, const char* const* filenames, uint32_t n_files,
+                                   const char* const* spec_ids, const SagePostColumns* post, const SageGroupColumns* groups);
+
 const char* sage_hip_last_error(void);
 int sage_hip_abi_version(void);
 

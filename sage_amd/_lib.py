@@ -246,6 +246,28 @@ class SagePostColumns(C.Structure):
                                          "aligned_rt", "predicted_rt", "delta_rt_model", "predicted_ims", "delta_ims_model")]
 
 
+class SageGroupInput(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("features", C.c_void_p), ("peptide_q", c_float_p), ("discriminant_score", c_float_p),
+                ("protein_grouping", C.c_int32), ("peptide_fdr", C.c_float)]
+
+
+class SageGroupOutput(C.Structure):
+    _fields_ = [("num_protein_groups", c_u32_p), ("protein_group_q", c_float_p), ("string_id", c_u32_p), ("strings", C.c_void_p),
+                ("n_strings", C.c_uint64), ("passing_protein_group", C.c_uint64), ("n_groups", C.c_uint32),
+                ("n_meta_peptides", C.c_uint32), ("cover_rounds", C.c_uint32), ("device_ms", C.c_float), ("host_graph_ms", C.c_double)]
+
+
+class SageGroupGraphView(C.Structure):
+    _fields_ = [("n_proteins", C.c_uint32), ("n_meta_peptides", C.c_uint32), ("n_groups", C.c_uint32), ("n_edges", C.c_uint64),
+                ("protein_id", c_u32_p), ("protein_decoy", c_u8_p), ("group_off", c_u64_p), ("group_proteins", c_u32_p),
+                ("evidence_off", c_u64_p), ("evidence", c_u32_p), ("edge_group", c_u32_p), ("edge_meta", c_u32_p)]
+
+
+class SageGroupColumns(C.Structure):
+    _fields_ = [("strings", C.POINTER(C.c_char_p)), ("n_strings", C.c_uint64), ("string_id", c_u32_p),
+                ("num_protein_groups", c_u32_p), ("protein_group_q", c_float_p)]
+
+
 class SageDbLayout(C.Structure):
     _fields_ = [("np", C.c_uint64), ("nf", C.c_uint64), ("tile_shift", C.c_uint32), ("n_tiles", C.c_uint32), ("lut_stride", C.c_uint32),
                 ("lut_scale", C.c_float), ("tile2_shift", C.c_uint32), ("n_tiles2", C.c_uint32), ("lut2_stride", C.c_uint32),
@@ -348,6 +370,16 @@ def load():
                                          c_float_p, c_float_p, C.POINTER(C.c_char_p), C.c_uint32]),
         "sage_hip_write_results": (C.c_int, [C.c_char_p, C.c_int, vp, vp, C.c_uint64, c_u64_p, c_u64_p, C.POINTER(C.c_char_p),
                                              C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(SagePostColumns)]),
+        "sage_hip_write_results_grouped": (C.c_int, [C.c_char_p, C.c_int, vp, vp, C.c_uint64, c_u64_p, c_u64_p, C.POINTER(C.c_char_p),
+                                                     C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(SagePostColumns),
+                                                     C.POINTER(SageGroupColumns)]),
+        "sage_hip_protein_groups": (C.c_int, [C.c_int, vp, C.POINTER(SageGroupInput), C.POINTER(SageGroupOutput)]),
+        "sage_hip_group_string": (C.c_char_p, [vp, C.c_uint64]),
+        "sage_hip_group_strings_free": (None, [vp]),
+        "sage_hip_group_graph_build": (C.c_int, [vp, c_u32_p, C.c_uint64, C.POINTER(vp)]),
+        "sage_hip_group_graph_view": (C.c_int, [vp, C.POINTER(SageGroupGraphView)]),
+        "sage_hip_group_graph_free": (None, [vp]),
+        "sage_hip_hostdb_protein_name": (C.c_uint64, [vp, C.c_uint64, C.c_char_p, C.c_uint64]),
         "sage_hip_lfq": (C.c_int, [C.c_int, C.POINTER(SageLfqInput), C.POINTER(SageLfqOutput)]),
         "sage_hip_lfq_im": (C.c_int, [C.c_int, C.POINTER(SageLfqInput), C.POINTER(SageLfqMobility), C.POINTER(SageLfqOutput)]),
         "sage_hip_mzml_mobility": (c_float_p, [vp]),
@@ -382,6 +414,8 @@ EXPORTED_SYMBOLS = [
     "sage_hip_tmt", "sage_hip_write_tmt", "sage_hip_mgf_read", "sage_hip_mzml_isolation_kinds", "sage_hip_mzml_charge_zero",
     "sage_hip_parse_f32", "sage_hip_batch_upload_kinds", "sage_hip_batch_process_upload_kinds", "sage_hip_score_batch_kinds",
     "sage_hip_lfq_im", "sage_hip_mzml_mobility", "sage_hip_mzml_has_mobility",
+    "sage_hip_protein_groups", "sage_hip_group_string", "sage_hip_group_strings_free", "sage_hip_group_graph_build",
+    "sage_hip_group_graph_view", "sage_hip_group_graph_free", "sage_hip_hostdb_protein_name", "sage_hip_write_results_grouped",
 ]
 
 

@@ -220,6 +220,38 @@ class IndexedDatabase:
         lib.sage_hip_hostdb_peptide_proteins(self._h, i, buf, n)
         return buf.value.decode()
 
+    def protein_name(self, i: int) -> str:
+        """name of protein `i` of the database (the FASTA accession, without the decoy tag)"""
+        lib = L.load()
+        n = lib.sage_hip_hostdb_protein_name(self._h, i, None, 0)
+        if n == 0:
+            raise IndexError(i)
+        buf = C.create_string_buffer(int(n))
+        lib.sage_hip_hostdb_protein_name(self._h, i, buf, n)
+        return buf.value.decode()
+
+    def group_graph(self, peptides) -> "GroupGraph":
+        """ProteinGrouper::build (protein_grouping.rs:171-231) for the ascending, distinct peptide indices `peptides`: the host
+        half of a grouping pass, without a device."""
+        idx = np.ascontiguousarray(peptides, dtype=np.uint32)
+        lib = L.load()
+        h = C.c_void_p()
+        L.check(lib.sage_hip_group_graph_build(self._h, L.as_ptr(idx, C.c_uint32), len(idx), C.byref(h)))
+        try:
+            v = L.SageGroupGraphView()
+            L.check(lib.sage_hip_group_graph_view(h, C.byref(v)))
+            ng, npr, ne = int(v.n_groups), int(v.n_proteins), int(v.n_edges)
+            copy = lambda p, n, dt: _view_array(p, n, dt).copy() if n else np.zeros(0, dt)
+            group_off = copy(v.group_off, ng + 1 if ng else 0, np.uint64)
+            evidence_off = copy(v.evidence_off, ng + 1 if ng else 0, np.uint64)
+            return GroupGraph(protein_id=copy(v.protein_id, npr, np.uint32), protein_decoy=copy(v.protein_decoy, npr, np.uint8),
+                              n_meta_peptides=int(v.n_meta_peptides), group_off=group_off,
+                              group_proteins=copy(v.group_proteins, int(group_off[-1]) if ng else 0, np.uint32),
+                              evidence_off=evidence_off, evidence=copy(v.evidence, int(evidence_off[-1]) if ng else 0, np.uint32),
+                              edge_group=copy(v.edge_group, ne, np.uint32), edge_meta=copy(v.edge_meta, ne, np.uint32))
+        finally:
+            lib.sage_hip_group_graph_free(h)
+
     def peptide_info(self, i: int):
         """(Peptide.proteins.len(), Peptide.semi_enzymatic)"""
         n, semi = C.c_uint32(), C.c_uint8()
@@ -859,6 +891,68 @@ def rescore(features: np.ndarray, precursor_tol: Tolerance, peptide_key, n_pepti
     L.check(L.load().sage_hip_rescore(device, C.byref(cin), C.byref(cout)))
     return RescoreResult(*outs, order, int(cout.passing_spectrum), int(cout.passing_peptide), int(cout.passing_protein),
                          bool(cout.lda_fitted), np.array(cout.coef[:], dtype=np.float64), float(cout.device_ms))
+
+
+@dataclass
+class GroupGraph:
+    """IndexedDatabase.group_graph: proteins in numbering order (ProteinIx -> a database protein with that name, decoy flag), the
+    groups (ProteinIx lists), every group's evidence (ascending meta-peptide indices) and the edge list of the set cover."""
+    protein_id: np.ndarray
+    protein_decoy: np.ndarray
+    n_meta_peptides: int
+    group_off: np.ndarray
+    group_proteins: np.ndarray
+    evidence_off: np.ndarray
+    evidence: np.ndarray
+    edge_group: np.ndarray
+    edge_meta: np.ndarray
+
+    @property
+    def n_groups(self) -> int:
+        return max(len(self.group_off) - 1, 0)
+
+
+@dataclass
+class ProteinGroupResult:
+    """Outputs of sage_hip_protein_groups, input order: Feature.protein_groups (strings[string_id[i]]), num_protein_groups,
+    protein_group_q; the passing count of picked_protein_group and the sizes of the last pass's graph."""
+    strings: List[str]
+    string_id: np.ndarray
+    num_protein_groups: np.ndarray
+    protein_group_q: np.ndarray
+    passing_protein_group: int
+    n_groups: int
+    n_meta_peptides: int
+    cover_rounds: int
+    device_ms: float
+    host_graph_ms: float
+
+    def protein_groups(self, i: int) -> str:
+        return self.strings[int(self.string_id[i])]
+
+
+def protein_groups(db: "IndexedDatabase", features: np.ndarray, peptide_q, discriminant_score, protein_grouping: bool = True,
+                   peptide_fdr: float = 0.01, device: int = 0) -> ProteinGroupResult:
+    """generate_protein_groups + picked_protein_group (sage-cli runner.rs:539-549) over ALL Features of a run: IDPicker protein
+    groups in two passes, the fallback protein list, and the picked protein-group FDR, on the device (rescore.hip) with the
+    graph and the strings built on the host (groups.cpp).  `features`: 1-D array of FEATURE_DTYPE."""
+    f = np.ascontiguousarray(features, dtype=L.FEATURE_DTYPE).reshape(-1)
+    n = len(f)
+    pq = np.ascontiguousarray(peptide_q, dtype=np.float32)
+    ds = np.ascontiguousarray(discriminant_score, dtype=np.float32)
+    assert len(pq) == n and len(ds) == n
+    num, sid, q = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.ones(n, np.float32)
+    cin = L.SageGroupInput(n, f.ctypes.data, L.as_ptr(pq, C.c_float), L.as_ptr(ds, C.c_float), int(bool(protein_grouping)),
+                           float(peptide_fdr))
+    cout = L.SageGroupOutput(L.as_ptr(num, C.c_uint32), L.as_ptr(q, C.c_float), L.as_ptr(sid, C.c_uint32))
+    lib = L.load()
+    L.check(lib.sage_hip_protein_groups(device, db._h, C.byref(cin), C.byref(cout)))
+    try:
+        strings = [lib.sage_hip_group_string(cout.strings, i).decode() for i in range(int(cout.n_strings))]
+    finally:
+        lib.sage_hip_group_strings_free(cout.strings)
+    return ProteinGroupResult(strings, sid, num, q, int(cout.passing_protein_group), int(cout.n_groups), int(cout.n_meta_peptides),
+                              int(cout.cover_rounds), float(cout.device_ms), float(cout.host_graph_ms))
 
 
 @dataclass

@@ -8,9 +8,10 @@ flow of runner.rs (read mzML -> SpectrumProcessor::process -> keep MS2 with >= m
 :311-325, :398-461) and the `results.sage.tsv` / `matched_fragments.sage.tsv` writers (:687-935).  Everything downstream
 of Scorer::score is limited to the LDA rescoring, q-values and picked peptide / protein FDR (runner.rs:536-541, on the
 device: rescore.hip), label-free MS1 quantification when `quant.lfq` is true (runner.rs:562-575, lfq.hip: `lfq.tsv`),
-isobaric-tag (TMT) reporter-ion quantification when `quant.tmt` is set (runner.rs:334-359, 398-410, tmt.hip: `tmt.tsv`) and
-the optional percolator .pin file; protein grouping, parquet, cloud IO are out of scope and their columns carry the defaults a
-Feature is born with (scoring.rs:576-592).  The search itself runs on the GPU through libsage_hip.so; there is no CPU fallback.
+isobaric-tag (TMT) reporter-ion quantification when `quant.tmt` is set (runner.rs:334-359, 398-410, tmt.hip: `tmt.tsv`),
+IDPicker protein groups with the picked protein-group FDR when the configuration names `protein_grouping` or
+`protein_grouping_peptide_fdr` (runner.rs:539-549, rescore.hip + groups.cpp; see run()) and the optional percolator .pin file;
+parquet and cloud IO are out of scope.  The search itself runs on the GPU through libsage_hip.so; there is no CPU fallback.
 """
 import argparse
 import json
@@ -24,7 +25,7 @@ from . import output
 from ._lib import FEATURE_DTYPE as L_FEATURE_DTYPE
 from .api import (LFQ_INTEGRATION, LFQ_SCORING, DatabaseParameters, DeviceDatabase, Isobaric, LfqSettings, RawBatch, Scorer,
                   ScorerParams, SpectrumBatch, SpectrumProcessor, TmtSettings, Tolerance, device_count, lfq, peptide_compositions,
-                  predict_rt, rescore, tmt)
+                  predict_rt, protein_groups, rescore, tmt)
 from .mgf import TOL_DA, is_mgf, read_mgf_native, read_spectra
 
 
@@ -44,7 +45,12 @@ def search_parameters(cfg: dict) -> dict:
         isotope_errors=(int(iso[0]), int(iso[1])), deisotope=True if cfg.get("deisotope") is None else bool(cfg["deisotope"]),
         chimera=bool(cfg.get("chimera", False)), wide_window=bool(cfg.get("wide_window", False)),
         score_type=cfg.get("score_type") or "SageHyperScore",
-        predict_rt=True if cfg.get("predict_rt") is None else bool(cfg["predict_rt"]))  # input.rs:372
+        predict_rt=True if cfg.get("predict_rt") is None else bool(cfg["predict_rt"]),  # input.rs:372
+        protein_grouping=True if cfg.get("protein_grouping") is None else bool(cfg["protein_grouping"]),  # input.rs:382
+        protein_grouping_peptide_fdr=0.01 if cfg.get("protein_grouping_peptide_fdr") is None
+        else float(cfg["protein_grouping_peptide_fdr"]),  # input.rs:383
+        # the protein-group stage runs when the configuration names one of its keys (see run())
+        protein_group_stage=cfg.get("protein_grouping") is not None or cfg.get("protein_grouping_peptide_fdr") is not None)
 
 
 def quant_settings(cfg: dict, log=print):
@@ -452,10 +458,14 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         psm_id += len(part)
     reader.shutdown(wait=True)
     # runner.rs:536-541: spectrum_fdr (LDA or heuristic, sort, q-values), picked_peptide, picked_protein — on the device.
-    # (protein grouping is outside this path: its columns keep the defaults, see output.py)
+    # runner.rs:539-549: generate_protein_groups + picked_protein_group, when the configuration names `protein_grouping` or
+    # `protein_grouping_peptide_fdr` (the reference runs the block in every run; here a configuration without either key keeps the
+    # columns' defaults, so that its results.sage.tsv stays the file sage_hip_write_results writes for a caller of the C ABI that
+    # does not call sage_hip_protein_groups)
     flat = np.concatenate(feats_all) if feats_all else np.zeros(0, dtype=L_FEATURE_DTYPE)
     post = None
     rtp = None
+    groups = None
     order = range(len(flat))
     rescore_summary = {}
     if len(flat):
@@ -483,8 +493,16 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         log(f"discovered {res.passing_spectrum} target peptide-spectrum matches at 1% FDR")  # runner.rs:576-587
         log(f"discovered {res.passing_peptide} target peptides at 1% FDR")
         log(f"discovered {res.passing_protein} target proteins (supported by proteotypic peptides only) at 1% FDR")
+        group_summary = {}
+        if sp["protein_group_stage"]:
+            groups = protein_groups(host, flat, res.peptide_q, res.discriminant_score, sp["protein_grouping"],
+                                    sp["protein_grouping_peptide_fdr"], device=device)
+            log(f"discovered {groups.passing_protein_group} target protein groups (supported by proteotypic peptides only) at 1% FDR")
+            group_summary = {"q_protein_group": groups.passing_protein_group, "protein_groups": groups.n_groups,
+                             "meta_peptides": groups.n_meta_peptides, "cover_rounds": groups.cover_rounds,
+                             "protein_groups_device_ms": groups.device_ms}
         rescore_summary = {"lda_fitted": res.lda_fitted, "q_spectrum": res.passing_spectrum, "q_peptide": res.passing_peptide,
-                           "q_protein": res.passing_protein, "rescore_ms": (time.time() - t0) * 1000.0,
+                           "q_protein": res.passing_protein, **group_summary, "rescore_ms": (time.time() - t0) * 1000.0,
                            "rescore_device_ms": res.device_ms}
 
     if rescore_summary:
@@ -514,7 +532,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     psm_ids = [m[0] for m in meta]
     spec_ids = [m[2] for m in meta]
     results = os.path.join(output_directory, "results.sage.tsv")
-    output.write_results_native(results, "tsv", host, flat, list(order), psm_ids, filenames, spec_ids, [rtp, post])
+    output.write_results_native(results, "tsv", host, flat, list(order), psm_ids, filenames, spec_ids, [rtp, post], groups)
     paths = [results]
     if sp["annotate_matches"]:
         fp = os.path.join(output_directory, "matched_fragments.sage.tsv")

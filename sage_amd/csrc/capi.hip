@@ -69,6 +69,14 @@ struct SageHostDb {
     HostDb db;
 };
 
+struct SageGroupStrings {
+    std::vector<std::string> strings;
+};
+
+struct SageGroupGraph {
+    GroupGraph g;
+};
+
 struct SageDeviceDb {
     int device = 0;
     uint64_t serial = next_db_serial();  // never reused: what a batch's stored precursor windows name their index by (WindowKey)
@@ -254,6 +262,55 @@ int sage_hip_rescore(int device, const SageRescoreInput* in, SageRescoreOutput* 
     const int rc = rescore_on_device(device, *in, *out, err);
     return rc == SAGE_HIP_OK ? rc : fail(rc, err);
 }
+
+// protein groups and picked protein-group FDR (rescore.hip, groups.cpp)
+int sage_hip_protein_groups(int device, const SageHostDb* db, const SageGroupInput* in, SageGroupOutput* out) {
+    if (!db || !in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_protein_groups: null argument");
+    if (sage_hip_device_count() <= 0)
+        return fail(SAGE_HIP_ERR_NO_DEVICE, "sage_hip_protein_groups: no HIP device (there is no CPU fallback)");
+    if (in->n >= (1ull << 31)) return fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_protein_groups: more than 2^31 features");
+    out->strings = nullptr;
+    out->n_strings = out->passing_protein_group = 0;
+    out->n_groups = out->n_meta_peptides = out->cover_rounds = 0;
+    out->device_ms = 0.0f;
+    out->host_graph_ms = 0.0;
+    if (in->n && (!in->features || !in->peptide_q || !in->discriminant_score || !out->num_protein_groups || !out->protein_group_q ||
+                  !out->string_id))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_protein_groups: null array");
+    std::unique_ptr<SageGroupStrings> table(new SageGroupStrings);
+    if (in->n) {
+        std::string err;
+        const int rc = protein_groups_on_device(device, db->db, *in, *out, table->strings, err);
+        if (rc != SAGE_HIP_OK) return fail(rc, err);
+    }
+    out->n_strings = table->strings.size();
+    out->strings = table.release();
+    return SAGE_HIP_OK;
+}
+const char* sage_hip_group_string(const SageGroupStrings* strings, uint64_t id) {
+    return strings && id < strings->strings.size() ? strings->strings[id].c_str() : nullptr;
+}
+void sage_hip_group_strings_free(SageGroupStrings* strings) { delete strings; }
+
+int sage_hip_group_graph_build(const SageHostDb* db, const uint32_t* peptides, uint64_t n, SageGroupGraph** out) {
+    if (!db || !out || (n && !peptides)) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_group_graph_build: null argument");
+    for (uint64_t i = 0; i < n; ++i)
+        if (peptides[i] >= db->db.n_peptides() || (i && peptides[i] <= peptides[i - 1]))
+            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_group_graph_build: peptide indices must be in range, ascending and distinct");
+    std::unique_ptr<SageGroupGraph> g(new SageGroupGraph);
+    build_group_graph(db->db, NameIndex(db->db), peptides, n, g->g);
+    *out = g.release();
+    return SAGE_HIP_OK;
+}
+int sage_hip_group_graph_view(const SageGroupGraph* graph, SageGroupGraphView* out) {
+    if (!graph || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_group_graph_view: null argument");
+    const GroupGraph& g = graph->g;
+    *out = SageGroupGraphView{(uint32_t)g.protein_name.size(), g.n_meta, g.n_groups(), (uint64_t)g.edge_group.size(),
+                              g.protein_db_id.data(), g.protein_decoy.data(), g.group_off.data(), g.group_proteins.data(),
+                              g.evidence_off.data(), g.evidence.data(), g.edge_group.data(), g.edge_meta.data()};
+    return SAGE_HIP_OK;
+}
+void sage_hip_group_graph_free(SageGroupGraph* graph) { delete graph; }
 
 int sage_hip_predict_rt(int device, const SageRtInput* in, SageRtOutput* out) {
     if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_predict_rt: null argument");
@@ -518,6 +575,26 @@ int sage_hip_write_results(const char* path, int format, const SageHostDb* db, c
     if (!write_results(path, format, db->db, features, n, order, psm_id, filenames, n_files, spec_ids, post, err))
         return fail(SAGE_HIP_ERR_INVALID, err);
     return SAGE_HIP_OK;
+}
+int sage_hip_write_results_grouped(const char* path, int format, const SageHostDb* db, const SageFeature* features, uint64_t n,
+                                   const uint64_t* order, const uint64_t* psm_id, const char* const* filenames, uint32_t n_files,
+                                   const char* const* spec_ids, const SagePostColumns* post, const SageGroupColumns* groups) {
+    if (!path || !db || (n && (!features || !psm_id || !filenames || !spec_ids)))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results_grouped: null argument");
+    if (format != SAGE_FORMAT_TSV && format != SAGE_FORMAT_PIN)
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results_grouped: unknown format");
+    for (uint64_t r = 0; order && r < n; ++r)
+        if (order[r] >= n) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results_grouped: order entry out of range");
+    for (uint64_t s = 0; groups && groups->strings && s < groups->n_strings; ++s)
+        if (!groups->strings[s]) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results_grouped: null string");
+    std::string err;
+    if (!write_results_grouped(path, format, db->db, features, n, order, psm_id, filenames, n_files, spec_ids, post, groups, err))
+        return fail(SAGE_HIP_ERR_INVALID, err);
+    return SAGE_HIP_OK;
+}
+uint64_t sage_hip_hostdb_protein_name(const SageHostDb* db, uint64_t id, char* out, uint64_t cap) {
+    if (!db || id >= db->db.protein_names.size()) return 0;
+    return copy_out(db->db.protein_names[id], out, cap);
 }
 int sage_hip_hostdb_feature_peptides(const SageHostDb* db, const uint32_t* peptide_idx, uint64_t n, uint64_t* seq_off, uint8_t* seq,
                                      float* monoisotopic) {

@@ -111,6 +111,35 @@ bool write_tmt(const char* path, const char* const* headers, uint32_t n_labels, 
                const char* const* spec_ids, const float* ion_injection_time, const float* intensity, const char* const* filenames,
                uint32_t n_files, std::string& err);
 
+// groups.cpp: the host half of protein grouping (protein_grouping.rs:159-231 ProteinGrouper::build)
+struct GroupGraph {
+    std::vector<uint32_t> protein_name;   // [ProteinIx] dense id of the protein's name (NameIndex), in numbering order
+    std::vector<uint8_t> protein_decoy;   // [ProteinIx]
+    std::vector<uint32_t> protein_db_id;  // [ProteinIx] a HostDb protein id that carries the name
+    uint32_t n_meta = 0;                  // distinct meta-peptides
+    std::vector<uint64_t> group_off;      // [groups + 1] into group_proteins (ascending ProteinIx inside a group)
+    std::vector<uint32_t> group_proteins;
+    std::vector<uint64_t> evidence_off;   // [groups + 1] into evidence: the group's ascending meta-peptide indices
+    std::vector<uint32_t> evidence;
+    std::vector<uint32_t> edge_group, edge_meta;  // one edge per evidence entry, in group order
+    uint32_t n_groups() const { return group_off.empty() ? 0u : (uint32_t)(group_off.size() - 1); }
+};
+struct NameIndex {  // HostDb protein id -> dense id of its name (two FASTA entries with one accession are one protein)
+    std::vector<uint32_t> of_protein;
+    uint32_t n_names = 0;
+    explicit NameIndex(const HostDb& db);
+};
+// peptides: ascending, distinct (the selected set P of one pass)
+void build_group_graph(const HostDb& db, const NameIndex& names, const uint32_t* peptides, uint64_t n, GroupGraph& out);
+// ProteinGroup::format: the group's names (decoy tag where decoy && generate_decoys), sorted, joined by '/'
+std::string group_string(const HostDb& db, const GroupGraph& g, uint32_t group);
+// rescore.hip: sage_hip_protein_groups on the device; `strings` receives the distinct protein_groups strings
+int protein_groups_on_device(int device, const HostDb& db, const SageGroupInput& in, SageGroupOutput& out, std::vector<std::string>& strings,
+                             std::string& err);
+bool write_results_grouped(const char* path, int format, const HostDb& db, const SageFeature* f, uint64_t n, const uint64_t* order,
+                           const uint64_t* psm_id, const char* const* filenames, uint32_t n_files, const char* const* spec_ids,
+                           const SagePostColumns* post, const SageGroupColumns* groups, std::string& err);
+
 // f32 residue masses, mass.rs:64-76
 float residue_mass(uint8_t aa);
 // IonSeries (ion_series.rs:36-85) for a flat peptide record; writes L-1 masses to out

@@ -144,8 +144,19 @@ std::string scan_number(const char* id) {
 bool write_results(const char* path, int format, const HostDb& db, const SageFeature* f, uint64_t n, const uint64_t* order,
                    const uint64_t* psm_id, const char* const* filenames, uint32_t n_files, const char* const* spec_ids,
                    const SagePostColumns* post, std::string& err) {
+    return write_results_grouped(path, format, db, f, n, order, psm_id, filenames, n_files, spec_ids, post, nullptr, err);
+}
+
+// the same rows with protein_groups / num_protein_groups / protein_group_q from `groups` (nullable, and each array nullable: the
+// Feature defaults None, 0 and 1.0)
+bool write_results_grouped(const char* path, int format, const HostDb& db, const SageFeature* f, uint64_t n, const uint64_t* order,
+                           const uint64_t* psm_id, const char* const* filenames, uint32_t n_files, const char* const* spec_ids,
+                           const SagePostColumns* post, const SageGroupColumns* groups, std::string& err) {
     static const SagePostColumns kNone{};
+    static const SageGroupColumns kNoGroups{};
     const SagePostColumns& pc = post ? *post : kNone;
+    const SageGroupColumns& gc = groups ? *groups : kNoGroups;
+    const bool group_strings = gc.strings && gc.string_id;
     FILE* fh = std::fopen(path, "wb");
     if (!fh) {
         err = std::string("cannot open ") + path;
@@ -173,9 +184,18 @@ bool write_results(const char* path, int format, const HostDb& db, const SageFea
             itoa(out, psm_id[i]);
             str(out, db.peptide_string(pep));
             str(out, db.peptide_proteins(pep));
-            out += '\t';  // protein_groups: None
+            if (group_strings) {
+                if (gc.string_id[i] >= gc.n_strings) {
+                    err = "feature " + std::to_string(i) + ": protein-group string id out of range";
+                    ok = false;
+                    break;
+                }
+                str(out, gc.strings[gc.string_id[i]]);
+            } else {
+                out += '\t';  // protein_groups: None
+            }
             itoa(out, db.pep_protein_off[pep + 1] - db.pep_protein_off[pep]);
-            itoa(out, 0);  // num_protein_groups
+            itoa(out, gc.num_protein_groups ? gc.num_protein_groups[i] : 0u);
             str(out, filenames[x.file_id]);
             str(out, spec_ids[i]);
             itoa(out, x.rank);
@@ -211,7 +231,7 @@ bool write_results(const char* path, int format, const HostDb& db, const SageFea
             f32(out, col(pc.spectrum_q, i, 1.0f));
             f32(out, col(pc.peptide_q, i, 1.0f));
             f32(out, col(pc.protein_q, i, 1.0f));
-            f32(out, 1.0f);  // protein_group_q
+            f32(out, col(gc.protein_group_q, i, 1.0f));
             f32(out, x.ms2_intensity);
         } else {  // serialize_pin, runner.rs:938-1084
             const unsigned z = x.charge;

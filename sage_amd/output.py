@@ -5,9 +5,10 @@ sage-cli/src/runner.rs:687-780 (serialize_feature), :782-828 (serialize_fragment
 written with `itoa`, floats with `ryu` (shortest digits that round-trip, Rust `ryu::Buffer::format`), reproduced by
 `ryu_f32` / `ryu_f64` below.  sage_discriminant_score, posterior_error, spectrum_q, peptide_q and protein_q come from the
 device rescoring (sage_hip_rescore), aligned_rt / predicted_rt / delta_rt_model / predicted_mobility / delta_mobility from
-sage_hip_predict_rt when `predict_rt` is on (the default, input.rs:372); without it, and for the protein-group columns
-nothing here computes, the defaults Feature gets in build_features (scoring.rs:576-592): predicted_rt 0.0, aligned_rt = rt,
-delta_rt_model / delta_ims_model 0.999, protein_group_q 1.0.  `results.sage.pin` follows runner.rs:938-1135.
+sage_hip_predict_rt when `predict_rt` is on (the default, input.rs:372), protein_groups / num_protein_groups / protein_group_q
+from sage_hip_protein_groups; where a stage did not run, the defaults Feature gets in build_features (scoring.rs:576-592):
+predicted_rt 0.0, aligned_rt = rt, delta_rt_model / delta_ims_model 0.999, no protein groups (an empty field, 0),
+protein_group_q 1.0.  `results.sage.pin` follows runner.rs:938-1135.
 """
 import ctypes
 import re
@@ -70,9 +71,11 @@ def ryu_f64(x) -> str:
 DEFAULT_POST = dict(discriminant_score=0.0, posterior_error=1.0, spectrum_q=1.0, peptide_q=1.0, protein_q=1.0)
 
 
-def feature_row(psm_id: int, f, db, filename: str, scannr: str, post: Optional[dict] = None) -> List[str]:
+def feature_row(psm_id: int, f, db, filename: str, scannr: str, post: Optional[dict] = None, protein_groups: Optional[str] = None,
+                num_protein_groups: int = 0, protein_group_q=1.0) -> List[str]:
     """serialize_feature (runner.rs:687-780) for one SageFeature record `f` (numpy void of FEATURE_DTYPE); `post` = the
-    rescoring outputs of this PSM (defaults of scoring.rs:576-592 when the rescoring did not run)."""
+    rescoring outputs of this PSM (defaults of scoring.rs:576-592 when the rescoring did not run); protein_groups /
+    num_protein_groups / protein_group_q = the protein-group stage's (None, 0, 1.0 when it did not run)."""
     post = dict(DEFAULT_POST, **(post or {}))
     pep = int(f["peptide_idx"])
     num_proteins, semi = db.peptide_info(pep)
@@ -81,7 +84,8 @@ def feature_row(psm_id: int, f, db, filename: str, scannr: str, post: Optional[d
     predicted_rt, delta_rt = post.get("predicted_rt", 0.0), post.get("delta_rt_model", 0.999)
     predicted_ims, delta_ims = post.get("predicted_ims", 0.0), post.get("delta_ims_model", 0.999)
     return [
-        str(psm_id), db.peptide_string(pep), db.peptide_proteins(pep), "", str(num_proteins), "0", filename, scannr,
+        str(psm_id), db.peptide_string(pep), db.peptide_proteins(pep), protein_groups or "", str(num_proteins), str(int(num_protein_groups)),
+        filename, scannr,
         str(int(f["rank"])), str(int(f["label"])), ryu_f32(f["expmass"]), ryu_f32(f["calcmass"]), str(int(f["charge"])),
         str(int(f["peptide_len"])), str(int(f["missed_cleavages"])), str(semi), ryu_f32(f["isotope_error"]),
         ryu_f32(f["delta_mass"]), ryu_f32(f["average_ppm"]), ryu_f64(f["hyperscore"]), ryu_f64(f["delta_next"]),
@@ -89,7 +93,7 @@ def feature_row(psm_id: int, f, db, filename: str, scannr: str, post: Optional[d
         ryu_f32(predicted_ims), ryu_f32(delta_ims), str(int(f["matched_peaks"])), str(int(f["longest_b"])), str(int(f["longest_y"])),
         ryu_f32(f["longest_y_pct"]), ryu_f32(f["matched_intensity_pct"]), str(int(f["scored_candidates"])),
         ryu_f64(f["poisson"]), ryu_f32(post["discriminant_score"]), ryu_f32(post["posterior_error"]),
-        ryu_f32(post["spectrum_q"]), ryu_f32(post["peptide_q"]), ryu_f32(post["protein_q"]), ryu_f32(1.0),
+        ryu_f32(post["spectrum_q"]), ryu_f32(post["peptide_q"]), ryu_f32(post["protein_q"]), ryu_f32(protein_group_q),
         ryu_f32(f["ms2_intensity"]),
     ]
 
@@ -186,10 +190,11 @@ def write_pin(path: str, rows: Sequence[List[str]]) -> None:
             fh.write(_record(r) + "\n")
 
 
-def write_results_native(path: str, fmt: str, db, features, order, psm_ids, filenames, spec_ids, post=None) -> None:
+def write_results_native(path: str, fmt: str, db, features, order, psm_ids, filenames, spec_ids, post=None, groups=None) -> None:
     """results.sage.tsv (fmt "tsv") / results.sage.pin (fmt "pin") through the C++ writer (sage_hip_write_results): the same
     bytes as feature_row / pin_row + write_features / write_pin, without a Python loop per PSM.  `post`: RescoreResult-like
-    and / or RtPrediction-like objects (attributes named like SagePostColumns), or None."""
+    and / or RtPrediction-like objects (attributes named like SagePostColumns), or None.  `groups`: a ProteinGroupResult-like
+    object (strings, string_id, num_protein_groups, protein_group_q) — then through sage_hip_write_results_grouped."""
     import ctypes as C
 
     from . import _lib as L
@@ -211,9 +216,18 @@ def write_results_native(path: str, fmt: str, db, features, order, psm_ids, file
                 assert len(a) == n
                 keep.append(a)
                 setattr(cols, k, L.as_ptr(a, C.c_float))
-    L.check(L.load().sage_hip_write_results(path.encode(), {"tsv": 0, "pin": 1}[fmt], db._h, f.ctypes.data, n,
-                                            None if order_a is None else L.as_ptr(order_a, C.c_uint64), L.as_ptr(ids, C.c_uint64),
-                                            names, len(filenames), specs, C.byref(cols)))
+    args = (path.encode(), {"tsv": 0, "pin": 1}[fmt], db._h, f.ctypes.data, n, None if order_a is None else L.as_ptr(order_a, C.c_uint64),
+            L.as_ptr(ids, C.c_uint64), names, len(filenames), specs, C.byref(cols))
+    if groups is None:
+        L.check(L.load().sage_hip_write_results(*args))
+        return
+    sid = np.ascontiguousarray(groups.string_id, dtype=np.uint32)
+    num = np.ascontiguousarray(groups.num_protein_groups, dtype=np.uint32)
+    gq = np.ascontiguousarray(groups.protein_group_q, dtype=np.float32)
+    assert len(sid) == n and len(num) == n and len(gq) == n
+    table = (C.c_char_p * max(len(groups.strings), 1))(*[s.encode() for s in groups.strings])
+    gcols = L.SageGroupColumns(table, len(groups.strings), L.as_ptr(sid, C.c_uint32), L.as_ptr(num, C.c_uint32), L.as_ptr(gq, C.c_float))
+    L.check(L.load().sage_hip_write_results_grouped(*args, C.byref(gcols)))
 
 
 LFQ_HEADERS = ["peptide", "charge", "proteins", "q_value", "score", "spectral_angle"]
