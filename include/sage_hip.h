@@ -338,6 +338,11 @@ int sage_hip_debug_filter_counters(SageScorer* scorer, unsigned long long* out4)
  * by the whole wavefront) since the scorer was created. out2[0] chunks of candidates taken that way, [1] the (ion, fragment charge)
  * matches added up for them. */
 int sage_hip_debug_heavy_counters(SageScorer* scorer, unsigned long long* out2);
+/* Debug aid, same condition: the route those chunks took. out2[0] chunks whose (ion, fragment charge) items went through one lookup
+ * trip, one item per lane, with the three sums made from LDS, [1] chunks that took a trip per fragment charge and the sums by
+ * readlane (more than 64 items, not the candidate's last chunk, a kernel instance without the route, or
+ * SAGE_HIP_DEBUG_FLAGS=262144 at scorer creation, which forces it). */
+int sage_hip_debug_heavy_routes(SageScorer* scorer, unsigned long long* out2);
 /* Debug aid (no condition): *out = 1 if the first pass of the scorer's last scoring step handed its preliminary lists to the
  * rescoring kernel in rows by schedule position, 0 if in the arrays indexed by spectrum (SAGE_HIP_DEBUG_FLAGS=131072 at scorer
  * creation forces the latter; so does every step that is not the plain narrow search with schedule records). */

@@ -2046,7 +2046,8 @@ static int score_resident_locked(SageScorer* s, SageDeviceBatch* b, SageFeature*
             // the array — its spectra are a range of the launch SCHEDULE — and gathering them at the end of the step costs 33 us of
             // scattered stores across the link, joining the parts for one contiguous copy 20 us of cross-stream wake-up:
             // profiles/r05_small_step_timeline.txt); a step in one part keeps them on the device and sends them home in one
-            // contiguous run behind its last kernel
+            // contiguous run behind its last kernel (round 13 had the kernels of a one-part step of 500 000 spectra store them home
+            // too, to save that run's ~35 us: rescore_kernel took 0.2 ms longer — DESIGN.md 10)
             uint32_t* const counts_to = (epilogue && ways > 1 && direct) ? count_view : o.out_count.p;
             rc = enqueue_compute(s, v, ow, true, s->exact_always ? MODE_EXACT : MODE_SCORE, st, rec, b->maybe_wide, start, counts_to, 0,
                                  defer_retry ? 1 : 0, b->widest);
@@ -2515,6 +2516,19 @@ int sage_hip_debug_heavy_counters(SageScorer* s, unsigned long long* out2) {
     out2[0] = out2[1] = 0;
     for (size_t b = 0; b < DBG_BLOCKS; b++)
         for (uint32_t k = 0; k < 2; k++) out2[k] += all[b * DBG_PRUNE_WORDS + 8 + k];
+    return SAGE_HIP_OK;
+}
+
+// debugging aid: which route the chunks of sage_hip_debug_heavy_counters took (kernels.hip: DBG_HEAVY_ONE_TRIP / _PER_CHARGE) — all
+// items in one lookup trip with the sums from LDS, or a trip per fragment charge with the sums by readlane
+int sage_hip_debug_heavy_routes(SageScorer* s, unsigned long long* out2) {
+    if (!s || !out2) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+    if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
+    std::vector<unsigned long long> all((size_t)DBG_BLOCKS * DBG_PRUNE_WORDS);
+    HIP_TRY(hipMemcpy(all.data(), s->dbg.p + (size_t)DBG_BLOCKS * 32, all.size() * 8, hipMemcpyDeviceToHost));
+    out2[0] = out2[1] = 0;
+    for (size_t b = 0; b < DBG_BLOCKS; b++)
+        for (uint32_t k = 0; k < 2; k++) out2[k] += all[b * DBG_PRUNE_WORDS + 10 + k];
     return SAGE_HIP_OK;
 }
 

@@ -514,6 +514,21 @@ SAGE_HD KindSeg kind_seg_next(const KindSeg& g, uint32_t lm1) {
 }
 SAGE_HD uint64_t kind_seg_mask(const KindSeg& g) { return g.len >= 64u ? ~0ull : ((1ull << g.len) - 1ull) << (g.lo & 63u); }
 
+// The ITEMS of a heavy candidate's chunk in one list: M1 / M2 / M3 have bit i set where ion i of the chunk passed the bitmap at
+// fragment charge 1 / 2 / 3, and the reference visits the (ion, charge) pairs ion by ion, charge by charge.  coop_items_below(i):
+// the items of the ions below bit i (i == 64: all of them, N) — so a kind segment [lo, lo + len) owns the positions
+// [coop_items_below(lo), coop_items_below(lo + len)); coop_item_pos: the position of the item (i, c), which must be set in Mc.
+// The one-trip route of kernels.hip: score_candidates lays a chunk's lookups out this way (lane i == ion i: the counts below a lane
+// are v_mbcnt of the wave-uniform masks).  tests/test_coop_items_emulation.py holds both to the plain enumeration.
+constexpr uint32_t COOP_ITEMS_CAP = 64;  // items of a chunk the one-trip route takes: one per lane
+SAGE_HD uint32_t coop_items_below(uint64_t M1, uint64_t M2, uint64_t M3, uint32_t i) {
+    const uint64_t below = i >= 64u ? ~0ull : (1ull << i) - 1ull;
+    return (uint32_t)(__builtin_popcountll(M1 & below) + __builtin_popcountll(M2 & below) + __builtin_popcountll(M3 & below));
+}
+SAGE_HD uint32_t coop_item_pos(uint64_t M1, uint64_t M2, uint64_t M3, uint32_t i, uint32_t c) {
+    return coop_items_below(M1, M2, M3, i) + (c >= 2u ? (uint32_t)((M1 >> i) & 1ull) : 0u) + (c >= 3u ? (uint32_t)((M2 >> i) & 1ull) : 0u);
+}
+
 // ---- Score (scoring.rs:17-30) -------------------------------------------------------------------
 struct Score {
     uint32_t peptide;

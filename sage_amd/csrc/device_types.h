@@ -66,8 +66,8 @@ __host__ __device__ inline size_t tm_lut_index(uint32_t t, uint32_t c, uint32_t 
 // SAGE_HIP_PHASE_CLOCKS=1: DevWork::dbg holds DBG_BLOCKS rows of 32 words (phase cycles and byte counts, kernels.hip: PhaseClock)
 // and behind them DBG_BLOCKS rows of DBG_PRUNE_WORDS words: what the rescoring prune dropped (words 0..3, sage_hip_debug_prune_counters)
 // the trips of the bitmap filter's two routes (words 4..7, sage_hip_debug_filter_counters) and what the cooperative path of the heavy
-// candidates took (words 8..9, sage_hip_debug_heavy_counters)
-constexpr uint32_t DBG_BLOCKS = 4096, DBG_PRUNE_WORDS = 10;
+// candidates took (words 8..9, sage_hip_debug_heavy_counters) and by which route (words 10..11, sage_hip_debug_heavy_routes)
+constexpr uint32_t DBG_BLOCKS = 4096, DBG_PRUNE_WORDS = 12;
 constexpr size_t DBG_TOTAL_WORDS = (size_t)DBG_BLOCKS * (32 + DBG_PRUNE_WORDS);
 
 struct DevScorer {

@@ -114,6 +114,9 @@ enum { DBG_FILTER_FLAT_CHUNKS = 4, DBG_FILTER_FLAT_TRIPS = 5, DBG_FILTER_FLAT_WO
 // ... and the cooperative path behind the prune (sage_hip_debug_heavy_counters): the chunks of heavy candidates the wavefront took
 // together, and the (ion, charge) matches it added up for them
 enum { DBG_HEAVY_CHUNKS = 8, DBG_HEAVY_ITEMS = 9 };
+// ... and which of its two routes those chunks took (sage_hip_debug_heavy_routes): all items in one lookup trip with the sums from
+// LDS, or a trip per fragment charge with the sums by readlane (more than 64 items, not the last chunk, an instance without the route)
+enum { DBG_HEAVY_ONE_TRIP = 10, DBG_HEAVY_PER_CHARGE = 11 };
 enum { DBG_NARROW_LUT = 26, DBG_NARROW_CELLS = 27, DBG_RESCORE = 28, DBG_TILE_LUT = 29, DBG_TILE_CELLS = 30, DBG_TILE_CAND = 31 };
 struct PhaseClock {
     unsigned long long* slot;
@@ -149,6 +152,9 @@ struct PhaseClock {
             atomicAdd(&prune[DBG_HEAVY_CHUNKS], 1ull);
             atomicAdd(&prune[DBG_HEAVY_ITEMS], (unsigned long long)items);
         }
+    }
+    __device__ __forceinline__ void heavy_route(bool one_trip) {  // wave-uniform, once per chunk of a heavy candidate
+        if (slot && (threadIdx.x & 63u) == 0) atomicAdd(&prune[one_trip ? DBG_HEAVY_ONE_TRIP : DBG_HEAVY_PER_CHARGE], 1ull);
     }
     __device__ __forceinline__ void prune_outcome(bool left_early, bool any_pass) {  // once per scoring round
         if (slot && (threadIdx.x & 63u) == 0) {
@@ -186,6 +192,7 @@ struct NoClock {
     __device__ __forceinline__ void prune_outcome(bool, bool) {}
     __device__ __forceinline__ void filter_trips(bool, uint32_t, uint32_t) {}
     __device__ __forceinline__ void heavy(uint32_t) {}
+    __device__ __forceinline__ void heavy_route(bool) {}
     __device__ __forceinline__ void start(unsigned long long*, uint32_t, uint32_t) {}
     __device__ __forceinline__ void mark(int) {}
     __device__ __forceinline__ void rebase(uint32_t) {}
@@ -3265,6 +3272,10 @@ __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevS
         // (SAGE_HIP_DEBUG_FLAGS=32: tests switch it off; 32768: tests take a lane from its first hit)
         uint64_t bigs = (sc.dbg_flags & 32u) ? 0ull : __ballot(hc > ((sc.dbg_flags & 32768u) ? 0u : COOP_MIN_HITS));
         if ((uint32_t)__popcll(bigs) > COOP_MAX_LANES && !(sc.dbg_flags & 64u)) bigs = 0ull;  // (64: tests take every heavy lane)
+        // (the one-trip route below works in the bitmap's bytes: only where the dense list may, and only in the instances that carry
+        // the flat filter — the general ones spill as it is, LONG keeps its registers.  262144: tests and A/B runs keep every heavy
+        // chunk on the trip per charge and the readlane sums)
+        const bool coop_lds = FLAT && DENSE && dense_ok && !(sc.dbg_flags & 262144u) && __ballot(j0 + 64u < nions) == 0ull;
         while (bigs) {
             const uint32_t L = (uint32_t)__ffsll((long long)bigs) - 1;
             bigs &= bigs - 1;
@@ -3274,7 +3285,91 @@ __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevS
             const bool on1 = (M1 >> lane) & 1ull, on2 = (M2 >> lane) & 1ull, on3 = (M3 >> lane) & 1ull;
             float it1 = 0.f, it2 = 0.f, it3 = 0.f, tm1 = 0.f, tm2 = 0.f, tm3 = 0.f;
             bool ok1 = false, ok2 = false, ok3 = false;
-            if (on1 || on2 || on3) {
+            // ---- ONE TRIP (round 13): the chunk's N <= 64 (ion, charge) items, one per lane, in the reference's order (core.h:
+            //      coop_item_pos), instead of one trip per fragment charge with most lanes idle in the second and third; and their
+            //      three ordered sums — n-terminal intensities, the others', ppm terms — by three lanes over LDS instead of a
+            //      wave-uniform loop of readlanes per match.  The LDS is the bitmap's, free under the dense list's condition (this is
+            //      the last chunk of every lane, and no later round reads the bitmap): 64 descriptor words and 3 x 64 floats.  The dense
+            //      list below overwrites them, after the barrier that ends this block.
+            const uint32_t N = (uint32_t)(__popcll(M1) + __popcll(M2) + __popcll(M3));
+            const bool one_trip = coop_lds && N <= COOP_ITEMS_CAP;
+            if (pc.slot) pc.heavy_route(one_trip);
+            float sum_b = 0.f, sum_y = 0.f, sum_p = 0.f;  // (one_trip: the candidate's three sums afterwards, wave-uniform)
+            if (one_trip) {
+                uint32_t* const cD = (uint32_t*)pbm;  // [64] position -> ion bit | n-terminal kind << 8 | charge << 16
+                float* const cS = (float*)(cD + 64);  // [3][64] position -> intensity (n-terminal), intensity (other), ppm term
+                float ionv = 0.f;
+                if (on1 || on2 || on3) ionv = db.ions[base_L + j0 + lane];
+                // the chunk's n-terminal bits, a kind segment at a time (wave-uniform)
+                uint64_t NT = 0ull;
+                {
+                    uint64_t rem = M1 | M2 | M3;
+                    for (KindSeg g = kind_seg_first(j0, lm1_L); rem && g.lo < 64u; g = kind_seg_next(g, lm1_L)) {
+                        const uint64_t seg = kind_seg_mask(g);
+                        rem &= ~seg;
+                        if ((nterm_mask >> g.kind) & 1u) NT |= seg;
+                    }
+                }
+                // (== coop_items_below(M1, M2, M3, lane): the masks are wave-uniform, the counts below a lane are v_mbcnt)
+                uint32_t p1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(M1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M1, 0u));
+                p1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(M2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M2, p1));
+                p1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(M3 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M3, p1));
+                const uint32_t p2 = p1 + (on1 ? 1u : 0u), p3 = p2 + (on2 ? 1u : 0u);  // (coop_item_pos of charges 2 and 3)
+                const uint32_t dsc = lane | ((uint32_t)((NT >> lane) & 1ull) << 8);
+                lds_sync();  // (the filter's reads of the bitmap, an earlier heavy candidate's reads of these words: all done)
+                if (on1) cD[p1] = dsc | (1u << 16);
+                if (on2) cD[p2] = dsc | (2u << 16);
+                if (on3) cD[p3] = dsc | (3u << 16);
+                lds_sync();
+                const uint32_t item = lane < N ? cD[lane] : 0u;
+                // (the item's ion: its owner lane's, through the crossbar — every lane takes part)
+                const float iv = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)((item & 63u) << 2), (int)__float_as_uint(ionv)));
+                // A slot that holds no n-terminal / no other / no match at all holds +0.0f, and so does every slot from N on: x + +0.0f
+                // is x bit for bit for every x but -0.0f, and a sum that began at +0.0f (Score's) is never -0.0f — round to nearest
+                // gives -0.0f only from two negative zeros.  So the three lanes below add EVERY slot of their array, four per read,
+                // and leave the reference's bits: its additions in its order, and additions of +0.0f between them.
+                float sb = 0.f, sy = 0.f, st = 0.f;
+                bool ok = false;
+                if (lane < N) {
+                    const uint32_t c = item >> 16;
+                    float mz = c == 2u ? iv * 0.5f : iv;  // (core.h: fragment_mz — x / 1 and x / 2 bit for bit)
+                    if (any_fz3 && c == 3u) mz = fragment_mz<FAST>(iv, 3u);
+                    float flo, fhi;
+                    tol_bounds_mode<FAST>(sc.fragment_tol, sym_tol, mz, flo, fhi);
+                    const int pk = select_peak_lut(pm, pi, P, plut, inv_w, flo, fhi);
+                    if (pk >= 0) {
+                        const float peak_mass = pm[pk], peak_intensity = pi[pk];
+                        ok = true;
+                        if (item & 0x100u) sb = peak_intensity;
+                        else sy = peak_intensity;
+                        st = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
+                    }
+                }
+                cS[lane] = sb;
+                cS[64u + lane] = sy;
+                cS[128u + lane] = st;
+                // the matched flags, back in ion space: item p's is bit p of the ballot, an ion's items sit at p1 / p2 / p3
+                const uint64_t Kp = __ballot(ok);
+                ok1 = on1 && ((Kp >> (p1 & 63u)) & 1ull);
+                ok2 = on2 && ((Kp >> (p2 & 63u)) & 1ull);
+                ok3 = on3 && ((Kp >> (p3 & 63u)) & 1ull);
+                lds_sync();
+                float acc = lane == 0u ? lane_valuef(s.summed_b, L) : lane == 1u ? lane_valuef(s.summed_y, L) : lane_valuef(s.ppm_difference, L);
+                if (lane < 3u) {
+                    const float4* const a = (const float4*)(cS + 64u * lane);
+                    float4 v = a[0];
+                    for (uint32_t q = 4u; q < N; q += 4u) {  // (wave-uniform trip count)
+                        const float4 nv = a[q >> 2];  // (the next four slots are in flight under this four's additions)
+                        acc += v.x; acc += v.y; acc += v.z; acc += v.w;
+                        v = nv;
+                    }
+                    acc += v.x; acc += v.y; acc += v.z; acc += v.w;
+                }
+                sum_b = lane_valuef(acc, 0u);
+                sum_y = lane_valuef(acc, 1u);
+                sum_p = lane_valuef(acc, 2u);
+                lds_sync();  // (the three lanes have read: the next heavy candidate, or the dense list, may write)
+            } else if (on1 || on2 || on3) {
                 const float ionv = db.ions[base_L + j0 + lane];
 #define SAGE_COOP_LOOKUP(C, ON, OK, IT, TM)                                                              \
     if (ON) {                                                                                            \
@@ -3296,7 +3391,8 @@ TM = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
             }
             const uint64_t K1 = __ballot(ok1), K2 = __ballot(ok2), K3 = __ballot(ok3);
             // the candidate's accumulators, wave-uniform while its matches are added in (ion, charge) order
-            float u_sb = lane_valuef(s.summed_b, L), u_sy = lane_valuef(s.summed_y, L), u_pp = lane_valuef(s.ppm_difference, L);
+            float u_sb = sum_b, u_sy = sum_y, u_pp = sum_p;
+            if (!one_trip) { u_sb = lane_valuef(s.summed_b, L); u_sy = lane_valuef(s.summed_y, L); u_pp = lane_valuef(s.ppm_difference, L); }
             uint32_t u_mm = (uint32_t)__builtin_amdgcn_readlane((int)mm, (int)L);
             RunReg u_b = lane_run(b_run, L);
             RunReg u_y = lane_run(y_run, L);
@@ -3314,6 +3410,7 @@ TM = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
                 u_mm += (uint32_t)(__popcll(K1 & seg) + __popcll(K2 & seg) + __popcll(K3 & seg)) << (nterm ? 0u : 16u);
                 if (nterm) run_matched_mask(u_b, S >> g.lo, g.idx0);
                 else run_matched_mask(u_y, S >> g.lo, g.idx0);
+                if (one_trip) continue;  // (the sums are made)
                 float acc = nterm ? u_sb : u_sy;
                 do {
                     const uint32_t bit = (uint32_t)__builtin_ctzll(S);

@@ -43,7 +43,11 @@ def gpu_counters(args, host, params, batch):
     print(f"# {args.config}: first {n} spectra on the device (profiling instance), {int(counts.sum())} PSMs, n_retry {t['n_retry']}, n_tied {t['n_tied']}"
           f" (a spectrum of the retry pass is scored twice)")
     print(f"chunks of heavy candidates taken together     {int(out[0])} ({out[0] / n:.2f} per spectrum)")
-    print(f"(ion, charge) items their add loop walked     {int(out[1])} ({out[1] / n:.2f} per spectrum)")
+    print(f"(ion, charge) matches added up for them       {int(out[1])} ({out[1] / n:.2f} per spectrum)")
+    routes = np.zeros(2, np.uint64)
+    L.check(L.load().sage_hip_debug_heavy_routes(scorer._h, L.as_ptr(routes, C.c_uint64)))
+    print(f"... in one lookup trip, sums from LDS         {int(routes[0])} ({100.0 * routes[0] / max(int(out[0]), 1):.2f} %)")
+    print(f"... a trip per fragment charge (fallback)     {int(routes[1])} ({100.0 * routes[1] / max(int(out[0]), 1):.2f} %: more than 64 items, or not the last chunk)")
 
 
 def bitmap_of(peaks, tol):
