@@ -763,6 +763,41 @@ int sage_hip_write_results_grouped(const char* path, int format, const SageHostD
                                    const uint64_t* order, const uint64_t* psm_id, const char* const* filenames, uint32_t n_files,
                                    const char* const* spec_ids, const SagePostColumns* post, const SageGroupColumns* groups);
 
+/* ---- positional isomers of reported PSMs.  An ADDITION over the reference, which has no counterpart: the scores a
+ * localisation step would be built from.  Additive to ABI 6.
+ * Two peptides of a host database are positional isomers when their decoy flag, their residue bytes and the multiset of their
+ * modification masses are equal — the bit patterns of the non-zero entries of `mods` over the peptide's residues, of nterm and of
+ * cterm (each when neither NaN nor 0).  A group has at least two members; groups are numbered by ascending smallest member, members
+ * inside a group are ascending peptide indices. */
+/* group_of: [n_peptides], 0xFFFFFFFF = the peptide has no isomer.  group_off: [n_groups + 1] into members.
+ * Call once with group_off == NULL and members == NULL to get *n_groups and *n_members. */
+int sage_hip_hostdb_isomer_groups(const SageHostDb* db, uint32_t* group_of, uint64_t* group_off, uint32_t* members,
+                                  uint64_t* n_groups, uint64_t* n_members);
+
+/* Score (scoring.rs:41-67) as score_candidate leaves it (scoring.rs:675-767) */
+typedef struct SageCandidateScore {
+    double hyperscore;
+    float summed_b, summed_y, average_ppm;   /* average_ppm: ppm_difference after the division at the end of score_candidate */
+    uint32_t matched_b, matched_y, longest_b, longest_y;
+    uint32_t pad;
+} SageCandidateScore;
+
+/* For PSM slot s = i * report_psms + r (features / counts as sage_hip_score_resident returned them for this batch and scorer),
+ * score the peptides cand_pep[cand_off[s] .. cand_off[s+1]) against spectrum i in the state PSM r was scored in: with chimera,
+ * after remove_matched_peaks (scoring.rs:598-644) for PSMs 0 .. r-1 of `features`, exactly as sage_hip_annotate_resident
+ * replays it; without chimera, the spectrum as uploaded.  Precursor charge (-> max_fragment_charge): cand_charge[c], or
+ * features[s].charge where cand_charge is NULL or cand_charge[c] == 0.  No min_matched_peaks filter: every candidate gets
+ * its Score.  out: [cand_off[n * report_psms]].
+ * SAGE_HIP_ERR_INVALID, before any launch: cand_off not non-decreasing (or not starting at 0), a non-empty list on a slot with
+ * r >= counts[i], a peptide index >= n_peptides, a charge above 254 (the reference's u8 arithmetic around max_fragment_charge has no room left there).  No
+ * candidate at all: SAGE_HIP_OK without a launch. */
+int sage_hip_score_candidates_resident(SageScorer* scorer, SageDeviceBatch* batch, const SageFeature* features,
+                                       const uint32_t* counts, const uint64_t* cand_off, const uint32_t* cand_pep,
+                                       const uint8_t* cand_charge, SageCandidateScore* out);
+/* HIP-event times of the scorer's last sage_hip_score_candidates_resident call: the whole call on the scorer's stream (uploads
+ * and the copy back included) and the kernel alone. */
+int sage_hip_last_candidates_timing(const SageScorer* scorer, float* call_ms, float* kernel_ms);
+
 const char* sage_hip_last_error(void);
 int sage_hip_abi_version(void);
 

@@ -169,6 +169,11 @@ FEATURE_DTYPE = np.dtype(
 assert FEATURE_DTYPE.itemsize == 120
 
 THEORETICAL_DTYPE = np.dtype([("peptide_index", "<u4"), ("fragment_mz", "<f4")])
+# SageCandidateScore (sage_hip.h)
+CANDIDATE_SCORE_DTYPE = np.dtype([("hyperscore", "<f8"), ("summed_b", "<f4"), ("summed_y", "<f4"), ("average_ppm", "<f4"),
+                                  ("matched_b", "<u4"), ("matched_y", "<u4"), ("longest_b", "<u4"), ("longest_y", "<u4"),
+                                  ("pad", "<u4")])
+assert CANDIDATE_SCORE_DTYPE.itemsize == 40
 
 ION_KINDS = {"a": 0, "b": 1, "c": 2, "x": 3, "y": 4, "z": 5}
 TOL_KINDS = {"ppm": 0, "pct": 1, "da": 2}
@@ -392,6 +397,9 @@ def load():
         "sage_hip_hostdb_build_chunk": (C.c_int, [C.c_char_p, C.POINTER(SageDbParams), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
         "sage_hip_hostdb_merge_kept": (C.c_int, [C.POINTER(vp), C.POINTER(c_u8_p), C.c_uint32, C.POINTER(SageDbParams),
                                                  C.POINTER(vp)]),
+        "sage_hip_hostdb_isomer_groups": (C.c_int, [vp, c_u32_p, c_u64_p, c_u32_p, c_u64_p, c_u64_p]),
+        "sage_hip_score_candidates_resident": (C.c_int, [vp, vp, vp, c_u32_p, c_u64_p, c_u32_p, c_u8_p, vp]),
+        "sage_hip_last_candidates_timing": (C.c_int, [vp, c_float_p, c_float_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
@@ -417,6 +425,7 @@ EXPORTED_SYMBOLS = [
     "sage_hip_lfq_im", "sage_hip_mzml_mobility", "sage_hip_mzml_has_mobility",
     "sage_hip_protein_groups", "sage_hip_group_string", "sage_hip_group_strings_free", "sage_hip_group_graph_build",
     "sage_hip_group_graph_view", "sage_hip_group_graph_free", "sage_hip_hostdb_protein_name", "sage_hip_write_results_grouped",
+    "sage_hip_hostdb_isomer_groups", "sage_hip_score_candidates_resident", "sage_hip_last_candidates_timing",
 ]
 
 

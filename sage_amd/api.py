@@ -268,6 +268,20 @@ class IndexedDatabase:
                                                           C.byref(npk), L.as_ptr(prk, C.c_uint32), C.byref(nprk)))
         return pk, int(npk.value), prk, int(nprk.value)
 
+    def isomer_groups(self):
+        """Positional isomers: peptides with the same decoy flag, residues and multiset of modification masses.
+        Returns (group_of[n_peptides] u32, 0xFFFFFFFF = no isomer; group_off[n_groups + 1] u64 into members; members u32):
+        groups by ascending smallest member, members ascending."""
+        lib = L.load()
+        ng, nm = C.c_uint64(), C.c_uint64()
+        group_of = np.empty(self.n_peptides, dtype=np.uint32)
+        L.check(lib.sage_hip_hostdb_isomer_groups(self._h, L.as_ptr(group_of, C.c_uint32), None, None, C.byref(ng), C.byref(nm)))
+        group_off = np.zeros(int(ng.value) + 1, dtype=np.uint64)
+        members = np.zeros(max(int(nm.value), 1), dtype=np.uint32)
+        L.check(lib.sage_hip_hostdb_isomer_groups(self._h, L.as_ptr(group_of, C.c_uint32), L.as_ptr(group_off, C.c_uint64),
+                                                  L.as_ptr(members, C.c_uint32), C.byref(ng), C.byref(nm)))
+        return group_of, group_off, members[:int(nm.value)]
+
     def feature_peptides(self, peptide_idx):
         """(seq_off[n + 1], residues, monoisotopic[n]) of the peptides behind `n` PSMs — the per-Feature peptide data the
         retention-time / mobility models embed (retention_model.rs:44-62, mobility_model.rs:103-158)."""
@@ -811,6 +825,41 @@ class Scorer:
         L.check(lib.sage_hip_annotate_resident(self._h, dbatch._h, feats.ctypes.data_as(C.c_void_p),
                                                L.as_ptr(counts, C.c_uint32), C.byref(fr)))
         return off, arr
+
+    def score_candidates(self, dbatch: DeviceBatch, feats: np.ndarray, counts: np.ndarray, cand_off, cand_pep, cand_charge=None):
+        """score_candidate (scoring.rs:675-767) of given peptides against the spectra of the PSMs that score_resident returned for
+        this batch: PSM r of spectrum i is slot i * report_psms + r and gets the peptides cand_pep[cand_off[slot] : cand_off[slot + 1]],
+        scored on the spectrum as PSM r saw it (chimera: after the peak removal of the ranks before it).  cand_charge: precursor
+        charge per candidate (None or 0: the PSM's own).  Returns a structured array (L.CANDIDATE_SCORE_DTYPE), one per candidate."""
+        lib = L.load()
+        rp = self.params.report_psms
+        feats = np.ascontiguousarray(feats).reshape(dbatch.n * rp)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        cand_off = np.ascontiguousarray(cand_off, dtype=np.uint64)
+        cand_pep = np.ascontiguousarray(cand_pep, dtype=np.uint32)
+        if len(cand_off) != dbatch.n * rp + 1 or len(counts) != dbatch.n:
+            raise ValueError("cand_off needs n * report_psms + 1 entries, counts n")
+        if len(cand_pep) < int(cand_off.max(initial=0)):
+            raise ValueError("cand_off points behind cand_pep")
+        charge_p = None
+        if cand_charge is not None:
+            if np.any((np.asarray(cand_charge) < 0) | (np.asarray(cand_charge) > 255)):
+                raise ValueError("cand_charge outside 0..255")
+            cand_charge = np.ascontiguousarray(cand_charge, dtype=np.uint8)
+            if len(cand_charge) != len(cand_pep):
+                raise ValueError("cand_charge and cand_pep differ in length")
+            charge_p = L.as_ptr(cand_charge, C.c_uint8)
+        out = np.zeros(int(cand_off[-1]) if len(cand_off) else 0, dtype=L.CANDIDATE_SCORE_DTYPE)
+        L.check(lib.sage_hip_score_candidates_resident(self._h, dbatch._h, feats.ctypes.data_as(C.c_void_p), L.as_ptr(counts, C.c_uint32),
+                                                       L.as_ptr(cand_off, C.c_uint64), L.as_ptr(cand_pep, C.c_uint32), charge_p,
+                                                       out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def last_candidates_timing(self):
+        """(ms of the last score_candidates call on the scorer's stream, ms of its kernel alone), from HIP events"""
+        a, k = C.c_float(), C.c_float()
+        L.check(L.load().sage_hip_last_candidates_timing(self._h, C.byref(a), C.byref(k)))
+        return float(a.value), float(k.value)
 
     def quick_score(self, dbatch: DeviceBatch, prefilter_low_memory: bool, keep: Optional[np.ndarray] = None) -> np.ndarray:
         """Scorer::quick_score (scoring.rs:255-298) over the batch; `keep` ([n_peptides] u8) is OR-updated and returned."""

@@ -235,12 +235,60 @@ def parse_devices(spec, n_visible: int):
     return out
 
 
-def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono=None):
+NO_ISOMER = 0xFFFFFFFF
+
+
+def isomer_candidates(groups, feats, counts):
+    """The candidate lists of Scorer.score_candidates for isomer scoring: for every reported PSM (slot i * report_psms + r,
+    r < counts[i]) every OTHER member of its peptide's isomer group, ascending.  groups: IndexedDatabase.isomer_groups().
+    Returns (cand_off[n * report_psms + 1] u64, cand_pep u32)."""
+    group_of, group_off, members = groups
+    n, report = feats.shape
+    valid = (np.arange(report)[None, :] < np.asarray(counts)[:, None]).reshape(-1)
+    pep = feats["peptide_idx"].reshape(-1).astype(np.int64)
+    g = np.where(valid, group_of[np.where(valid, pep, 0)] if len(group_of) else NO_ISOMER, NO_ISOMER).astype(np.int64)
+    has = g != NO_ISOMER
+    first = np.zeros(n * report, dtype=np.int64)
+    size = np.zeros(n * report, dtype=np.int64)
+    first[has] = group_off[g[has]].astype(np.int64)
+    size[has] = group_off[g[has] + 1].astype(np.int64) - first[has]
+    before = np.cumsum(size) - size
+    mem = members[np.repeat(first - before, size) + np.arange(int(size.sum()))] if size.sum() else np.zeros(0, np.uint32)
+    cand_pep = mem[mem != np.repeat(pep, size)].astype(np.uint32)
+    cand_off = np.zeros(n * report + 1, dtype=np.uint64)
+    cand_off[1:] = np.cumsum(np.where(has, size - 1, 0))
+    return cand_off, cand_pep
+
+
+def best_isomers(cand_off, cand_pep, scores):
+    """Per slot: (number of candidates, the best one's peptide index, hyperscore, matched_b + matched_y) — the largest
+    hyperscore under a plain f64 `>`, ties to the smallest peptide index (the lists are ascending); NO_ISOMER / 0 where a slot
+    has no candidate."""
+    off = cand_off.astype(np.int64)
+    lens = np.diff(off)
+    best_pep = np.full(len(lens), NO_ISOMER, dtype=np.uint32)
+    best_h = np.zeros(len(lens), dtype=np.float64)
+    best_m = np.zeros(len(lens), dtype=np.uint32)
+    some = np.flatnonzero(lens > 0)
+    if len(some):
+        h = scores["hyperscore"]
+        top = np.maximum.reduceat(h, off[some])
+        at = np.where(h == np.repeat(top, lens[some]), np.arange(len(h)), len(h))
+        pick = np.minimum.reduceat(at, off[some])
+        best_pep[some], best_h[some] = cand_pep[pick], h[pick]
+        best_m[some] = scores["matched_b"][pick] + scores["matched_y"][pick]
+    return lens.astype(np.uint32), best_pep, best_h, best_m
+
+
+def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono=None, isomers=None):
     """Scorer::score over every MS2 spectrum of one file (runner.rs:311-325), on all the workers' devices at once: the file's
     spectra are cut into work-balanced shards that are contiguous in PRECURSOR MASS (sharding.plan_mass_shards: index
     replicated, no exchange between devices, and a device walks 1 / N of the mass-sorted index instead of all of it), one host
     thread per device preprocesses, scores and — if asked — annotates its shard, and the shards' results are merged back into
-    input order, as `collect()` leaves them.  Returns (features[n, report], counts[n], ids, annotation | None)."""
+    input order, as `collect()` leaves them.  Returns (features[n, report], counts[n], ids, annotation | None).
+    isomers: IndexedDatabase.isomer_groups() — each shard's device then scores the positional isomers of its PSMs next to the
+    annotation call, and a fifth value is returned: (isomers, best_isomer peptide, isomer_hyperscore, isomer_matched_peaks),
+    each [n, report] (best_isomers)."""
     import threading
 
     from .sharding import estimate_work, plan_mass_shards, plan_shards, precursor_sort_mass
@@ -265,7 +313,7 @@ def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono
             shards = plan_mass_shards(precursor_sort_mass(raw.precursor_mz, raw.precursor_charge, params), len(workers),
                                       None if narrow else weights)
     results = [None] * len(workers)
-    stage_ms = [(0.0, 0.0, 0.0)] * len(workers)  # per worker: preprocess + upload, score, annotate
+    stage_ms = [(0.0, 0.0, 0.0, 0.0)] * len(workers)  # per worker: preprocess + upload, score, annotate, isomers
     errors = []
 
     def work(k):
@@ -286,9 +334,15 @@ def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono
             feats, counts = feats.copy(), counts.copy()
             t2 = time.time()
             ann = scorer.annotate(dbatch, feats, counts) if annotate else None
+            t3 = time.time()
+            iso = None
+            if isomers is not None:
+                cand_off, cand_pep = isomer_candidates(isomers, feats, counts)
+                iso = tuple(a.reshape(feats.shape) for a in
+                            best_isomers(cand_off, cand_pep, scorer.score_candidates(dbatch, feats, counts, cand_off, cand_pep)))
             dbatch.close()
-            stage_ms[k] = ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (time.time() - t2) * 1e3)
-            results[k] = (feats, counts, ids, ann, idx[kept])  # (idx[kept]: positions in the file of the batch's spectra)
+            stage_ms[k] = ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (time.time() - t3) * 1e3)
+            results[k] = (feats, counts, ids, ann, idx[kept], iso)  # (idx[kept]: positions in the file of the batch's spectra)
         except BaseException as exc:  # noqa: BLE001 — re-raised on the calling thread
             errors.append(exc)
 
@@ -324,6 +378,9 @@ def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono
     valid = np.arange(report)[None, :] < counts[:, None]
     feats["spec_index"] = np.where(valid, np.arange(len(counts), dtype=np.uint32)[:, None], feats["spec_index"])  # row of `ids`
     search_file.last_stage_ms = tuple(max(x[i] for x in stage_ms) for i in range(3))  # (the slowest worker's, per stage)
+    if isomers is not None:
+        search_file.last_isomer_ms = max(x[3] for x in stage_ms)
+        return feats, counts, ids, ann, tuple(np.concatenate([p[5][j] for p in parts], axis=0)[perm] for j in range(4))
     return feats, counts, ids, ann
 
 
@@ -378,6 +435,13 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     log(f"generated {host.n_peptides} peptides and their fragment index in {int((time.time() - t0) * 1000)}ms" +
         (f" on {len(devices)} devices" if len(devices) > 1 else ""))
     os.makedirs(output_directory, exist_ok=True)
+    # "score_isomers": an addition over the reference, whose serde schema ignores the key.  The table of positional isomers is made
+    # once per run, on the host threads; every file's PSMs are then scored against their isomers on the device that holds the batch
+    isomer_groups, isomer_parts, isomer_ms = None, [], 0.0
+    if bool(cfg.get("score_isomers", False)):
+        t_iso = time.time()
+        isomer_groups = host.isomer_groups()
+        isomer_ms = (time.time() - t_iso) * 1e3
     feats_all, meta, frags = [], [], []  # per PSM: (filename, spectrum id); matched-fragment rows
     psm_id = 1  # PSM_COUNTER starts at 1 (scoring.rs:163)
     n_searched = 0
@@ -426,10 +490,11 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         if search_raw.n == 0:
             continue
         t0 = time.time()
-        found = search_file(workers, processor, search_raw, sp, host_preprocess, sp["annotate_matches"], host.pep_mono)
+        found = search_file(workers, processor, search_raw, sp, host_preprocess, sp["annotate_matches"], host.pep_mono,
+                            isomers=isomer_groups)
         if found is None:
             continue
-        feats, counts, ids, ann = found
+        feats, counts, ids, ann = found[:4]
         n_batch = len(counts)
         dt = (time.time() - t0) * 1000.0
         search_ms += dt
@@ -450,6 +515,9 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         part = feats[spec_of, rank_of].copy()
         part["file_id"] = file_id
         feats_all.append(part)
+        if isomer_groups is not None:
+            isomer_parts.append(tuple(a[spec_of, rank_of] for a in found[4]))
+            isomer_ms += getattr(search_file, "last_isomer_ms", 0.0)
         meta += [(psm_id + j, name, ids[i]) for j, i in enumerate(spec_of.tolist())]
         if arr is not None:
             for j, (i, r) in enumerate(zip(spec_of.tolist(), rank_of.tolist())):
@@ -538,6 +606,15 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         fp = os.path.join(output_directory, "matched_fragments.sage.tsv")
         output.write_fragments(fp, [r for i in order for r in frags[i]])
         paths.append(fp)
+    isomer_summary = {}
+    if isomer_groups is not None:
+        ip = os.path.join(output_directory, "isomers.sage.tsv")
+        cols = [np.concatenate([p[j] for p in isomer_parts]) if isomer_parts else np.zeros(0) for j in range(4)]
+        rows = output.isomer_rows(host, flat, list(order), psm_ids, *cols)
+        output.write_isomers(ip, rows)
+        paths.append(ip)
+        isomer_summary = {"isomer_rows": len(rows), "isomer_ms": isomer_ms}
+        log(f"- isomer scoring: {int(isomer_ms):8d} ms ({len(rows)} PSMs with positional isomers)")
     if tmt_parts:  # runner.rs:638-641: only when some spectrum was quantified
         tp = os.path.join(output_directory, "tmt.tsv")
         output.write_tmt_native(tp, isobaric.headers(), filenames, np.concatenate([np.full(len(p[1]), p[0], np.uint32) for p in tmt_parts]),
@@ -563,7 +640,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     stage_totals["total_after_index_ms"] = (time.time() - t_run) * 1e3
     summary = {"version": "sage-hip 0.1 (search-and-score path of sage 0.15.0-beta.2)", "psms": len(flat),
                "spectra_searched": n_searched, "search_ms": search_ms, "stages": stage_totals, "output_paths": paths, **rescore_summary,
-               **lfq_summary, **tmt_summary}
+               **lfq_summary, **tmt_summary, **isomer_summary}
     with open(os.path.join(output_directory, "results.json"), "w") as fh:
         json.dump(dict(cfg, output_paths=paths, summary=summary), fh, indent=2, default=str)
     return summary

@@ -67,6 +67,11 @@ static uint64_t next_db_serial() {
 
 struct SageHostDb {
     HostDb db;
+    // sage_hip_hostdb_isomer_groups: made by the first call (the sizing call), handed out by the ones after it
+    mutable std::mutex iso_mu;
+    mutable bool iso_made = false;
+    mutable std::vector<uint32_t> iso_of, iso_members;
+    mutable std::vector<uint64_t> iso_off;
 };
 
 struct SageGroupStrings {
@@ -239,6 +244,13 @@ struct SageScorer {
     DevBuf<uint8_t> an_kinds, keep;
     DevBuf<int32_t> an_charges, an_ord;
     DevBuf<float> an_int, an_calc, an_exp;
+    // ... and of sage_hip_score_candidates_resident (the features and counts go through an_feats / an_counts)
+    DevBuf<uint32_t> cs_list, cs_pep;
+    DevBuf<uint64_t> cs_off;
+    DevBuf<uint8_t> cs_charge;
+    DevBuf<SageCandidateScore> cs_out;
+    Events<4> cs_ev;  // call begin, kernel begin, kernel end, call end
+    float cs_call_ms = 0.f, cs_kernel_ms = 0.f;
 };
 
 extern "C" {
@@ -610,6 +622,27 @@ int sage_hip_hostdb_feature_peptides(const SageHostDb* db, const uint32_t* pepti
         off += len;
     }
     seq_off[n] = off;
+    return SAGE_HIP_OK;
+}
+int sage_hip_hostdb_isomer_groups(const SageHostDb* db, uint32_t* group_of, uint64_t* group_off, uint32_t* members, uint64_t* n_groups,
+                                  uint64_t* n_members) {
+    if (!db || !n_groups || !n_members) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_hostdb_isomer_groups: null argument");
+    std::lock_guard<std::mutex> lock(db->iso_mu);
+    if (!db->iso_made) {
+        db->db.isomer_groups(db->iso_of, db->iso_off, db->iso_members);
+        db->iso_made = true;
+    }
+    const std::vector<uint32_t>&of = db->iso_of, &mem = db->iso_members;
+    const std::vector<uint64_t>& off = db->iso_off;
+    const bool sizing = !group_off && !members;
+    if (!sizing) {
+        if (!group_off || (!members && !mem.empty())) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_hostdb_isomer_groups: group_off and members go together");
+        std::memcpy(group_off, off.data(), off.size() * sizeof(uint64_t));
+        if (!mem.empty()) std::memcpy(members, mem.data(), mem.size() * sizeof(uint32_t));
+    }
+    if (group_of && !of.empty()) std::memcpy(group_of, of.data(), of.size() * sizeof(uint32_t));
+    *n_groups = off.size() - 1;
+    *n_members = mem.size();
     return SAGE_HIP_OK;
 }
 int sage_hip_hostdb_competition_keys(const SageHostDb* db, const uint32_t* peptide_idx, uint64_t n, uint32_t* peptide_key,
@@ -2401,6 +2434,85 @@ int sage_hip_annotate_resident(SageScorer* s, SageDeviceBatch* b, const SageFeat
     HIP_TRY(hipMemcpyAsync(out->mz_calculated, s->an_calc.p, total * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out->mz_experimental, s->an_exp.p, total * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return SAGE_HIP_OK;
+}
+
+int sage_hip_score_candidates_resident(SageScorer* s, SageDeviceBatch* b, const SageFeature* features, const uint32_t* counts,
+                                       const uint64_t* cand_off, const uint32_t* cand_pep, const uint8_t* cand_charge,
+                                       SageCandidateScore* out) {
+    if (!s || !b || !cand_off) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: null argument");
+    if (b->device != s->db->device) return fail(SAGE_HIP_ERR_INVALID, "batch and scorer live on different devices");
+    std::lock_guard<std::mutex> lock(s->mu);
+    const uint32_t n = b->n, rp = s->params.report_psms;
+    const size_t slots = (size_t)n * rp;
+    const uint64_t np = s->db->view.np;
+    s->cs_call_ms = s->cs_kernel_ms = 0.f;
+    // everything the kernel indexes with is checked here: bad input is an error, never a device fault
+    if (cand_off[0] != 0) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: cand_off[0] must be 0");
+    for (size_t t = 0; t < slots; t++)
+        if (cand_off[t + 1] < cand_off[t]) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: cand_off decreases at slot " + std::to_string(t));
+    const uint64_t total = cand_off[slots];
+    if (total == 0) return SAGE_HIP_OK;
+    if (!features || !counts || !cand_pep || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: null argument");
+    std::vector<uint32_t> list;
+    for (uint32_t i = 0; i < n; i++) {
+        const size_t s0 = (size_t)i * rp;
+        if (cand_off[s0 + rp] == cand_off[s0]) continue;
+        if (counts[i] > rp) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: counts[" + std::to_string(i) + "] exceeds report_psms");
+        for (uint32_t r = 0; r < rp; r++) {
+            if (r >= counts[i]) {
+                if (cand_off[s0 + r + 1] != cand_off[s0 + r])
+                    return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: candidates on slot " + std::to_string(s0 + r) +
+                                                          ", which holds no PSM (rank >= counts[" + std::to_string(i) + "])");
+                continue;
+            }
+            const SageFeature& f = features[s0 + r];
+            if (f.peptide_idx >= np) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: feature peptide_idx out of range");
+            if (f.charge > 254) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: feature charge above 254");
+        }
+        list.push_back(i);
+    }
+    for (uint64_t c = 0; c < total; c++) {
+        if (cand_pep[c] >= np)
+            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: cand_pep[" + std::to_string(c) + "] is not a peptide of the database");
+        if (cand_charge && cand_charge[c] > 254)
+            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: cand_charge[" + std::to_string(c) + "] above 254");
+    }
+    if (candidates_lds_bytes(b->view) > 160 * 1024)
+        return fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_score_candidates_resident: a spectrum of the batch has more peaks than a compute unit's LDS holds");
+    HIP_TRY(hipSetDevice(s->db->device));
+    HIP_TRY(s->cs_ev.create());
+    HIP_TRY(s->an_feats.reserve(slots));
+    HIP_TRY(s->an_counts.reserve(n));
+    HIP_TRY(s->cs_off.reserve(slots + 1));
+    HIP_TRY(s->cs_list.reserve(list.size()));
+    HIP_TRY(s->cs_pep.reserve(total));
+    if (cand_charge) HIP_TRY(s->cs_charge.reserve(total));
+    HIP_TRY(s->cs_out.reserve(total));
+    hipStream_t st = s->stream;
+    HIP_TRY(hipEventRecord(s->cs_ev[0], st));
+    HIP_TRY(hipMemcpyAsync(s->an_feats.p, features, slots * sizeof(SageFeature), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->an_counts.p, counts, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->cs_off.p, cand_off, (slots + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->cs_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->cs_pep.p, cand_pep, total * 4, hipMemcpyHostToDevice, st));
+    if (cand_charge) HIP_TRY(hipMemcpyAsync(s->cs_charge.p, cand_charge, total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(s->cs_ev[1], st));
+    launch_candidates(s->db->view, s->dev, b->view, s->an_feats.p, s->an_counts.p, s->cs_list.p, (uint32_t)list.size(), s->cs_off.p,
+                      s->cs_pep.p, cand_charge ? s->cs_charge.p : nullptr, s->lnfact.p, (uint32_t)s->lnfact.n, s->cs_out.p, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->cs_ev[2], st));
+    HIP_TRY(hipMemcpyAsync(out, s->cs_out.p, total * sizeof(SageCandidateScore), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(s->cs_ev[3], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&s->cs_call_ms, s->cs_ev[0], s->cs_ev[3]));
+    HIP_TRY(hipEventElapsedTime(&s->cs_kernel_ms, s->cs_ev[1], s->cs_ev[2]));
+    return SAGE_HIP_OK;
+}
+int sage_hip_last_candidates_timing(const SageScorer* s, float* call_ms, float* kernel_ms) {
+    if (!s || !call_ms || !kernel_ms) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_last_candidates_timing: null argument");
+    *call_ms = s->cs_call_ms;
+    *kernel_ms = s->cs_kernel_ms;
     return SAGE_HIP_OK;
 }
 

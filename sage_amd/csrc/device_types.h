@@ -330,5 +330,10 @@ void launch_window_max(const DevScorer& sc, const DevBatchView& b, const float* 
 void launch_quick_mark(const DevScorer& sc, const DevBatchView& b, const DevWork& w, uint8_t* keep, void* stream);
 void launch_annotate(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const SageFeature* feats,
                      const uint32_t* counts, const uint64_t* psm_off, const DevFragments& out, void* stream);
+// candidates_kernel: score_candidate of the peptides cand_pep[cand_off[slot] ..) for the PSM slots of the n_list spectra of spec_list
+size_t candidates_lds_bytes(const DevBatchView& b);
+void launch_candidates(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const SageFeature* feats, const uint32_t* counts,
+                       const uint32_t* spec_list, uint32_t n_list, const uint64_t* cand_off, const uint32_t* cand_pep,
+                       const uint8_t* cand_charge, const double* lnfact_table, uint32_t lnfact_n, SageCandidateScore* out, void* stream);
 
 }  // namespace sagehip

@@ -1050,4 +1050,86 @@ uint64_t process_ms2(uint64_t take_top_n, bool deisotope, float min_deisotope_mz
     return kept.size();
 }
 
+// Positional isomers: peptides with the same decoy flag, the same residues and the same multiset of modification
+// masses (bit patterns of the non-zero entries of `mods`, and of nterm / cterm when neither NaN nor 0).  Every peptide's sorted mass
+// list is made once, on the host threads; the peptides are then sorted by (hash of the key, the key itself, index), so equal keys
+// are neighbours in ascending index order and a hash collision only costs a comparison.
+void HostDb::isomer_groups(std::vector<uint32_t>& group_of, std::vector<uint64_t>& group_off, std::vector<uint32_t>& members) const {
+    const size_t np = n_peptides();
+    std::vector<uint64_t> mass_off(np + 1, 0);
+    parallel_for(np, 4096, [&](size_t ib, size_t ie, unsigned) {
+        for (size_t p = ib; p < ie; p++) {
+            uint64_t n = 0;
+            for (uint64_t j = seq_off[p]; j < seq_off[p + 1]; j++) n += mods[j] != 0.0f;
+            n += nterm[p] == nterm[p] && nterm[p] != 0.0f;
+            n += cterm[p] == cterm[p] && cterm[p] != 0.0f;
+            mass_off[p + 1] = n;
+        }
+    });
+    for (size_t p = 0; p < np; p++) mass_off[p + 1] += mass_off[p];
+    std::vector<uint32_t> mass(mass_off[np]);
+    std::vector<uint64_t> hash(np);
+    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    parallel_for(np, 4096, [&](size_t ib, size_t ie, unsigned) {
+        for (size_t p = ib; p < ie; p++) {
+            uint32_t* m = mass.data() + mass_off[p];
+            size_t n = 0;
+            for (uint64_t j = seq_off[p]; j < seq_off[p + 1]; j++)
+                if (mods[j] != 0.0f) m[n++] = bits(mods[j]);
+            if (nterm[p] == nterm[p] && nterm[p] != 0.0f) m[n++] = bits(nterm[p]);
+            if (cterm[p] == cterm[p] && cterm[p] != 0.0f) m[n++] = bits(cterm[p]);
+            std::sort(m, m + n);
+            uint64_t h = 0xcbf29ce484222325ull ^ decoy[p];  // FNV-1a over decoy, residues, sorted masses
+            auto mix = [&h](uint64_t v) { h = (h ^ v) * 0x100000001b3ull; };
+            for (uint64_t j = seq_off[p]; j < seq_off[p + 1]; j++) mix(seq[j]);
+            mix(0x1FFull);
+            for (size_t k = 0; k < n; k++) mix(m[k]);
+            hash[p] = h;
+        }
+    });
+    // <0, 0, >0 on (decoy, residues, masses)
+    auto key_cmp = [&](uint32_t a, uint32_t b) -> int {
+        if (decoy[a] != decoy[b]) return decoy[a] < decoy[b] ? -1 : 1;
+        const uint64_t la = seq_off[a + 1] - seq_off[a], lb = seq_off[b + 1] - seq_off[b];
+        if (la != lb) return la < lb ? -1 : 1;
+        if (const int c = la ? std::memcmp(seq.data() + seq_off[a], seq.data() + seq_off[b], la) : 0) return c;
+        const uint64_t ma = mass_off[a + 1] - mass_off[a], mb = mass_off[b + 1] - mass_off[b];
+        if (ma != mb) return ma < mb ? -1 : 1;
+        for (uint64_t k = 0; k < ma; k++) {
+            const uint32_t x = mass[mass_off[a] + k], y = mass[mass_off[b] + k];
+            if (x != y) return x < y ? -1 : 1;
+        }
+        return 0;
+    };
+    std::vector<uint32_t> order(np);
+    for (size_t p = 0; p < np; p++) order[p] = (uint32_t)p;
+    parallel_stable_sort(order, [&](uint32_t a, uint32_t b) {
+        if (hash[a] != hash[b]) return hash[a] < hash[b];
+        return key_cmp(a, b) < 0;  // (stable: equal keys stay in ascending index order)
+    });
+    struct RunRec {
+        uint32_t first;
+        size_t begin, len;
+    };
+    std::vector<RunRec> runs;
+    for (size_t i = 0; i < np;) {
+        size_t j = i + 1;
+        while (j < np && hash[order[j]] == hash[order[i]] && key_cmp(order[i], order[j]) == 0) j++;
+        if (j - i >= 2) runs.push_back(RunRec{order[i], i, j - i});
+        i = j;
+    }
+    std::sort(runs.begin(), runs.end(), [](const RunRec& a, const RunRec& b) { return a.first < b.first; });
+    group_of.assign(np, 0xFFFFFFFFu);
+    group_off.assign(runs.size() + 1, 0);
+    members.clear();
+    for (size_t g = 0; g < runs.size(); g++) {
+        for (size_t k = 0; k < runs[g].len; k++) {
+            const uint32_t p = order[runs[g].begin + k];
+            group_of[p] = (uint32_t)g;
+            members.push_back(p);
+        }
+        group_off[g + 1] = members.size();
+    }
+}
+
 }  // namespace sagehip

@@ -63,6 +63,8 @@ struct HostDb {
     std::string peptide_proteins(uint64_t i) const;
     void competition_keys(const uint32_t* peptide_idx, uint64_t n, uint32_t* peptide_key, uint32_t& n_peptide_keys,
                           uint32_t* protein_key, uint32_t& n_protein_keys) const;
+    // positional isomers: group_of[n_peptides] (0xFFFFFFFF: none), group_off[n_groups + 1] into members
+    void isomer_groups(std::vector<uint32_t>& group_of, std::vector<uint64_t>& group_off, std::vector<uint32_t>& members) const;
 };
 
 unsigned host_threads();

@@ -4635,6 +4635,131 @@ __global__ __launch_bounds__(64) void annotate_kernel(DevDbView db, DevScorer sc
     }
 }
 
+// score_candidate (scoring.rs:675-767) of GIVEN peptides against the spectra of reported PSMs (positional isomers):
+// one wavefront per spectrum of `spec_list` (the host lists the spectra that have a candidate) walks the spectrum's PSMs in rank
+// order — with chimera, the PSM's own peaks leave the LDS copy of the spectrum before the next rank, as in annotate_kernel — and
+// scores the candidates of slot (spectrum, rank) one after the other.  A candidate's (ion, fragment charge) items are matched 64
+// per trip; the matches of a trip are then added up in lane order by the whole wavefront (wave-uniform registers), so the three f32
+// sums and the two Runs see them in the reference's order.  Lane k keeps the Score of the k-th candidate of a batch of 64; the
+// logarithm of the hyperscore is taken once per batch, one candidate per lane.  No min_matched_peaks filter and no prune: every
+// candidate gets its record.
+__global__ __launch_bounds__(64) void candidates_kernel(DevDbView db, DevScorer sc, DevBatchView b, const SageFeature* __restrict__ feats,
+                                                        const uint32_t* __restrict__ counts, const uint32_t* __restrict__ spec_list,
+                                                        uint32_t n_list, const uint64_t* __restrict__ cand_off,
+                                                        const uint32_t* __restrict__ cand_pep, const uint8_t* __restrict__ cand_charge,
+                                                        const double* __restrict__ lnfact_table, uint32_t lnfact_n,
+                                                        SageCandidateScore* __restrict__ out) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const uint32_t lane = lane_id();
+    if (blockIdx.x >= n_list) return;
+    const uint32_t spec = spec_list[blockIdx.x];
+    if (spec >= b.n) return;
+    float* pm = (float*)smem;
+    float* pi = pm + b.pcap;
+    uint8_t* rm = (uint8_t*)(pi + b.pcap);
+    uint8_t* rm2 = rm + b.pcap;
+    const uint64_t p0 = b.peak_off[spec];
+    uint32_t P = (uint32_t)(b.peak_off[spec + 1] - p0);
+    for (uint32_t i = lane; i < P; i += WAVE) {
+        pm[i] = b.masses[p0 + i];
+        pi[i] = b.intensities[p0 + i];
+    }
+    __syncthreads();
+    float tic = 0.0f;
+    const uint32_t count = counts[spec];
+    const size_t slot0 = (size_t)spec * sc.report_psms;
+    uint32_t ranks = 0;  // ranks up to the last one that has candidates: nothing behind it needs the spectrum
+    for (uint32_t r = 0; r < count; r++)
+        if (cand_off[slot0 + r + 1] > cand_off[slot0 + r]) ranks = r + 1;
+    for (uint32_t r = 0; r < ranks; r++) {
+        const SageFeature f = feats[slot0 + r];
+        const uint64_t c0 = cand_off[slot0 + r], c1 = cand_off[slot0 + r + 1];
+        const uint32_t ptop = pow2_floor(P);
+        for (uint64_t cb = c0; cb < c1; cb += WAVE) {
+            const uint32_t nb = c1 - cb < WAVE ? (uint32_t)(c1 - cb) : WAVE;
+            Score mine{};
+            for (uint32_t k = 0; k < nb; k++) {
+                const uint32_t pep = cand_pep[cb + k];
+                uint32_t z = cand_charge ? cand_charge[cb + k] : 0u;
+                if (!z) z = f.charge;
+                const uint32_t nfz = max_fragment_charge(sc.max_fragment_charge, z) - 1;
+                const uint64_t ion_base = db.ion_off[pep];
+                const uint32_t lm1 = db.n_kinds ? (uint32_t)((db.ion_off[pep + 1] - ion_base) / db.n_kinds) : 0;
+                const uint32_t n_items = db.n_kinds * lm1 * nfz;
+                // the candidate's sums and Runs: the same value in every lane
+                float summed_b = 0.0f, summed_y = 0.0f, ppm = 0.0f;
+                uint32_t matched_b = 0, matched_y = 0;
+                uint64_t b_run = 0, y_run = 0;
+                for (uint32_t base = 0; base < n_items; base += WAVE) {
+                    const uint32_t t = base + lane;
+                    int pk = -1;
+                    float inten = 0.0f, term = 0.0f;
+                    uint32_t where = 0;  // ion index inside its kind | 1 << 31 for the kinds counted as y (x, y, z)
+                    if (t < n_items) {
+                        const uint32_t ion = t / nfz, charge = t - ion * nfz + 1;
+                        const float mz = db.ions[ion_base + ion] / (float)charge;
+                        pk = select_most_intense_peak_lockstep(pm, pi, P, ptop, mz, sc.fragment_tol);
+                        if (pk >= 0) {
+                            const float peak_mass = pm[pk];
+                            inten = pi[pk];
+                            term = inten * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);  // scoring.rs:719-720
+                            const uint32_t kidx = ion / lm1;
+                            where = (ion - kidx * lm1) | (db.ion_kinds[kidx] <= 2 ? 0u : 0x80000000u);
+                        }
+                    }
+                    for (uint64_t m = __ballot(pk >= 0); m; m &= m - 1ull) {
+                        const uint32_t src = (uint32_t)__builtin_ctzll(m);
+                        const float it = lane_valuef(inten, src);
+                        const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)where, (int)__builtin_amdgcn_readfirstlane(src));
+                        ppm += lane_valuef(term, src);
+                        if (w & 0x80000000u) {
+                            matched_y += 1;
+                            summed_y += it;
+                            run_matched_packed(y_run, w & 0x7FFFFFFFu);
+                        } else {
+                            matched_b += 1;
+                            summed_b += it;
+                            run_matched_packed(b_run, w);
+                        }
+                    }
+                }
+                if (lane == k) {
+                    mine.matched_b = matched_b;
+                    mine.matched_y = matched_y;
+                    mine.summed_b = summed_b;
+                    mine.summed_y = summed_y;
+                    mine.longest_b = run_longest_packed(b_run);
+                    mine.longest_y = run_longest_packed(y_run);
+                    mine.ppm_difference = ppm / (summed_b + summed_y);  // scoring.rs:759
+                }
+            }
+            double ln_lambda;
+            bool undecided;
+            const double ln_i = cr_log_pair<true>(hyperscore_arg(mine), 1.0, false, false, ln_lambda, undecided);
+            const double h = hyperscore_dev(sc.score_type, mine, ln_i, lnfact_table, lnfact_n);
+            if (lane < nb) {
+                SageCandidateScore* o = out + cb + lane;
+                o->hyperscore = h;
+                o->summed_b = mine.summed_b;
+                o->summed_y = mine.summed_y;
+                o->average_ppm = mine.ppm_difference;
+                o->matched_b = mine.matched_b;
+                o->matched_y = mine.matched_y;
+                o->longest_b = mine.longest_b;
+                o->longest_y = mine.longest_y;
+                o->pad = 0u;
+            }
+        }
+        if (sc.chimera && r + 1 < ranks) {
+            const uint32_t wpep = f.peptide_idx;
+            const uint32_t wmfc = max_fragment_charge(sc.max_fragment_charge, f.charge);
+            const uint64_t wbase = db.ion_off[wpep];
+            const uint32_t wlm1 = db.n_kinds ? (uint32_t)((db.ion_off[wpep + 1] - wbase) / db.n_kinds) : 0;
+            remove_matched_peaks_dev(pm, pi, rm, rm2, P, tic, db.ions + wbase, db.n_kinds * wlm1 * (wmfc - 1), wmfc, sc.fragment_tol);
+        }
+    }
+}
+
 }  // namespace
 
 size_t prelim_lds_bytes(const DevScorer& sc, const DevBatchView& b, bool huge) { return prelim_layout_bytes(sc, b, huge); }
@@ -4687,7 +4812,8 @@ int spectrum_kernel_prepare(size_t max_lds_bytes) {
                           (const void*)rescore_kernel<true, true, false, false>, (const void*)rescore_kernel<false, false, false, false>,
                           (const void*)rescore_kernel<false, false, true, false>, (const void*)rescore_kernel<false, true, false, false>,
                           (const void*)narrow_kernel<true, true>, (const void*)narrow_kernel<true, false>,
-                          (const void*)narrow_kernel<false, true>, (const void*)narrow_kernel<false, false>, (const void*)annotate_kernel}) {
+                          (const void*)narrow_kernel<false, true>, (const void*)narrow_kernel<false, false>, (const void*)annotate_kernel,
+                          (const void*)candidates_kernel}) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes);
         if (e != hipSuccess) return (int)e;
         // (pbm_bit reads the peak bitmap through LDS address 0: the dynamic LDS of these kernels must start there)
@@ -4922,6 +5048,14 @@ void launch_annotate(const DevDbView& db, const DevScorer& sc, const DevBatchVie
     if (b.n == 0) return;
     const size_t lds = ((size_t)b.pcap * 10 + 15) & ~(size_t)15;
     hipLaunchKernelGGL(annotate_kernel, dim3(b.n), dim3(64), lds, (hipStream_t)stream, db, sc, b, feats, counts, psm_off, out);
+}
+size_t candidates_lds_bytes(const DevBatchView& b) { return ((size_t)b.pcap * 10 + 15) & ~(size_t)15; }  // pm, pi, rm, rm2: as annotate_kernel
+void launch_candidates(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const SageFeature* feats, const uint32_t* counts,
+                       const uint32_t* spec_list, uint32_t n_list, const uint64_t* cand_off, const uint32_t* cand_pep,
+                       const uint8_t* cand_charge, const double* lnfact_table, uint32_t lnfact_n, SageCandidateScore* out, void* stream) {
+    if (b.n == 0 || n_list == 0) return;
+    hipLaunchKernelGGL(candidates_kernel, dim3(n_list), dim3(64), candidates_lds_bytes(b), (hipStream_t)stream, db, sc, b, feats, counts,
+                       spec_list, n_list, cand_off, cand_pep, cand_charge, lnfact_table, lnfact_n, out);
 }
 
 }  // namespace sagehip

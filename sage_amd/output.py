@@ -132,6 +132,29 @@ def write_fragments(path: str, rows: Sequence[List[str]]) -> None:
             fh.write(_record(r) + "\n")
 
 
+ISOMER_HEADERS = ["psm_id", "peptide", "isomers", "best_isomer", "isomer_hyperscore", "isomer_matched_peaks", "delta_isomer"]
+
+
+def isomer_rows(db, features, order, psm_ids, n_isomers, best_pep, best_hyperscore, best_matched) -> List[List[str]]:
+    """isomers.sage.tsv (an addition over the reference): one row per PSM whose peptide has positional isomers, in the row order of
+    results.sage.tsv.  The arrays are indexed like `features`; delta_isomer = hyperscore - isomer_hyperscore in f64."""
+    rows = []
+    for i in order:
+        if int(n_isomers[i]) == 0:
+            continue
+        h, hi = np.float64(features[i]["hyperscore"]), np.float64(best_hyperscore[i])
+        rows.append([str(psm_ids[i]), db.peptide_string(int(features[i]["peptide_idx"])), str(int(n_isomers[i])),
+                     db.peptide_string(int(best_pep[i])), ryu_f64(hi), str(int(best_matched[i])), ryu_f64(h - hi)])
+    return rows
+
+
+def write_isomers(path: str, rows: Sequence[List[str]]) -> None:
+    with open(path, "w", newline="") as fh:
+        fh.write(_record(ISOMER_HEADERS) + "\n")
+        for r in rows:
+            fh.write(_record(r) + "\n")
+
+
 PIN_HEADERS = ["SpecId", "Label", "ScanNr", "ExpMass", "CalcMass", "FileName", "retentiontime", "ion_mobility", "rank", "z=2",
                "z=3", "z=4", "z=5", "z=6", "z=other", "peptide_len", "missed_cleavages", "semi_enzymatic", "isotope_error",
                "ln(precursor_ppm)", "fragment_ppm", "ln(hyperscore)", "ln(delta_next)", "ln(delta_best)", "aligned_rt",
