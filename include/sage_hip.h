@@ -347,6 +347,20 @@ int sage_hip_debug_heavy_routes(SageScorer* scorer, unsigned long long* out2);
  * rescoring kernel in rows by schedule position, 0 if in the arrays indexed by spectrum (SAGE_HIP_DEBUG_FLAGS=131072 at scorer
  * creation forces the latter; so does every step that is not the plain narrow search with schedule records). */
 int sage_hip_debug_handover_route(SageScorer* scorer, uint32_t* out);
+/* Debug aid (no condition): *out = the instance of the rescoring kernel the first pass of the scorer's last scoring step (or its last
+ * quick_score) launched, as bits: CHIMERA the general instance with chimera rounds (a chimera search, or SAGE_HIP_RESCORE_GENERAL=1
+ * at scorer creation); KINDS2 the instance compiled for a database of exactly two ion kinds, the first n-terminal (a / b / c) and
+ * the second not — {b, y}, {c, z}, {a, x} — taken by searches without chimera rounds unless SAGE_HIP_RESCORE_KINDS_GENERAL=1 at
+ * scorer creation; FAST the short divisions; ACC the full logarithm and quick_score; PROF the phase clocks (SAGE_HIP_PHASE_CLOCKS=1).
+ * BIG: the kernel for lists wider than a wavefront instead (report_psms > 32, peptides beyond 1023 residues).  NONE: no launch yet. */
+#define SAGE_HIP_RESCORE_INST_CHIMERA 1u
+#define SAGE_HIP_RESCORE_INST_KINDS2 2u
+#define SAGE_HIP_RESCORE_INST_FAST 4u
+#define SAGE_HIP_RESCORE_INST_ACC 8u
+#define SAGE_HIP_RESCORE_INST_PROF 16u
+#define SAGE_HIP_RESCORE_INST_BIG 32u
+#define SAGE_HIP_RESCORE_INST_NONE 0xFFFFFFFFu
+int sage_hip_debug_rescore_instance(SageScorer* scorer, uint32_t* out);
 
 /* Debug aid (no condition): the device database read back, so that tests can hold every table sage_hip_db_create derived
  *  to a plain restatement, entry for entry.  The layout: the scalars the kernels address the tables with. */

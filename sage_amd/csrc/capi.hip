@@ -231,6 +231,7 @@ struct SageScorer {
     bool hand_rows = true;      // the narrow first pass hands its lists over in schedule order (DevWork::hand) where enqueue_compute
                                 // allows it (SAGE_HIP_DEBUG_FLAGS=131072, read at scorer creation: always by spectrum)
     bool last_hand = false;     // ... and the last first pass enqueued did (sage_hip_debug_handover_route)
+    uint32_t last_rescore = RESCORE_INST_NONE;  // the rescoring instance the last first pass (or quick_score) launched (sage_hip_debug_rescore_instance)
     uint32_t qmax = 1;
     WorkSet ws;                 // the working set (lane 0)
     WorkSet ws2;                // a second one: the streaming pipeline scores two chunks of a narrow batch side by side (lane 1)
@@ -969,7 +970,15 @@ static int scorer_init(SageScorer* sp, SageDeviceDb* db, const SageScorerParams*
     s->hand_rows = (d.dbg_flags & 131072u) == 0u;  // (131072: tests and A/B runs keep the hand-over arrays indexed by spectrum)
     d.prune_min = (d.dbg_flags & 4096u) ? 0u : d.min_matched_peaks;  // (4096: tests and A/B runs switch the rescoring prune off)
     d.rescore_general = 0;
-    if (const char* e = getenv("SAGE_HIP_RESCORE_GENERAL")) d.rescore_general = atoi(e) != 0 ? 1u : 0u;
+    if (const char* e = getenv("SAGE_HIP_RESCORE_GENERAL")) d.rescore_general = atoi(e) != 0 ? RESCORE_GENERAL_CHIMERA : 0u;
+    {
+        // the instance compiled for two ion kinds, the first n-terminal (a / b / c), the second not — {b, y}, the reference's default:
+        // decided here, once per scorer, from the database's kinds (SAGE_HIP_RESCORE_KINDS_GENERAL=1: tests and A/B runs keep the general one)
+        const DevDbView& v = db->view;
+        bool kinds2 = v.n_kinds == 2u && v.ion_kinds[0] <= 2 && v.ion_kinds[1] > 2;
+        if (const char* e = getenv("SAGE_HIP_RESCORE_KINDS_GENERAL")) kinds2 = kinds2 && atoi(e) == 0;
+        if (!kinds2) d.rescore_general |= RESCORE_GENERAL_KINDS;
+    }
     d.exact = 0;
     d.xcd_chunk = 1024;
     if (const char* e = getenv("SAGE_HIP_XCD_CHUNK")) d.xcd_chunk = (uint32_t)std::max(0, atoi(e));
@@ -1880,8 +1889,10 @@ static int enqueue_compute(SageScorer* s, const DevBatchView& view_in, OutSet& o
         HIP_TRY(hipGetLastError());
     }
     if (!no_timing) HIP_TRY(hipEventRecord(o.ev[1].e, st));
-    if (with_rescore && (wide || !(fused || one_launch)))  // (behind search_kernel / the fused kernel: only the spectra the large-window kernels assembled)
+    if (with_rescore && (wide || !(fused || one_launch))) {  // (behind search_kernel / the fused kernel: only the spectra the large-window kernels assembled)
+        s->last_rescore = rescore_instance_code(sc1, w1, false);
         HIP_TRY((hipError_t)launch_rescore(s->db->view, sc1, view, w1, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, rec, count_buf, nullptr, st));
+    }
     if (!no_timing) HIP_TRY(hipEventRecord(o.ev[2].e, st));
 retry_pass:
     if (o.two_pass && phase != 1) {
@@ -2533,10 +2544,11 @@ int sage_hip_quick_score_resident(SageScorer* s, SageDeviceBatch* b, int prefilt
         w.hugebuf = s->ws.hugebuf.p;
         w.huge_stride = (uint32_t)huge_stride_bytes(s->dev);
     }
-    if (prefilter_low_memory)
+    if (prefilter_low_memory) {
+        s->last_rescore = rescore_instance_code(s->dev, w, true);
         HIP_TRY((hipError_t)launch_rescore(s->db->view, s->dev, b->view, w, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, o.features.p,
                                            o.out_count.p, s->keep.p, s->stream));
-    else
+    } else
         launch_quick_mark(s->dev, b->view, w, s->keep.p, s->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(o.h_counters, o.counters.p, 2 * CTR_COUNT * 4, hipMemcpyDeviceToHost, s->stream));
@@ -2649,6 +2661,19 @@ int sage_hip_debug_heavy_routes(SageScorer* s, unsigned long long* out2) {
 int sage_hip_debug_handover_route(SageScorer* s, uint32_t* out) {
     if (!s || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
     *out = s->last_hand ? 1u : 0u;
+    return SAGE_HIP_OK;
+}
+
+// debugging aid: the instance of the rescoring kernels the first pass of the last scoring step (or the last quick_score) launched —
+// SAGE_HIP_RESCORE_INST_* bits, SAGE_HIP_RESCORE_INST_NONE before the first
+int sage_hip_debug_rescore_instance(SageScorer* s, uint32_t* out) {
+    if (!s || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+    static_assert(RESCORE_INST_CHIMERA == SAGE_HIP_RESCORE_INST_CHIMERA && RESCORE_INST_KINDS2 == SAGE_HIP_RESCORE_INST_KINDS2 &&
+                      RESCORE_INST_FAST == SAGE_HIP_RESCORE_INST_FAST && RESCORE_INST_ACC == SAGE_HIP_RESCORE_INST_ACC &&
+                      RESCORE_INST_PROF == SAGE_HIP_RESCORE_INST_PROF && RESCORE_INST_BIG == SAGE_HIP_RESCORE_INST_BIG &&
+                      RESCORE_INST_NONE == SAGE_HIP_RESCORE_INST_NONE,
+                  "include/sage_hip.h names the bits of device_types.h");
+    *out = s->last_rescore;
     return SAGE_HIP_OK;
 }
 

@@ -514,6 +514,22 @@ SAGE_HD KindSeg kind_seg_next(const KindSeg& g, uint32_t lm1) {
 }
 SAGE_HD uint64_t kind_seg_mask(const KindSeg& g) { return g.len >= 64u ? ~0ull : ((1ull << g.len) - 1ull) << (g.lo & 63u); }
 
+// The same for a table of exactly TWO kinds, kind 0 n-terminal (a / b / c) and kind 1 not — {b, y}, the reference's default; the
+// instances of kernels.hip: score_candidates compiled for it (KINDS2).  A chunk then holds at most two segments and their boundary
+// is one number: kinds2_bound(j0, lm1) bits of the chunk at ion j0 belong to kind 0 — lm1 - j0 clamped to [0, 64].  The kind-0
+// segment is the bits below the boundary (kinds2_nt_mask), index j0 at bit 0; the kind-1 segment is every bit from the boundary on
+// (a caller's masks reach no further than the candidate's 2 * lm1 ions), its first bit index kinds2_idx0_c: 0 when the boundary
+// lies inside the chunk (or on its first bit with j0 == lm1), j0 - lm1 when the chunk began inside kind 1.  kinds2_decode: the
+// (index, kind) of ion j — what `while (idx >= lm1) { idx -= lm1; kind++; }` leaves for j < 2 * lm1.
+// tests/test_two_kinds_emulation.py holds all of them to the general walks for every lm1 up to 200 and every chunk.
+SAGE_HD uint32_t kinds2_bound(uint32_t j0, uint32_t lm1) { return j0 >= lm1 ? 0u : lm1 - j0 < 64u ? lm1 - j0 : 64u; }
+SAGE_HD uint64_t kinds2_nt_mask(uint32_t bound) { return bound >= 64u ? ~0ull : (1ull << bound) - 1ull; }
+SAGE_HD uint32_t kinds2_idx0_c(uint32_t j0, uint32_t lm1) { return j0 >= lm1 ? j0 - lm1 : 0u; }
+SAGE_HD uint32_t kinds2_decode(uint32_t j, uint32_t lm1, bool& cterm) {
+    cterm = j >= lm1;
+    return j - (cterm ? lm1 : 0u);
+}
+
 // The ITEMS of a heavy candidate's chunk in one list: M1 / M2 / M3 have bit i set where ion i of the chunk passed the bitmap at
 // fragment charge 1 / 2 / 3, and the reference visits the (ion, charge) pairs ion by ion, charge by charge.  coop_items_below(i):
 // the items of the ions below bit i (i == 64: all of them, N) — so a kind segment [lo, lo + len) owns the positions

@@ -95,8 +95,11 @@ struct DevScorer {
     uint32_t dbg_flags;  // timing experiments only (SAGE_HIP_DEBUG_FLAGS)
     uint32_t prune_min;  // min_matched_peaks for the rescoring kernels' prune (kernels.hip: score_candidates drops a candidate that cannot
                          //    reach it any more, rescore_spectrum leaves when no candidate reached it); 0: both off (SAGE_HIP_DEBUG_FLAGS=4096)
-    uint32_t rescore_general;  // 1: launch_rescore takes the general instance of rescore_kernel (CHIMERA == true) for every search
-                               //    (SAGE_HIP_RESCORE_GENERAL=1, read at scorer creation: tests and A/B runs of the two routes); host only
+    uint32_t rescore_general;  // host only, decided at scorer creation; bits (RESCORE_GENERAL_*):
+                               //    1: launch_rescore takes the general instance of rescore_kernel (CHIMERA == true) for every search
+                               //       (SAGE_HIP_RESCORE_GENERAL=1: tests and A/B runs of the two routes)
+                               //    2: ... and never the instance compiled for two ion kinds (KINDS2): the database's kinds are not
+                               //       {n-terminal, other}, or SAGE_HIP_RESCORE_KINDS_GENERAL=1
     uint32_t xcd_chunk;  // consecutive schedule positions one XCD takes at a time (kernels.hip: xcd_position); 0: round-robin
     uint32_t fast_log;   // 1: this pass is followed by the exact retry pass, so its rescoring kernel may carry the fast phase of the
                          //    correctly rounded logarithm only and queue the (rare) spectrum it cannot round for (crlog.h)
@@ -314,6 +317,13 @@ void launch_process_big(uint32_t n_big, const uint32_t* big_list, unsigned char*
                         uint32_t* out_count, void* stream);
 void launch_compact(uint32_t n, const uint64_t* peak_off, uint32_t stride, const float* sm, const float* si, float* masses,
                     float* intens, void* stream);
+// DevScorer::rescore_general
+constexpr uint32_t RESCORE_GENERAL_CHIMERA = 1u, RESCORE_GENERAL_KINDS = 2u;
+// The instance of the rescoring kernels a launch_rescore with these arguments takes (sage_hip_debug_rescore_instance; include/sage_hip.h:
+// SAGE_HIP_RESCORE_INST_*): the template arguments of rescore_kernel as bits, or RESCORE_INST_BIG for rescore_big_kernel.
+constexpr uint32_t RESCORE_INST_CHIMERA = 1u, RESCORE_INST_KINDS2 = 2u, RESCORE_INST_FAST = 4u, RESCORE_INST_ACC = 8u, RESCORE_INST_PROF = 16u,
+                   RESCORE_INST_BIG = 32u, RESCORE_INST_NONE = 0xFFFFFFFFu;
+uint32_t rescore_instance_code(const DevScorer& sc, const DevWork& w, bool quick);
 // (returns a hipError_t: hipErrorInvalidValue when `keep` would meet an instance compiled without quick_score's block)
 int launch_rescore(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const DevWork& w,
                    const double* lnfact_table, uint32_t lnfact_n, uint32_t max_ions, SageFeature* out,

@@ -3114,7 +3114,10 @@ __device__ __forceinline__ uint64_t lane_run(uint64_t v, uint32_t src_lane) { re
 // the lanes' own hits of a round's last chunk go through a dense work list in the bitmap's bytes
 constexpr uint32_t DENSE_CAP = 384;  // items of the dense work list: 2 x 4 + 2 bytes each and a flag bit, inside the bitmap's 4 KB
 static_assert(DENSE_CAP % 64 == 0 && DENSE_CAP * 10 + DENSE_CAP / 8 <= PBM_WORDS * 4, "the dense work list fits the bitmap");
-template <class PC, bool LONG = false, bool FAST = false, bool FLAT = !LONG>
+// KINDS2: the instance for a table of exactly two ion kinds, kind 0 n-terminal and kind 1 not ({b, y}, {c, z}, {a, x} — core.h:
+// kinds2_bound ...): an ion's kind is one compare instead of a subtract loop, a heavy chunk's kind segments are the two sides of
+// one boundary instead of a walk, and neither db.n_kinds nor `nterm_mask` is read.
+template <class PC, bool LONG = false, bool FAST = false, bool FLAT = !LONG, bool KINDS2 = false>
 __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevScorer& sc, const uint32_t* pbm, const uint32_t* plut,
                                                  const float* pm, const float* pi, const uint32_t P, const float inv_w,
                                                  const bool valid, const uint64_t ion_base, const uint32_t lm1, const uint32_t nfz,
@@ -3138,7 +3141,7 @@ __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevS
     uint32_t mm = 0;                // matched_b | matched_y << 16 (u16 in the reference)
     const bool scored = valid && lm1 && nfz;
     const float* __restrict__ my = db.ions + ion_base;
-    const uint32_t nions = scored ? db.n_kinds * lm1 : 0u;
+    const uint32_t nions = scored ? (KINDS2 ? 2u : db.n_kinds) * lm1 : 0u;
     for (uint32_t j0 = 0; __ballot(j0 < nions) != 0ull; j0 += 64u) {  // (wave-uniform trip count)
         const bool act = j0 < nions;
         const uint32_t n_here = !act ? 0u : nions - j0 < 64u ? nions - j0 : 64u;
@@ -3302,7 +3305,9 @@ __device__ __forceinline__ void score_candidates(const DevDbView& db, const DevS
                 if (on1 || on2 || on3) ionv = db.ions[base_L + j0 + lane];
                 // the chunk's n-terminal bits, a kind segment at a time (wave-uniform)
                 uint64_t NT = 0ull;
-                {
+                if constexpr (KINDS2) {
+                    NT = kinds2_nt_mask(kinds2_bound(j0, lm1_L));
+                } else {
                     uint64_t rem = M1 | M2 | M3;
                     for (KindSeg g = kind_seg_first(j0, lm1_L); rem && g.lo < 64u; g = kind_seg_next(g, lm1_L)) {
                         const uint64_t seg = kind_seg_mask(g);
@@ -3401,6 +3406,31 @@ TM = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
             // additions, on the reference's operands in the reference's (ion, charge) order.
             uint64_t anyK = K1 | K2 | K3;
             if (pc.slot) pc.heavy((uint32_t)(__popcll(K1) + __popcll(K2) + __popcll(K3)));
+            // (the matches of the set bits of S, in (ion, charge) order, into ACC and the ppm sum: the per-charge route's sums)
+#define SAGE_COOP_ADD(S, ACC)                                                                                       \
+    do {                                                                                                            \
+        const uint32_t bit = (uint32_t)__builtin_ctzll(S);                                                          \
+        S &= S - 1ull;                                                                                              \
+        if ((K1 >> bit) & 1ull) { ACC += lane_valuef(it1, bit); u_pp += lane_valuef(tm1, bit); }                    \
+        if ((K2 >> bit) & 1ull) { ACC += lane_valuef(it2, bit); u_pp += lane_valuef(tm2, bit); }                    \
+        if ((K3 >> bit) & 1ull) { ACC += lane_valuef(it3, bit); u_pp += lane_valuef(tm3, bit); }                    \
+    } while (S);
+            if constexpr (KINDS2) {
+                // two kinds: the bits below the boundary are kind 0's, n-terminal, index j0 at bit 0; the others kind 1's (core.h)
+                const uint32_t bound = kinds2_bound(j0, lm1_L);
+                const uint64_t NT = kinds2_nt_mask(bound);
+                uint64_t Sb = anyK & NT, Sy = anyK & ~NT;
+                if (Sb) {
+                    u_mm += (uint32_t)(__popcll(K1 & NT) + __popcll(K2 & NT) + __popcll(K3 & NT));
+                    run_matched_mask(u_b, Sb, j0);
+                    if (!one_trip) SAGE_COOP_ADD(Sb, u_sb)
+                }
+                if (Sy) {  // (then bound < 64)
+                    u_mm += (uint32_t)(__popcll(K1 & ~NT) + __popcll(K2 & ~NT) + __popcll(K3 & ~NT)) << 16;
+                    run_matched_mask(u_y, Sy >> bound, kinds2_idx0_c(j0, lm1_L));
+                    if (!one_trip) SAGE_COOP_ADD(Sy, u_sy)
+                }
+            } else {
             for (KindSeg g = kind_seg_first(j0, lm1_L); anyK && g.lo < 64u; g = kind_seg_next(g, lm1_L)) {
                 const uint64_t seg = kind_seg_mask(g);
                 uint64_t S = anyK & seg;
@@ -3412,16 +3442,12 @@ TM = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
                 else run_matched_mask(u_y, S >> g.lo, g.idx0);
                 if (one_trip) continue;  // (the sums are made)
                 float acc = nterm ? u_sb : u_sy;
-                do {
-                    const uint32_t bit = (uint32_t)__builtin_ctzll(S);
-                    S &= S - 1ull;
-                    if ((K1 >> bit) & 1ull) { acc += lane_valuef(it1, bit); u_pp += lane_valuef(tm1, bit); }
-                    if ((K2 >> bit) & 1ull) { acc += lane_valuef(it2, bit); u_pp += lane_valuef(tm2, bit); }
-                    if ((K3 >> bit) & 1ull) { acc += lane_valuef(it3, bit); u_pp += lane_valuef(tm3, bit); }
-                } while (S);
+                SAGE_COOP_ADD(S, acc)
                 if (nterm) u_sb = acc;
                 else u_sy = acc;
             }
+            }
+#undef SAGE_COOP_ADD
             if (lane == L) {
                 s.summed_b = u_sb; s.summed_y = u_sy; s.ppm_difference = u_pp;
                 mm = u_mm;
@@ -3454,8 +3480,11 @@ TM = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
                     const uint32_t bit = (uint32_t)__ffsll((long long)any) - 1;
                     any &= any - 1;
                     uint32_t kind_i = 0, idx = j0 + bit;
-                    while (idx >= lm1) { idx -= lm1; kind_i++; }
-                    const uint32_t word = idx | (((nterm_mask >> kind_i) & 1u) << 15) | (bit << 16) | (lane << 24);
+                    bool cterm = false;
+                    if constexpr (KINDS2) idx = kinds2_decode(idx, lm1, cterm);
+                    else while (idx >= lm1) { idx -= lm1; kind_i++; }
+                    const uint32_t nt = KINDS2 ? (cterm ? 0u : 1u) : (nterm_mask >> kind_i) & 1u;
+                    const uint32_t word = idx | (nt << 15) | (bit << 16) | (lane << 24);
                     if ((m1 >> bit) & 1ull) dW[pos++] = word | (1u << 22);
                     if (any_fz2 && ((m2 >> bit) & 1ull)) dW[pos++] = word | (2u << 22);
                     if (any_fz3 && ((m3 >> bit) & 1ull)) dW[pos++] = word | (3u << 22);
@@ -3523,7 +3552,9 @@ TM = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
             const float nion = my[j0 + nbit];  // (the next item's ion is in flight while this one is matched)
             const uint32_t jj = j0 + bit;
             uint32_t kind_i = 0, idx = jj;
-            while (idx >= lm1) { idx -= lm1; kind_i++; }
+            bool cterm = false;
+            if constexpr (KINDS2) idx = kinds2_decode(idx, lm1, cterm);
+            else while (idx >= lm1) { idx -= lm1; kind_i++; }
             for (uint32_t c = 1; c <= nfz; c++) {
                 if (c <= 3 && !(((c == 1 ? m1 : c == 2 ? m2 : m3) >> bit) & 1ull)) continue;
                 // (x / 1.0 == x, x / 2.0 == x * 0.5 bit for bit: the IEEE division only for charges 3 and up; c is wave-uniform)
@@ -3534,7 +3565,7 @@ TM = peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
                 if (pk < 0) continue;
                 const float peak_mass = pm[pk], peak_intensity = pi[pk];
                 s.ppm_difference += peak_intensity * __builtin_fabsf(mz - peak_mass) * 2E6f / (mz + peak_mass);
-                if ((nterm_mask >> kind_i) & 1u) {
+                if (KINDS2 ? !cterm : (nterm_mask >> kind_i) & 1u) {
                     mm += 1u;
                     s.summed_b += peak_intensity;
                     run_matched_packed(b_run, idx);
@@ -3719,7 +3750,7 @@ __device__ __forceinline__ CandGather gather_candidate(const DevDbView& db, cons
     return g;
 }
 
-template <bool ACC, class KA, bool FAST = false, bool CHIMERA = true, class PC>
+template <bool ACC, class KA, bool FAST = false, bool CHIMERA = true, bool KINDS2 = false, class PC>
 __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const DevWork& w,
                                                  const double* __restrict__ lnfact_table, uint32_t lnfact_n,
                                                  SageFeature* __restrict__ out, uint32_t* __restrict__ out_count,
@@ -3753,14 +3784,16 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
                                     __float_as_uint(b.rt ? b.rt[spec] : 0.0f), __float_as_uint(ims));
         *(uint4*)(R.hdr + 4) = make_uint4(b.file_id ? b.file_id[spec] : 0u, tot_matched, tot_scored, 0u);
     }
-#define SAGE_N_ITEMS (valid ? db.n_kinds * lm1 * nfz : 0u)  /* (ion, fragment charge) pairs of this candidate */
+    static_assert(!(KINDS2 && CHIMERA), "the two-kind form is instantiated for the instances without chimera rounds");
+#define SAGE_N_ITEMS (valid ? (KINDS2 ? 2u : db.n_kinds) * lm1 * nfz : 0u)  /* (ion, fragment charge) pairs of this candidate */
 
     double ln_lambda = 0.0;  // (cr_log_pair, first round)
     lds_sync();  // (the peaks are in LDS; the gathers above stay in flight)
     pc.mark(0);
     const bool sym_tol = (sc.tol_mode & TOL_SYM) != 0u;  // (core.h: TolMode — the host's, once per scorer)
-    uint32_t nterm_mask = 0;  // bit k: ion kind k is a / b / c (counts towards matched_b, scoring.rs:727-731)
-    for (uint32_t k = 0; k < db.n_kinds; k++) nterm_mask |= (db.ion_kinds[k] <= 2 ? 1u : 0u) << k;
+    uint32_t nterm_mask = KINDS2 ? 1u : 0u;  // bit k: ion kind k is a / b / c (counts towards matched_b, scoring.rs:727-731)
+    if constexpr (!KINDS2)  // (KINDS2: kind 0 is, kind 1 is not — the host's choice of the instance, launch_rescore)
+        for (uint32_t k = 0; k < db.n_kinds; k++) nterm_mask |= (db.ion_kinds[k] <= 2 ? 1u : 0u) << k;
     uint32_t n_emitted = 0;
     const bool any_fz2 = __ballot(valid && nfz >= 2) != 0ull, any_fz3 = __ballot(valid && nfz >= 3) != 0ull;
     for (uint32_t round = 0;; round++) {
@@ -3771,14 +3804,14 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
             // ions per kind = peptide length - 1 (ion_series.rs:68-85; the ion table holds n_kinds * (L - 1) values per peptide): from
             // the peptide's record, not as (ion_off[pep + 1] - ion_off[pep]) / n_kinds — a 64-bit division per candidate
             const uint32_t plen = pep_rec & 0xFFFFu;
-            lm1 = db.n_kinds && plen ? plen - 1u : 0u;
+            lm1 = (KINDS2 || db.n_kinds) && plen ? plen - 1u : 0u;
             R.meta[lane] = make_uint2(pep_rec, __float_as_uint(pep_mass));  // (for the Feature record of a reporting lane)
         }
         if (round == 0) build_peak_bitmap(pbm, pm, P, sc.pbm_reach);
         lds_sync();
         if (round == 0) {
         if (pc.slot) {  // bytes this spectrum's rescoring asks for: peaks, candidate records, every candidate's ion table
-            const uint32_t ion_bytes = wave_sum(valid ? 4u * db.n_kinds * lm1 + 24u : 0u);
+            const uint32_t ion_bytes = wave_sum(valid ? 4u * (KINDS2 ? 2u : db.n_kinds) * lm1 + 24u : 0u);
             const uint32_t ncand = (uint32_t)__popcll(__ballot(mine != PRESCORE_EMPTY));
             if (lane == 0) pc.bytes(DBG_RESCORE, 8ull * P + 8ull * ncand + ion_bytes);
             // shape of the work: (ion, charge) items of all candidates, of the longest candidate, candidates, peaks
@@ -3799,7 +3832,7 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
         s.ppm_difference = 0.0f;
         s.longest_b = s.longest_y = 0;
         pc.mark(5);  // (... the peak table and the bitmap)
-        score_candidates<PC, false, FAST, !CHIMERA>(db, sc, pbm, plut, pm, pi, P, inv_w, valid, ion_base, lm1, nfz, any_fz2, any_fz3, nterm_mask, sym_tol,
+        score_candidates<PC, false, FAST, !CHIMERA, KINDS2>(db, sc, pbm, plut, pm, pi, P, inv_w, valid, ion_base, lm1, nfz, any_fz2, any_fz3, nterm_mask, sym_tol,
                                                     s, pc, !CHIMERA || !sc.chimera);
         pc.mark(1);  // (... the lanes' own hits)
         // ---- from here on: the arguments through `la`, the spectrum's scalars from R.hdr (see LateArgs) ----
@@ -4238,7 +4271,8 @@ __host__ __device__ inline size_t narrow_scratch_bytes(const DevScorer& sc, cons
 // from 3.7 to 6.0 resp. 7.2 ms per 500 000 C3 spectra.  DESIGN.md 4.7.)
 // FAST: the instance with the short divisions (core.h: div_const_fast), for scorers whose dividends the host has bounded.
 // CHIMERA: see rescore_spectrum — false is the instance of every search without chimera rounds.
-template <bool PROF, bool ACC, bool FAST = false, bool CHIMERA = true>
+// KINDS2: see score_candidates — true (with CHIMERA == false only) is the instance of a database of two ion kinds, n-terminal first.
+template <bool PROF, bool ACC, bool FAST = false, bool CHIMERA = true, bool KINDS2 = false>
 __global__ __launch_bounds__(64) SAGE_RESCORE_WAVES_ATTR void rescore_kernel(RescoreKernargs A) {
     // (ONE argument: rescore_spectrum reads what it needs late straight from the kernarg segment — LateArgs<RescoreKernargs>)
     const DevDbView& db = A.db;
@@ -4336,7 +4370,7 @@ __global__ __launch_bounds__(64) SAGE_RESCORE_WAVES_ATTR void rescore_kernel(Res
         cg = gather_candidate(db, mine);
     }
     // (a list no trim touched is the reference's list already: equal hyperscores are ranked by it, no retry)
-    rescore_spectrum<ACC, RescoreKernargs, FAST, CHIMERA>(db, sc, b, w, lnfact_table, lnfact_n, out, out_count, keep, R, spec, P, mine, cg, tot_m,
+    rescore_spectrum<ACC, RescoreKernargs, FAST, CHIMERA, KINDS2>(db, sc, b, w, lnfact_table, lnfact_n, out, out_count, keep, R, spec, P, mine, cg, tot_m,
                                                           tot_s, sc.exact != 0 || st == ST_OK_ORDERED, true, pc);
 }
 
@@ -4811,6 +4845,8 @@ int spectrum_kernel_prepare(size_t max_lds_bytes) {
                           (const void*)rescore_kernel<false, false, true>, (const void*)rescore_kernel<false, true>,
                           (const void*)rescore_kernel<true, true, false, false>, (const void*)rescore_kernel<false, false, false, false>,
                           (const void*)rescore_kernel<false, false, true, false>, (const void*)rescore_kernel<false, true, false, false>,
+                          (const void*)rescore_kernel<true, true, false, false, true>, (const void*)rescore_kernel<false, false, false, false, true>,
+                          (const void*)rescore_kernel<false, false, true, false, true>,
                           (const void*)narrow_kernel<true, true>, (const void*)narrow_kernel<true, false>,
                           (const void*)narrow_kernel<false, true>, (const void*)narrow_kernel<false, false>, (const void*)annotate_kernel,
                           (const void*)candidates_kernel}) {
@@ -4951,6 +4987,22 @@ static void (*rescore_instance(bool prof, bool acc, bool fast))(RescoreKernargs)
            : acc ? rescore_kernel<false, true, false, CHIMERA>
                  : (fast ? rescore_kernel<false, false, true, CHIMERA> : rescore_kernel<false, false, false, CHIMERA>);
 }
+// ... and the two-kind instances (KINDS2, CHIMERA == false): the profiling one and the production one in its two forms.  The ACC
+// instance without the clocks — the exact retry pass of a wide search, quick_score — has no two-kind form and stays general.
+static void (*rescore_instance_kinds2(bool prof, bool fast))(RescoreKernargs) {
+    return prof ? rescore_kernel<true, true, false, false, true>
+                : (fast ? rescore_kernel<false, false, true, false, true> : rescore_kernel<false, false, false, false, true>);
+}
+uint32_t rescore_instance_code(const DevScorer& sc, const DevWork& w, bool quick) {
+    if (sc.big_path) return RESCORE_INST_BIG;
+    const bool prof = w.dbg != nullptr;
+    const bool acc = prof || !sc.fast_log || quick;
+    const bool general = sc.chimera != 0u || (sc.rescore_general & RESCORE_GENERAL_CHIMERA) != 0u;
+    const bool kinds2 = !general && !(sc.rescore_general & RESCORE_GENERAL_KINDS) && (prof || !acc);
+    const bool fast = !prof && !acc && (sc.tol_mode & TOL_FAST) != 0u;
+    return (general ? RESCORE_INST_CHIMERA : 0u) | (kinds2 ? RESCORE_INST_KINDS2 : 0u) | (fast ? RESCORE_INST_FAST : 0u) |
+           (acc ? RESCORE_INST_ACC : 0u) | (prof ? RESCORE_INST_PROF : 0u);
+}
 int launch_rescore(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const DevWork& w,
                    const double* lnfact_table, uint32_t lnfact_n, uint32_t max_ions, SageFeature* out,
                    uint32_t* out_count, uint8_t* keep, void* stream) {
@@ -4971,9 +5023,13 @@ int launch_rescore(const DevDbView& db, const DevScorer& sc, const DevBatchView&
     const bool acc = prof || !sc.fast_log || keep != nullptr;
     if (keep && !acc) return (int)hipErrorInvalidValue;  // (a selection edited out of step with the kernels fails here, not silently)
     // a search without chimera rounds takes the instance compiled without them (DevScorer::rescore_general: both routes in one build)
-    const bool general = sc.chimera != 0u || sc.rescore_general != 0u;
+    // ... and, when the database's kinds allow it (capi.hip: scorer_init decides once per scorer), the instance compiled for two kinds
+    const uint32_t code = rescore_instance_code(sc, w, keep != nullptr);
+    const bool general = (code & RESCORE_INST_CHIMERA) != 0u;
     const bool fast = (sc.tol_mode & TOL_FAST) != 0u;
-    const auto kern = general ? rescore_instance<true>(prof, acc, fast) : rescore_instance<false>(prof, acc, fast);
+    const auto kern = (code & RESCORE_INST_KINDS2) ? rescore_instance_kinds2(prof, fast)
+                      : general                    ? rescore_instance<true>(prof, acc, fast)
+                                                   : rescore_instance<false>(prof, acc, fast);
     const RescoreKernargs args{db, sc, b, w, lnfact_table, lnfact_n, out, out_count, keep};
     hipLaunchKernelGGL(kern, dim3(b.n), dim3(64), rescore_lds_bytes(sc, b, max_ions, keep != nullptr), (hipStream_t)stream, args);
     return (int)hipSuccess;
