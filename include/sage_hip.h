@@ -812,6 +812,42 @@ int sage_hip_score_candidates_resident(SageScorer* scorer, SageDeviceBatch* batc
  * and the copy back included) and the kernel alone. */
 int sage_hip_last_candidates_timing(const SageScorer* scorer, float* call_ms, float* kernel_ms);
 
+/* ---- site localisation of reported PSMs, Ascore style (after Beausoleil et al. 2006).  An ADDITION over the
+ * reference, additive to ABI 6.  Every peak of a spectrum has a depth rank inside its 100-unit mass window (1 = the most
+ * intense, ranks above 11 stored as 11); an (ion, fragment charge) item of a candidate matches at depth d (1..10) when its
+ * tolerance window — select_most_intense_peak's — holds a peak of rank <= d. */
+typedef struct SageDepthCounts {   /* per candidate */
+    uint16_t n[10];                /* n[d - 1]: items matched at depth d; non-decreasing */
+    uint16_t n_items;              /* N: kinds x ions x fragment charges, as score_candidate walks them */
+    uint16_t pad;
+} SageDepthCounts;
+typedef struct SageLocalisation {  /* per PSM slot */
+    double best_score, second_score;  /* peptide scores: sum_d w[d] * S(n[d], N, d) / 7, S = -10 log10 P(Binomial(N, d/100) >= n) */
+    double ascore;                 /* S(a[depth], Ns, depth) - S(b[depth], Ns, depth); NaN without a second candidate */
+    uint32_t best, second;         /* positions in the slot's list; 0xFFFFFFFF = none */
+    uint32_t n_site_items;         /* Ns: items whose ion differs between best and second (f32 bit patterns) */
+    uint16_t a[10], b[10];         /* site-determining items of best / of second matched at depth d */
+    uint8_t depth;                 /* d*: the depth with the largest a[d] - b[d], ties to the smallest; 0 without a pair */
+    uint8_t pad[3];
+} SageLocalisation;
+/* The lists and their rules are those of sage_hip_score_candidates_resident (same slots, same spectrum states, same
+ * SAGE_HIP_ERR_INVALID cases before any launch), and: all candidates of a slot have the residue count and the number of fragment
+ * charges of the slot's first candidate, else SAGE_HIP_ERR_INVALID; a candidate of more than 65 535 items: SAGE_HIP_ERR_UNSUPPORTED.
+ * per_candidate: [cand_off[n * report_psms]] or NULL.  per_slot: [n * report_psms]; a slot without candidates gets best = second =
+ * 0xFFFFFFFF, ascore = NaN and zeros, a slot with one candidate its best and best_score, second = 0xFFFFFFFF, ascore = NaN.
+ * No candidate at all: SAGE_HIP_OK without a launch, per_slot untouched. */
+int sage_hip_localise_resident(SageScorer* scorer, SageDeviceBatch* batch, const SageFeature* features, const uint32_t* counts,
+                               const uint64_t* cand_off, const uint32_t* cand_pep, const uint8_t* cand_charge,
+                               SageDepthCounts* per_candidate, SageLocalisation* per_slot);
+/* Host only: the f64 arithmetic of DESIGN.md 7f on given counts.  n ([10], may be NULL) with n_items -> depth_scores[10] (S per
+ * depth) and *peptide_score, each optional.  a, b ([10]) with n_site_items -> *depth and *ascore (all four or none).  A count
+ * above its total: SAGE_HIP_ERR_INVALID. */
+int sage_hip_ascore_from_counts(const uint16_t* n, uint32_t n_items, const uint16_t* a, const uint16_t* b, uint32_t n_site_items,
+                                double* depth_scores, double* peptide_score, uint8_t* depth, double* ascore);
+/* HIP-event times of the scorer's last sage_hip_localise_resident call: the whole call on the scorer's stream (uploads, the copies
+ * back and the host's pair selection between the two kernels included) and the two kernels alone. */
+int sage_hip_last_localise_timing(const SageScorer* scorer, float* call_ms, float* kernel_ms);
+
 const char* sage_hip_last_error(void);
 int sage_hip_abi_version(void);
 

@@ -174,6 +174,12 @@ CANDIDATE_SCORE_DTYPE = np.dtype([("hyperscore", "<f8"), ("summed_b", "<f4"), ("
                                   ("matched_b", "<u4"), ("matched_y", "<u4"), ("longest_b", "<u4"), ("longest_y", "<u4"),
                                   ("pad", "<u4")])
 assert CANDIDATE_SCORE_DTYPE.itemsize == 40
+# SageDepthCounts / SageLocalisation (sage_hip.h)
+DEPTH_COUNTS_DTYPE = np.dtype([("n", "<u2", (10,)), ("n_items", "<u2"), ("pad", "<u2")])
+assert DEPTH_COUNTS_DTYPE.itemsize == 24
+LOCALISATION_DTYPE = np.dtype([("best_score", "<f8"), ("second_score", "<f8"), ("ascore", "<f8"), ("best", "<u4"), ("second", "<u4"),
+                               ("n_site_items", "<u4"), ("a", "<u2", (10,)), ("b", "<u2", (10,)), ("depth", "u1"), ("pad", "u1", (3,))])
+assert LOCALISATION_DTYPE.itemsize == 80
 
 ION_KINDS = {"a": 0, "b": 1, "c": 2, "x": 3, "y": 4, "z": 5}
 TOL_KINDS = {"ppm": 0, "pct": 1, "da": 2}
@@ -401,6 +407,9 @@ def load():
         "sage_hip_hostdb_isomer_groups": (C.c_int, [vp, c_u32_p, c_u64_p, c_u32_p, c_u64_p, c_u64_p]),
         "sage_hip_score_candidates_resident": (C.c_int, [vp, vp, vp, c_u32_p, c_u64_p, c_u32_p, c_u8_p, vp]),
         "sage_hip_last_candidates_timing": (C.c_int, [vp, c_float_p, c_float_p]),
+        "sage_hip_localise_resident": (C.c_int, [vp, vp, vp, c_u32_p, c_u64_p, c_u32_p, c_u8_p, vp, vp]),
+        "sage_hip_ascore_from_counts": (C.c_int, [vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp]),
+        "sage_hip_last_localise_timing": (C.c_int, [vp, c_float_p, c_float_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
@@ -427,6 +436,7 @@ EXPORTED_SYMBOLS = [
     "sage_hip_protein_groups", "sage_hip_group_string", "sage_hip_group_strings_free", "sage_hip_group_graph_build",
     "sage_hip_group_graph_view", "sage_hip_group_graph_free", "sage_hip_hostdb_protein_name", "sage_hip_write_results_grouped",
     "sage_hip_hostdb_isomer_groups", "sage_hip_score_candidates_resident", "sage_hip_last_candidates_timing",
+    "sage_hip_localise_resident", "sage_hip_ascore_from_counts", "sage_hip_last_localise_timing",
 ]
 
 

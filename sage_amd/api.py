@@ -706,6 +706,34 @@ class DeviceBatch:
             pass
 
 
+def ascore_from_counts(n=None, n_items=0, a=None, b=None, n_site_items=0):
+    """The f64 arithmetic of site localisation on given integer counts, on the host (sage_hip_ascore_from_counts).
+    n ([10]) with n_items -> depth_scores[10] and peptide_score; a, b ([10]) with n_site_items -> depth and ascore.  Returns a dict
+    of what was asked for."""
+    lib = L.load()
+    out = {}
+    n_p = a_p = b_p = ds_p = ps_p = d_p = as_p = None
+    if n is not None:
+        n = np.ascontiguousarray(n, dtype=np.uint16)
+        if n.shape != (10,):
+            raise ValueError("n needs 10 entries")
+        ds, ps = np.zeros(10, dtype=np.float64), C.c_double()
+        n_p, ds_p, ps_p = n.ctypes.data_as(C.c_void_p), ds.ctypes.data_as(C.c_void_p), C.cast(C.byref(ps), C.c_void_p)
+    if a is not None or b is not None:
+        a, b = np.ascontiguousarray(a, dtype=np.uint16), np.ascontiguousarray(b, dtype=np.uint16)
+        if a.shape != (10,) or b.shape != (10,):
+            raise ValueError("a and b need 10 entries each")
+        depth, asc = C.c_uint8(), C.c_double()
+        a_p, b_p = a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)
+        d_p, as_p = C.cast(C.byref(depth), C.c_void_p), C.cast(C.byref(asc), C.c_void_p)
+    L.check(lib.sage_hip_ascore_from_counts(n_p, int(n_items), a_p, b_p, int(n_site_items), ds_p, ps_p, d_p, as_p))
+    if n is not None:
+        out.update(depth_scores=ds, peptide_score=float(ps.value))
+    if a is not None:
+        out.update(depth=int(depth.value), ascore=float(asc.value))
+    return out
+
+
 class Scorer:
     """scoring.rs:210-309.  `score` takes a whole batch: a per-spectrum call cannot amortise a launch."""
 
@@ -832,6 +860,16 @@ class Scorer:
         scored on the spectrum as PSM r saw it (chimera: after the peak removal of the ranks before it).  cand_charge: precursor
         charge per candidate (None or 0: the PSM's own).  Returns a structured array (L.CANDIDATE_SCORE_DTYPE), one per candidate."""
         lib = L.load()
+        feats, counts, cand_off, cand_pep, cand_charge = self._candidate_lists(dbatch, feats, counts, cand_off, cand_pep, cand_charge)
+        charge_p = None if cand_charge is None else L.as_ptr(cand_charge, C.c_uint8)
+        out = np.zeros(int(cand_off[-1]) if len(cand_off) else 0, dtype=L.CANDIDATE_SCORE_DTYPE)
+        L.check(lib.sage_hip_score_candidates_resident(self._h, dbatch._h, feats.ctypes.data_as(C.c_void_p), L.as_ptr(counts, C.c_uint32),
+                                                       L.as_ptr(cand_off, C.c_uint64), L.as_ptr(cand_pep, C.c_uint32), charge_p,
+                                                       out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def _candidate_lists(self, dbatch, feats, counts, cand_off, cand_pep, cand_charge):
+        """the list arguments of score_candidates / localise, checked and made contiguous"""
         rp = self.params.report_psms
         feats = np.ascontiguousarray(feats).reshape(dbatch.n * rp)
         counts = np.ascontiguousarray(counts, dtype=np.uint32)
@@ -841,19 +879,39 @@ class Scorer:
             raise ValueError("cand_off needs n * report_psms + 1 entries, counts n")
         if len(cand_pep) < int(cand_off.max(initial=0)):
             raise ValueError("cand_off points behind cand_pep")
-        charge_p = None
         if cand_charge is not None:
             if np.any((np.asarray(cand_charge) < 0) | (np.asarray(cand_charge) > 255)):
                 raise ValueError("cand_charge outside 0..255")
             cand_charge = np.ascontiguousarray(cand_charge, dtype=np.uint8)
             if len(cand_charge) != len(cand_pep):
                 raise ValueError("cand_charge and cand_pep differ in length")
-            charge_p = L.as_ptr(cand_charge, C.c_uint8)
-        out = np.zeros(int(cand_off[-1]) if len(cand_off) else 0, dtype=L.CANDIDATE_SCORE_DTYPE)
-        L.check(lib.sage_hip_score_candidates_resident(self._h, dbatch._h, feats.ctypes.data_as(C.c_void_p), L.as_ptr(counts, C.c_uint32),
-                                                       L.as_ptr(cand_off, C.c_uint64), L.as_ptr(cand_pep, C.c_uint32), charge_p,
-                                                       out.ctypes.data_as(C.c_void_p)))
-        return out
+        return feats, counts, cand_off, cand_pep, cand_charge
+
+    def localise(self, dbatch: DeviceBatch, feats: np.ndarray, counts: np.ndarray, cand_off, cand_pep, cand_charge=None,
+                 per_candidate: bool = False):
+        """Site localisation over the lists score_candidates takes: per PSM slot the two candidates with the largest
+        peptide score and the Ascore between them.  Returns a structured array (L.LOCALISATION_DTYPE) of n * report_psms slots —
+        a slot without candidates has best == second == 0xFFFFFFFF and ascore NaN — and, with per_candidate, the depth counts of
+        every candidate (L.DEPTH_COUNTS_DTYPE) as a second value."""
+        lib = L.load()
+        feats, counts, cand_off, cand_pep, cand_charge = self._candidate_lists(dbatch, feats, counts, cand_off, cand_pep, cand_charge)
+        slots = np.zeros(dbatch.n * self.params.report_psms, dtype=L.LOCALISATION_DTYPE)
+        slots["best"] = slots["second"] = 0xFFFFFFFF
+        slots["ascore"] = np.nan
+        total = int(cand_off[-1]) if len(cand_off) else 0
+        cnt = np.zeros(total, dtype=L.DEPTH_COUNTS_DTYPE) if per_candidate else None
+        L.check(lib.sage_hip_localise_resident(self._h, dbatch._h, feats.ctypes.data_as(C.c_void_p), L.as_ptr(counts, C.c_uint32),
+                                               L.as_ptr(cand_off, C.c_uint64), L.as_ptr(cand_pep, C.c_uint32),
+                                               None if cand_charge is None else L.as_ptr(cand_charge, C.c_uint8),
+                                               cnt.ctypes.data_as(C.c_void_p) if per_candidate and total else None,
+                                               slots.ctypes.data_as(C.c_void_p)))
+        return (slots, cnt) if per_candidate else slots
+
+    def last_localise_timing(self):
+        """(ms of the last localise call on the scorer's stream, ms of its two kernels alone), from HIP events"""
+        a, k = C.c_float(), C.c_float()
+        L.check(L.load().sage_hip_last_localise_timing(self._h, C.byref(a), C.byref(k)))
+        return float(a.value), float(k.value)
 
     def last_candidates_timing(self):
         """(ms of the last score_candidates call on the scorer's stream, ms of its kernel alone), from HIP events"""

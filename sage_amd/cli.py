@@ -280,7 +280,40 @@ def best_isomers(cand_off, cand_pep, scores):
     return lens.astype(np.uint32), best_pep, best_h, best_m
 
 
-def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono=None, isomers=None):
+def localisation_candidates(groups, feats, counts):
+    """The candidate lists of Scorer.localise: for every reported PSM whose peptide has positional isomers, the PSM's own peptide
+    followed by isomer_candidates' members.  Returns (cand_off[n * report_psms + 1] u64, cand_pep u32)."""
+    off, others = isomer_candidates(groups, feats, counts)
+    lens = np.diff(off.astype(np.int64))
+    has = lens > 0
+    cand_off = np.zeros(len(lens) + 1, dtype=np.uint64)
+    cand_off[1:] = np.cumsum(lens + has)
+    cand_pep = np.empty(int(cand_off[-1]), dtype=np.uint32)
+    own_at = cand_off[:-1].astype(np.int64)[has]
+    rest = np.ones(len(cand_pep), dtype=bool)
+    rest[own_at] = False
+    cand_pep[own_at] = feats["peptide_idx"].reshape(-1)[has]
+    cand_pep[rest] = others
+    return cand_off, cand_pep
+
+
+def localisation_columns(cand_off, cand_pep, slots):
+    """Per slot, from Scorer.localise's records: (placements, best placement's peptide index, its peptide score, the second one's
+    peptide index, its peptide score, site-determining items, depth, ascore, reported_is_best); NO_ISOMER / 0 / NaN where a slot has
+    no list.  The reported peptide is position 0 of its list."""
+    off = cand_off.astype(np.int64)
+    lens = np.diff(off)
+    some = lens > 0
+    best_pep = np.full(len(lens), NO_ISOMER, dtype=np.uint32)
+    second_pep = np.full(len(lens), NO_ISOMER, dtype=np.uint32)
+    best_pep[some] = cand_pep[off[:-1][some] + slots["best"][some].astype(np.int64)]
+    pair = some & (slots["second"] != NO_ISOMER)
+    second_pep[pair] = cand_pep[off[:-1][pair] + slots["second"][pair].astype(np.int64)]
+    return (lens.astype(np.uint32), best_pep, slots["best_score"].copy(), second_pep, slots["second_score"].copy(),
+            slots["n_site_items"].copy(), slots["depth"].copy(), slots["ascore"].copy(), some & (slots["best"] == 0))
+
+
+def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono=None, isomers=None, localise=None):
     """Scorer::score over every MS2 spectrum of one file (runner.rs:311-325), on all the workers' devices at once: the file's
     spectra are cut into work-balanced shards that are contiguous in PRECURSOR MASS (sharding.plan_mass_shards: index
     replicated, no exchange between devices, and a device walks 1 / N of the mass-sorted index instead of all of it), one host
@@ -288,7 +321,10 @@ def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono
     input order, as `collect()` leaves them.  Returns (features[n, report], counts[n], ids, annotation | None).
     isomers: IndexedDatabase.isomer_groups() — each shard's device then scores the positional isomers of its PSMs next to the
     annotation call, and a fifth value is returned: (isomers, best_isomer peptide, isomer_hyperscore, isomer_matched_peaks),
-    each [n, report] (best_isomers)."""
+    each [n, report] (best_isomers).
+    localise: the same table — each shard's device then localises the modification sites of its PSMs (Scorer.localise over
+    localisation_candidates), and a sixth value is returned: localisation_columns' arrays, each [n, report].  With either of the
+    two asked for, six values are returned, None in the place of the one that was not."""
     import threading
 
     from .sharding import estimate_work, plan_mass_shards, plan_shards, precursor_sort_mass
@@ -313,7 +349,7 @@ def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono
             shards = plan_mass_shards(precursor_sort_mass(raw.precursor_mz, raw.precursor_charge, params), len(workers),
                                       None if narrow else weights)
     results = [None] * len(workers)
-    stage_ms = [(0.0, 0.0, 0.0, 0.0)] * len(workers)  # per worker: preprocess + upload, score, annotate, isomers
+    stage_ms = [(0.0, 0.0, 0.0, 0.0, 0.0)] * len(workers)  # per worker: preprocess + upload, score, annotate, isomers, localisation
     errors = []
 
     def work(k):
@@ -340,9 +376,15 @@ def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono
                 cand_off, cand_pep = isomer_candidates(isomers, feats, counts)
                 iso = tuple(a.reshape(feats.shape) for a in
                             best_isomers(cand_off, cand_pep, scorer.score_candidates(dbatch, feats, counts, cand_off, cand_pep)))
+            t4 = time.time()
+            loc = None
+            if localise is not None:
+                cand_off, cand_pep = localisation_candidates(localise, feats, counts)
+                loc = tuple(a.reshape(feats.shape) for a in
+                            localisation_columns(cand_off, cand_pep, scorer.localise(dbatch, feats, counts, cand_off, cand_pep)))
             dbatch.close()
-            stage_ms[k] = ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (time.time() - t3) * 1e3)
-            results[k] = (feats, counts, ids, ann, idx[kept], iso)  # (idx[kept]: positions in the file of the batch's spectra)
+            stage_ms[k] = ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (time.time() - t4) * 1e3)
+            results[k] = (feats, counts, ids, ann, idx[kept], iso, loc)  # (idx[kept]: positions in the file of the batch's spectra)
         except BaseException as exc:  # noqa: BLE001 — re-raised on the calling thread
             errors.append(exc)
 
@@ -378,9 +420,13 @@ def search_file(workers, processor, raw, sp, host_preprocess, annotate, pep_mono
     valid = np.arange(report)[None, :] < counts[:, None]
     feats["spec_index"] = np.where(valid, np.arange(len(counts), dtype=np.uint32)[:, None], feats["spec_index"])  # row of `ids`
     search_file.last_stage_ms = tuple(max(x[i] for x in stage_ms) for i in range(3))  # (the slowest worker's, per stage)
-    if isomers is not None:
+    if isomers is not None or localise is not None:
         search_file.last_isomer_ms = max(x[3] for x in stage_ms)
-        return feats, counts, ids, ann, tuple(np.concatenate([p[5][j] for p in parts], axis=0)[perm] for j in range(4))
+        search_file.last_localise_ms = max(x[4] for x in stage_ms)
+
+        def merged(at):
+            return tuple(np.concatenate([p[at][j] for p in parts], axis=0)[perm] for j in range(len(parts[0][at])))
+        return feats, counts, ids, ann, merged(5) if isomers is not None else None, merged(6) if localise is not None else None
     return feats, counts, ids, ann
 
 
@@ -442,6 +488,12 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         t_iso = time.time()
         isomer_groups = host.isomer_groups()
         isomer_ms = (time.time() - t_iso) * 1e3
+    # "localise": likewise an addition, over the same table; on its own or next to "score_isomers"
+    localise_groups, localise_parts, localise_ms = None, [], 0.0
+    if bool(cfg.get("localise", False)):
+        t_loc = time.time()
+        localise_groups = host.isomer_groups()
+        localise_ms = (time.time() - t_loc) * 1e3
     feats_all, meta, frags = [], [], []  # per PSM: (filename, spectrum id); matched-fragment rows
     psm_id = 1  # PSM_COUNTER starts at 1 (scoring.rs:163)
     n_searched = 0
@@ -491,7 +543,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
             continue
         t0 = time.time()
         found = search_file(workers, processor, search_raw, sp, host_preprocess, sp["annotate_matches"], host.pep_mono,
-                            isomers=isomer_groups)
+                            isomers=isomer_groups, localise=localise_groups)
         if found is None:
             continue
         feats, counts, ids, ann = found[:4]
@@ -518,6 +570,9 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         if isomer_groups is not None:
             isomer_parts.append(tuple(a[spec_of, rank_of] for a in found[4]))
             isomer_ms += getattr(search_file, "last_isomer_ms", 0.0)
+        if localise_groups is not None:
+            localise_parts.append(tuple(a[spec_of, rank_of] for a in found[5]))
+            localise_ms += getattr(search_file, "last_localise_ms", 0.0)
         meta += [(psm_id + j, name, ids[i]) for j, i in enumerate(spec_of.tolist())]
         if arr is not None:
             for j, (i, r) in enumerate(zip(spec_of.tolist(), rank_of.tolist())):
@@ -615,6 +670,15 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         paths.append(ip)
         isomer_summary = {"isomer_rows": len(rows), "isomer_ms": isomer_ms}
         log(f"- isomer scoring: {int(isomer_ms):8d} ms ({len(rows)} PSMs with positional isomers)")
+    localise_summary = {}
+    if localise_groups is not None:
+        lp = os.path.join(output_directory, "localisation.sage.tsv")
+        cols = [np.concatenate([p[j] for p in localise_parts]) if localise_parts else np.zeros(0) for j in range(9)]
+        rows = output.localisation_rows(host, flat, list(order), psm_ids, *cols)
+        output.write_localisation(lp, rows)
+        paths.append(lp)
+        localise_summary = {"localisation_rows": len(rows), "localisation_ms": localise_ms}
+        log(f"- localisation:   {int(localise_ms):8d} ms ({len(rows)} PSMs with positional isomers)")
     if tmt_parts:  # runner.rs:638-641: only when some spectrum was quantified
         tp = os.path.join(output_directory, "tmt.tsv")
         output.write_tmt_native(tp, isobaric.headers(), filenames, np.concatenate([np.full(len(p[1]), p[0], np.uint32) for p in tmt_parts]),
@@ -640,7 +704,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     stage_totals["total_after_index_ms"] = (time.time() - t_run) * 1e3
     summary = {"version": "sage-hip 0.1 (search-and-score path of sage 0.15.0-beta.2)", "psms": len(flat),
                "spectra_searched": n_searched, "search_ms": search_ms, "stages": stage_totals, "output_paths": paths, **rescore_summary,
-               **lfq_summary, **tmt_summary, **isomer_summary}
+               **lfq_summary, **tmt_summary, **isomer_summary, **localise_summary}
     with open(os.path.join(output_directory, "results.json"), "w") as fh:
         json.dump(dict(cfg, output_paths=paths, summary=summary), fh, indent=2, default=str)
     return summary

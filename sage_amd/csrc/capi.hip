@@ -97,6 +97,7 @@ struct SageDeviceDb {
     std::mutex pm_mu;
     DevBuf<uint64_t> pm_off;
     std::vector<float> h_pep_mono;    // host copy: window-size estimate at batch upload
+    std::vector<uint16_t> h_len;      // host copy of the residue counts: sage_hip_localise_resident's equal-length rule
     DevBuf<SageTheoretical> tm_frag;  // tile-major copy + position table for the large-window kernel
     DevBuf<uint32_t> tm_lut;
     DevBuf<SageTheoretical> tm2_frag; // small-tile copy + table for the narrow kernel's per-peak lookups
@@ -176,6 +177,80 @@ struct SageDeviceBatch {
     DevBatchView view{};
 };
 
+// The depth scores of site localisation: S(n, N, d) = -10 log10 P(X >= n), X ~ Binomial(N, d / 100), by log-sum-exp
+// over k = n .. N in ascending k (N reaches several hundred, where the plain product underflows).  A search asks for the same
+// (n, N, d) again and again — some hundred thousand candidates, a few hundred distinct N —, so every value is computed once, by
+// exactly this arithmetic, and kept; lg[k] = ln Gamma(k + 1) = ln k!.
+// ln Gamma(x) for x >= 1 by the Lanczos approximation with g = 6.0246800407767296 and 13 terms (the rational form and the
+// coefficients of Boost.Math's lanczos13m53, which CPython's math.lgamma evaluates in the same way): the C library's lgamma is
+// not used, since it writes the process-wide `signgam` — two scorers localise on two host threads — and its last bits change from
+// one C library to the next, and with them the last digits of every score in localisation.sage.tsv.
+inline double lgamma_lanczos(double x) {
+    static const double NUM[13] = {23531376880.410759688572007674451636754734846804940, 42919803642.649098768957899047001988850926355848959,
+                                   35711959237.355668049440185451547166705960488635843, 17921034426.037209699919755754458931112671403265390,
+                                   6039542586.3520280050642916443072979210699388420708, 1439720407.3117216736632230727949123939715485786772,
+                                   248874557.86205415651146038641322942321632125127801, 31426415.585400194380614231628318205362874684987640,
+                                   2876370.6289353724412254090516208496135991145378768, 186056.26539522349504029498971604569928220784236328,
+                                   8071.6720023658162106380029022722506138218516325024, 210.82427775157934587250973392071336271166969580291,
+                                   2.5066282746310002701649081771338373386264310793408};
+    static const double DEN[13] = {0.0, 39916800.0, 120543840.0, 150917976.0, 105258076.0, 45995730.0, 13339535.0, 2637558.0,
+                                   357423.0, 32670.0, 1925.0, 66.0, 1.0};
+    const double g = 6.024680040776729583740234375;
+    if (x == 1.0 || x == 2.0) return 0.0;
+    double num = 0.0, den = 0.0;
+    if (x < 5.0) {
+        for (int i = 12; i >= 0; i--) {
+            num = num * x + NUM[i];
+            den = den * x + DEN[i];
+        }
+    } else {  // (in 1 / x: the powers of a large x would overflow)
+        for (int i = 0; i < 13; i++) {
+            num = num / x + NUM[i];
+            den = den / x + DEN[i];
+        }
+    }
+    double r = std::log(num / den) - g;
+    r += (x - 0.5) * (std::log(x + g - 0.5) - 1.0);
+    return r;
+}
+constexpr uint32_t LOC_NONE = 0xFFFFFFFFu;
+const double LOC_WEIGHT[10] = {0.5, 0.75, 1.0, 1.0, 1.0, 1.0, 0.75, 0.5, 0.25, 0.25};
+struct DepthScores {
+    std::vector<double> lg, terms;
+    std::vector<std::vector<double>> by_n_items;  // [N][(n - 1) * 10 + d - 1], NaN = not computed yet
+    size_t kept = 0;
+    double compute(uint32_t n, uint32_t N, uint32_t d) {
+        while (lg.size() <= N) lg.push_back(lgamma_lanczos((double)lg.size() + 1.0));
+        const double p = (double)d / 100.0, lp = std::log(p), lq = std::log(1.0 - p);
+        terms.resize((size_t)N - n + 1);
+        double m = -INFINITY;
+        for (uint32_t k = n; k <= N; k++) {
+            const double v = lg[N] - lg[k] - lg[N - k] + (double)k * lp + (double)(N - k) * lq;
+            terms[k - n] = v;
+            if (v > m) m = v;
+        }
+        double sum = 0.0;
+        for (double v : terms) sum += std::exp(v - m);
+        return -10.0 / std::log(10.0) * (m + std::log(sum));
+    }
+    double get(uint32_t n, uint32_t N, uint32_t d) {
+        if (n == 0 || N == 0) return 0.0;
+        if (kept > (1u << 23)) {  // (64 MB of values: start again)
+            by_n_items.clear();
+            kept = 0;
+        }
+        if (by_n_items.size() <= N) by_n_items.resize((size_t)N + 1);
+        std::vector<double>& t = by_n_items[N];
+        if (t.empty()) {
+            t.assign((size_t)N * 10, std::nan(""));
+            kept += t.size();
+        }
+        double& v = t[(size_t)(n - 1) * 10 + d - 1];
+        if (std::isnan(v)) v = compute(n, N, d);
+        return v;
+    }
+};
+
 struct SageScorer {
     SageDeviceDb* db = nullptr;
     SageScorerParams params{};
@@ -252,6 +327,13 @@ struct SageScorer {
     DevBuf<SageCandidateScore> cs_out;
     Events<4> cs_ev;  // call begin, kernel begin, kernel end, call end
     float cs_call_ms = 0.f, cs_kernel_ms = 0.f;
+    // ... and of sage_hip_localise_resident (the lists go through the cs_* buffers above)
+    DevBuf<SageDepthCounts> lc_counts;
+    DevBuf<uint32_t> lc_list2, lc_pair_a, lc_pair_b;
+    DevBuf<DevSiteCounts> lc_site;
+    Events<6> lc_ev;  // call begin, kernel 1 begin / end, kernel 2 begin / end, call end
+    float lc_call_ms = 0.f, lc_kernel_ms = 0.f;
+    DepthScores lc_scores;
 };
 
 extern "C" {
@@ -689,12 +771,14 @@ int sage_hip_db_create(const SageDbView* v, int device, SageDeviceDb** out) {
     std::vector<uint64_t> ion_off(np + 1, 0);
     std::vector<uint32_t> info(np);
     uint32_t max_ions = 0, max_len = 0;
+    d->h_len.reserve(np);
     for (uint64_t i = 0; i < np; i++) {
         const uint64_t len = v->seq_off[i + 1] - v->seq_off[i];
         // (the production rescoring kernel keeps a candidate's longest-run state in 10-bit fields — kernels.hip, run_matched_packed —;
         // a database with longer peptides is scored by the general instances: scorer_init, DevScorer::long_runs)
         if (len > 65535) return fail(SAGE_HIP_ERR_UNSUPPORTED, "peptide longer than 65535 residues");  // (pep_info: 16 bits)
         max_len = std::max<uint32_t>(max_len, (uint32_t)len);
+        d->h_len.push_back((uint16_t)len);
         const uint64_t cnt = (len ? len - 1 : 0) * nk;
         ion_off[i + 1] = ion_off[i] + cnt;
         max_ions = std::max<uint32_t>(max_ions, (uint32_t)cnt);
@@ -2448,6 +2532,48 @@ int sage_hip_annotate_resident(SageScorer* s, SageDeviceBatch* b, const SageFeat
     return SAGE_HIP_OK;
 }
 
+}  // extern "C"
+// The argument rules of the calls that take candidate lists per PSM slot (sage_hip_score_candidates_resident,
+// sage_hip_localise_resident): everything their kernels index with is checked here — bad input is an error, never a device
+// fault.  total: the number of candidates (0: nothing to do); list: the spectra that have one.
+static int check_candidate_lists(const std::string& who, const SageScorer* s, const SageDeviceBatch* b, const SageFeature* features,
+                                 const uint32_t* counts, const uint64_t* cand_off, const uint32_t* cand_pep, const uint8_t* cand_charge,
+                                 bool out_given, uint64_t& total, std::vector<uint32_t>& list) {
+    const uint32_t n = b->n, rp = s->params.report_psms;
+    const size_t slots = (size_t)n * rp;
+    const uint64_t np = s->db->view.np;
+    if (cand_off[0] != 0) return fail(SAGE_HIP_ERR_INVALID, who + ": cand_off[0] must be 0");
+    for (size_t t = 0; t < slots; t++)
+        if (cand_off[t + 1] < cand_off[t]) return fail(SAGE_HIP_ERR_INVALID, who + ": cand_off decreases at slot " + std::to_string(t));
+    total = cand_off[slots];
+    if (total == 0) return SAGE_HIP_OK;
+    if (!features || !counts || !cand_pep || !out_given) return fail(SAGE_HIP_ERR_INVALID, who + ": null argument");
+    for (uint32_t i = 0; i < n; i++) {
+        const size_t s0 = (size_t)i * rp;
+        if (cand_off[s0 + rp] == cand_off[s0]) continue;
+        if (counts[i] > rp) return fail(SAGE_HIP_ERR_INVALID, who + ": counts[" + std::to_string(i) + "] exceeds report_psms");
+        for (uint32_t r = 0; r < rp; r++) {
+            if (r >= counts[i]) {
+                if (cand_off[s0 + r + 1] != cand_off[s0 + r])
+                    return fail(SAGE_HIP_ERR_INVALID, who + ": candidates on slot " + std::to_string(s0 + r) +
+                                                          ", which holds no PSM (rank >= counts[" + std::to_string(i) + "])");
+                continue;
+            }
+            const SageFeature& f = features[s0 + r];
+            if (f.peptide_idx >= np) return fail(SAGE_HIP_ERR_INVALID, who + ": feature peptide_idx out of range");
+            if (f.charge > 254) return fail(SAGE_HIP_ERR_INVALID, who + ": feature charge above 254");
+        }
+        list.push_back(i);
+    }
+    for (uint64_t c = 0; c < total; c++) {
+        if (cand_pep[c] >= np)
+            return fail(SAGE_HIP_ERR_INVALID, who + ": cand_pep[" + std::to_string(c) + "] is not a peptide of the database");
+        if (cand_charge && cand_charge[c] > 254)
+            return fail(SAGE_HIP_ERR_INVALID, who + ": cand_charge[" + std::to_string(c) + "] above 254");
+    }
+    return SAGE_HIP_OK;
+}
+extern "C" {
 int sage_hip_score_candidates_resident(SageScorer* s, SageDeviceBatch* b, const SageFeature* features, const uint32_t* counts,
                                        const uint64_t* cand_off, const uint32_t* cand_pep, const uint8_t* cand_charge,
                                        SageCandidateScore* out) {
@@ -2456,39 +2582,13 @@ int sage_hip_score_candidates_resident(SageScorer* s, SageDeviceBatch* b, const 
     std::lock_guard<std::mutex> lock(s->mu);
     const uint32_t n = b->n, rp = s->params.report_psms;
     const size_t slots = (size_t)n * rp;
-    const uint64_t np = s->db->view.np;
     s->cs_call_ms = s->cs_kernel_ms = 0.f;
-    // everything the kernel indexes with is checked here: bad input is an error, never a device fault
-    if (cand_off[0] != 0) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: cand_off[0] must be 0");
-    for (size_t t = 0; t < slots; t++)
-        if (cand_off[t + 1] < cand_off[t]) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: cand_off decreases at slot " + std::to_string(t));
-    const uint64_t total = cand_off[slots];
-    if (total == 0) return SAGE_HIP_OK;
-    if (!features || !counts || !cand_pep || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: null argument");
+    uint64_t total = 0;
     std::vector<uint32_t> list;
-    for (uint32_t i = 0; i < n; i++) {
-        const size_t s0 = (size_t)i * rp;
-        if (cand_off[s0 + rp] == cand_off[s0]) continue;
-        if (counts[i] > rp) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: counts[" + std::to_string(i) + "] exceeds report_psms");
-        for (uint32_t r = 0; r < rp; r++) {
-            if (r >= counts[i]) {
-                if (cand_off[s0 + r + 1] != cand_off[s0 + r])
-                    return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: candidates on slot " + std::to_string(s0 + r) +
-                                                          ", which holds no PSM (rank >= counts[" + std::to_string(i) + "])");
-                continue;
-            }
-            const SageFeature& f = features[s0 + r];
-            if (f.peptide_idx >= np) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: feature peptide_idx out of range");
-            if (f.charge > 254) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: feature charge above 254");
-        }
-        list.push_back(i);
-    }
-    for (uint64_t c = 0; c < total; c++) {
-        if (cand_pep[c] >= np)
-            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: cand_pep[" + std::to_string(c) + "] is not a peptide of the database");
-        if (cand_charge && cand_charge[c] > 254)
-            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: cand_charge[" + std::to_string(c) + "] above 254");
-    }
+    if (const int rc = check_candidate_lists("sage_hip_score_candidates_resident", s, b, features, counts, cand_off, cand_pep, cand_charge,
+                                             out != nullptr, total, list))
+        return rc;
+    if (total == 0) return SAGE_HIP_OK;
     if (candidates_lds_bytes(b->view) > 160 * 1024)
         return fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_score_candidates_resident: a spectrum of the batch has more peaks than a compute unit's LDS holds");
     HIP_TRY(hipSetDevice(s->db->device));
@@ -2524,6 +2624,206 @@ int sage_hip_last_candidates_timing(const SageScorer* s, float* call_ms, float* 
     if (!s || !call_ms || !kernel_ms) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_last_candidates_timing: null argument");
     *call_ms = s->cs_call_ms;
     *kernel_ms = s->cs_kernel_ms;
+    return SAGE_HIP_OK;
+}
+
+}  // extern "C"
+// ---- site localisation: the f64 arithmetic over the integer counts the device returns ----
+namespace {
+double peptide_score(DepthScores& ds, const uint16_t* n, uint32_t N) {
+    double sum = 0.0;
+    for (uint32_t d = 1; d <= 10; d++) sum += LOC_WEIGHT[d - 1] * ds.get(n[d - 1], N, d);
+    return sum / 7.0;
+}
+// d*: the depth with the largest a[d] - b[d] (signed), ties to the smallest; the Ascore there
+double ascore_of(DepthScores& ds, const uint16_t* a, const uint16_t* b, uint32_t Ns, uint8_t& depth) {
+    depth = 1;
+    if (Ns == 0) return 0.0;
+    int best = (int)a[0] - (int)b[0];
+    for (uint32_t d = 2; d <= 10; d++)
+        if ((int)a[d - 1] - (int)b[d - 1] > best) {
+            best = (int)a[d - 1] - (int)b[d - 1];
+            depth = (uint8_t)d;
+        }
+    return ds.get(a[depth - 1], Ns, depth) - ds.get(b[depth - 1], Ns, depth);
+}
+}  // namespace
+extern "C" {
+int sage_hip_ascore_from_counts(const uint16_t* n, uint32_t n_items, const uint16_t* a, const uint16_t* b, uint32_t n_site_items,
+                                double* depth_scores, double* peptide_score_out, uint8_t* depth, double* ascore) {
+    DepthScores ds;
+    if (n) {
+        for (int d = 0; d < 10; d++)
+            if (n[d] > n_items) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_ascore_from_counts: a count exceeds n_items");
+        if (depth_scores)
+            for (uint32_t d = 1; d <= 10; d++) depth_scores[d - 1] = ds.get(n[d - 1], n_items, d);
+        if (peptide_score_out) *peptide_score_out = peptide_score(ds, n, n_items);
+    } else if (depth_scores || peptide_score_out) {
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_ascore_from_counts: depth_scores / peptide_score need n");
+    }
+    if (a || b || depth || ascore) {
+        if (!a || !b || !depth || !ascore) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_ascore_from_counts: a, b, depth and ascore go together");
+        for (int d = 0; d < 10; d++)
+            if (a[d] > n_site_items || b[d] > n_site_items)
+                return fail(SAGE_HIP_ERR_INVALID, "sage_hip_ascore_from_counts: a count exceeds n_site_items");
+        *ascore = ascore_of(ds, a, b, n_site_items, *depth);
+    }
+    return SAGE_HIP_OK;
+}
+
+int sage_hip_localise_resident(SageScorer* s, SageDeviceBatch* b, const SageFeature* features, const uint32_t* counts,
+                               const uint64_t* cand_off, const uint32_t* cand_pep, const uint8_t* cand_charge,
+                               SageDepthCounts* per_candidate, SageLocalisation* per_slot) {
+    const std::string who = "sage_hip_localise_resident";
+    if (!s || !b || !cand_off) return fail(SAGE_HIP_ERR_INVALID, who + ": null argument");
+    if (b->device != s->db->device) return fail(SAGE_HIP_ERR_INVALID, "batch and scorer live on different devices");
+    std::lock_guard<std::mutex> lock(s->mu);
+    const uint32_t n = b->n, rp = s->params.report_psms;
+    const size_t slots = (size_t)n * rp;
+    s->lc_call_ms = s->lc_kernel_ms = 0.f;
+    uint64_t total = 0;
+    std::vector<uint32_t> list;
+    if (const int rc = check_candidate_lists(who, s, b, features, counts, cand_off, cand_pep, cand_charge, per_slot != nullptr, total, list))
+        return rc;
+    if (total == 0) return SAGE_HIP_OK;
+    // the pair's items are compared position by position: one residue count and one number of fragment charges per slot
+    const std::vector<uint16_t>& len = s->db->h_len;
+    const uint32_t nk = s->db->view.n_kinds;
+    for (uint32_t i : list)
+        for (uint32_t r = 0; r < counts[i]; r++) {
+            const size_t slot = (size_t)i * rp + r;
+            uint32_t len0 = 0, nfz0 = 0;
+            for (uint64_t c = cand_off[slot]; c < cand_off[slot + 1]; c++) {
+                const uint32_t z = cand_charge && cand_charge[c] ? cand_charge[c] : features[slot].charge;
+                const uint32_t nfz = sagecore::max_fragment_charge(s->dev.max_fragment_charge, z) - 1, l = len[cand_pep[c]];
+                if (c == cand_off[slot]) {
+                    len0 = l;
+                    nfz0 = nfz;
+                }
+                if (l != len0 || nfz != nfz0)
+                    return fail(SAGE_HIP_ERR_INVALID, who + ": the candidates of slot " + std::to_string(slot) +
+                                                          " differ in residue count or in fragment charges (cand_pep[" + std::to_string(c) + "])");
+                if ((uint64_t)nk * (l ? l - 1 : 0) * nfz > 65535)
+                    return fail(SAGE_HIP_ERR_UNSUPPORTED, who + ": cand_pep[" + std::to_string(c) + "] has more than 65535 items");
+            }
+        }
+    if (localise_lds_bytes(b->view) > 160 * 1024)
+        return fail(SAGE_HIP_ERR_UNSUPPORTED, who + ": a spectrum of the batch has more peaks than a compute unit's LDS holds");
+    std::vector<SageDepthCounts> own;
+    if (!per_candidate) {
+        own.resize(total);
+        per_candidate = own.data();
+    }
+    HIP_TRY(hipSetDevice(s->db->device));
+    HIP_TRY(s->lc_ev.create());
+    HIP_TRY(s->an_feats.reserve(slots));
+    HIP_TRY(s->an_counts.reserve(n));
+    HIP_TRY(s->cs_off.reserve(slots + 1));
+    HIP_TRY(s->cs_list.reserve(list.size()));
+    HIP_TRY(s->lc_list2.reserve(list.size()));
+    HIP_TRY(s->cs_pep.reserve(total));
+    if (cand_charge) HIP_TRY(s->cs_charge.reserve(total));
+    HIP_TRY(s->lc_counts.reserve(total));
+    HIP_TRY(s->lc_pair_a.reserve(slots));
+    HIP_TRY(s->lc_pair_b.reserve(slots));
+    HIP_TRY(s->lc_site.reserve(slots));
+    hipStream_t st = s->stream;
+    HIP_TRY(hipEventRecord(s->lc_ev[0], st));
+    HIP_TRY(hipMemcpyAsync(s->an_feats.p, features, slots * sizeof(SageFeature), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->an_counts.p, counts, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->cs_off.p, cand_off, (slots + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->cs_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->cs_pep.p, cand_pep, total * 4, hipMemcpyHostToDevice, st));
+    if (cand_charge) HIP_TRY(hipMemcpyAsync(s->cs_charge.p, cand_charge, total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(s->lc_ev[1], st));
+    launch_depth_counts(s->db->view, s->dev, b->view, s->an_feats.p, s->an_counts.p, s->cs_list.p, (uint32_t)list.size(), s->cs_off.p,
+                        s->cs_pep.p, cand_charge ? s->cs_charge.p : nullptr, s->lc_counts.p, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->lc_ev[2], st));
+    HIP_TRY(hipMemcpyAsync(per_candidate, s->lc_counts.p, total * sizeof(SageDepthCounts), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // best and second peptide score per slot: a plain f64 `>`, ties to the smaller position
+    std::vector<uint32_t> pair_a(slots, LOC_NONE), pair_b(slots, LOC_NONE), list2;
+    for (size_t slot = 0; slot < slots; slot++) {
+        SageLocalisation& o = per_slot[slot];
+        std::memset(&o, 0, sizeof o);
+        o.best = o.second = LOC_NONE;
+        o.ascore = std::nan("");
+    }
+    for (uint32_t i : list) {
+        bool pairs = false;
+        for (uint32_t r = 0; r < counts[i]; r++) {
+            const size_t slot = (size_t)i * rp + r;
+            const uint64_t c0 = cand_off[slot], c1 = cand_off[slot + 1];
+            if (c1 == c0) continue;
+            SageLocalisation& o = per_slot[slot];
+            double ps1 = 0.0, ps2 = 0.0;
+            uint32_t i1 = LOC_NONE, i2 = LOC_NONE;
+            for (uint64_t c = c0; c < c1; c++) {
+                const double ps = peptide_score(s->lc_scores, per_candidate[c].n, per_candidate[c].n_items);
+                const uint32_t at = (uint32_t)(c - c0);
+                if (i1 == LOC_NONE || ps > ps1) {
+                    ps2 = ps1;
+                    i2 = i1;
+                    ps1 = ps;
+                    i1 = at;
+                } else if (i2 == LOC_NONE || ps > ps2) {
+                    ps2 = ps;
+                    i2 = at;
+                }
+            }
+            o.best = i1;
+            o.best_score = ps1;
+            o.depth = 0;
+            if (i2 != LOC_NONE) {
+                o.second = i2;
+                o.second_score = ps2;
+                pair_a[slot] = i1;
+                pair_b[slot] = i2;
+                pairs = true;
+            }
+        }
+        if (pairs) list2.push_back(i);
+    }
+    std::vector<DevSiteCounts> site(slots);
+    if (!list2.empty()) {
+        HIP_TRY(hipMemcpyAsync(s->lc_list2.p, list2.data(), list2.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s->lc_pair_a.p, pair_a.data(), slots * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s->lc_pair_b.p, pair_b.data(), slots * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(s->lc_site.p, 0, slots * sizeof(DevSiteCounts), st));
+        HIP_TRY(hipEventRecord(s->lc_ev[3], st));
+        launch_site_counts(s->db->view, s->dev, b->view, s->an_feats.p, s->an_counts.p, s->lc_list2.p, (uint32_t)list2.size(), s->cs_off.p,
+                           s->cs_pep.p, cand_charge ? s->cs_charge.p : nullptr, s->lc_pair_a.p, s->lc_pair_b.p, s->lc_site.p, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(s->lc_ev[4], st));
+        HIP_TRY(hipMemcpyAsync(site.data(), s->lc_site.p, slots * sizeof(DevSiteCounts), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipEventRecord(s->lc_ev[5], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t slot = 0; slot < slots; slot++) {
+        if (pair_b[slot] == LOC_NONE) continue;
+        SageLocalisation& o = per_slot[slot];
+        const DevSiteCounts& c = site[slot];
+        o.n_site_items = c.n_site_items;
+        for (int j = 0; j < 5; j++) {
+            o.a[2 * j] = (uint16_t)(c.a[j] & 0xFFFFu);
+            o.a[2 * j + 1] = (uint16_t)(c.a[j] >> 16);
+            o.b[2 * j] = (uint16_t)(c.b[j] & 0xFFFFu);
+            o.b[2 * j + 1] = (uint16_t)(c.b[j] >> 16);
+        }
+        o.ascore = ascore_of(s->lc_scores, o.a, o.b, o.n_site_items, o.depth);
+    }
+    HIP_TRY(hipEventElapsedTime(&s->lc_call_ms, s->lc_ev[0], s->lc_ev[5]));
+    float k1 = 0.f, k2 = 0.f;
+    HIP_TRY(hipEventElapsedTime(&k1, s->lc_ev[1], s->lc_ev[2]));
+    if (!list2.empty()) HIP_TRY(hipEventElapsedTime(&k2, s->lc_ev[3], s->lc_ev[4]));
+    s->lc_kernel_ms = k1 + k2;
+    return SAGE_HIP_OK;
+}
+int sage_hip_last_localise_timing(const SageScorer* s, float* call_ms, float* kernel_ms) {
+    if (!s || !call_ms || !kernel_ms) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_last_localise_timing: null argument");
+    *call_ms = s->lc_call_ms;
+    *kernel_ms = s->lc_kernel_ms;
     return SAGE_HIP_OK;
 }
 

@@ -413,6 +413,48 @@ SAGE_HD int select_most_intense_peak_lockstep(const float* masses, const float* 
     return best;
 }
 
+// ---- depth ranks of a spectrum's peaks and the min-rank of a tolerance window (site localisation) ---------
+// Peak p lies in window floorf(mass[p] / 100.0f); the peaks are sorted by mass, so a window is a contiguous run.  rank[p] is
+// 1 + the number of peaks q of p's window with intensity[q] > intensity[p], or an equal intensity and q < p; ranks above
+// DEPTH_RANK_CAP are stored as DEPTH_RANK_CAP.  At depth d (1..10) a peak is present iff rank <= d.
+constexpr uint32_t DEPTH_RANK_CAP = 11;
+constexpr uint32_t DEPTH_NO_PEAK = 255;  // min-rank of an empty tolerance window
+constexpr uint32_t DEPTHS = 10;
+SAGE_HD float depth_window(float mass) { return __builtin_floorf(mass / 100.0f); }
+// One peak's rank: the window's ends are found by walking the sorted masses from p to both sides.
+SAGE_HD uint8_t depth_rank_of(const float* masses, const float* intensities, uint32_t n, uint32_t p) {
+    const float w = depth_window(masses[p]), ip = intensities[p];
+    uint32_t rank = 1;
+    for (uint32_t q = p; q-- > 0 && depth_window(masses[q]) == w;) rank += intensities[q] >= ip ? 1u : 0u;
+    for (uint32_t q = p + 1; q < n && depth_window(masses[q]) == w; q++) rank += intensities[q] > ip ? 1u : 0u;
+    return (uint8_t)(rank > DEPTH_RANK_CAP ? DEPTH_RANK_CAP : rank);
+}
+// The smallest rank over the peaks select_most_intense_peak_lockstep looks at for `center`: the same bounds, the same two
+// partition points (`top` = pow2_floor(n)), the same inclusive ends.  DEPTH_NO_PEAK when the window holds no peak.
+SAGE_HD uint32_t min_rank_in_window_lockstep(const float* masses, const uint8_t* rank, uint32_t n, uint32_t top, float center,
+                                             const Tol& tol) {
+    float lo, hi;
+    tol_bounds(tol, center, lo, hi);
+    const int32_t klo = order_key(lo), khi = order_key(hi);
+    uint32_t a = 0, b = 0;
+    for (uint32_t step = top; step; step >>= 1) {
+        const uint32_t ia = a + step, ib = b + step;
+        const int32_t ka = order_key(masses[(ia < n ? ia : n) - 1]);
+        const int32_t kb = order_key(masses[(ib < n ? ib : n) - 1]);
+        a = (ia <= n && ka < klo) ? ia : a;
+        b = (ib <= n && kb <= khi) ? ib : b;
+    }
+    const uint32_t left = a ? a - 1 : 0;
+    const uint32_t right = b > left ? b : left;
+    uint32_t best = DEPTH_NO_PEAK;
+    for (uint32_t idx = left; idx < right; idx++) {
+        const float m = masses[idx];
+        const uint32_t r = rank[idx];
+        if (m >= lo && m <= hi && r < best) best = r;
+    }
+    return best;
+}
+
 // ---- Run (scoring.rs:771-793) -------------------------------------------------------------------
 struct Run {
     uint32_t start, length, last, longest;

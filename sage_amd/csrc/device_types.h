@@ -345,5 +345,18 @@ size_t candidates_lds_bytes(const DevBatchView& b);
 void launch_candidates(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const SageFeature* feats, const uint32_t* counts,
                        const uint32_t* spec_list, uint32_t n_list, const uint64_t* cand_off, const uint32_t* cand_pep,
                        const uint8_t* cand_charge, const double* lnfact_table, uint32_t lnfact_n, SageCandidateScore* out, void* stream);
+// depth_counts_kernel / site_counts_kernel (site localisation): the depth counts of every candidate; the counts over the
+// site-determining items of the pair (pair_a[slot], pair_b[slot]: positions in the slot's list, pair_b == 0xFFFFFFFF: no pair)
+struct DevSiteCounts {
+    uint32_t n_site_items;
+    uint32_t a[5], b[5];  // a[1..10], b[1..10] as u16 pairs, the lower depth in the low half
+};
+size_t localise_lds_bytes(const DevBatchView& b);
+void launch_depth_counts(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const SageFeature* feats, const uint32_t* counts,
+                         const uint32_t* spec_list, uint32_t n_list, const uint64_t* cand_off, const uint32_t* cand_pep,
+                         const uint8_t* cand_charge, SageDepthCounts* out, void* stream);
+void launch_site_counts(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const SageFeature* feats, const uint32_t* counts,
+                        const uint32_t* spec_list, uint32_t n_list, const uint64_t* cand_off, const uint32_t* cand_pep,
+                        const uint8_t* cand_charge, const uint32_t* pair_a, const uint32_t* pair_b, DevSiteCounts* out, void* stream);
 
 }  // namespace sagehip

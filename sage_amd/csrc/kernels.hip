@@ -4794,6 +4794,180 @@ __global__ __launch_bounds__(64) void candidates_kernel(DevDbView db, DevScorer 
     }
 }
 
+// ---- site localisation of reported PSMs -------------------------------------------------------------------------
+// Both kernels walk the spectra of `spec_list` as candidates_kernel does — one wavefront per spectrum, the peaks in LDS, the
+// chimera peak removal replayed between ranks — and keep one more byte per peak there: its depth rank (core.h: depth_rank_of),
+// rebuilt by the whole wavefront, one peak per lane, whenever the spectrum changes.  LDS: pm, pi, rm, rm2, rank = 11 bytes per peak.
+__device__ __forceinline__ void build_depth_ranks(const float* pm, const float* pi, uint8_t* rank, uint32_t P) {
+    for (uint32_t i = lane_id(); i < P; i += WAVE) rank[i] = depth_rank_of(pm, pi, P, i);
+    __syncthreads();
+}
+// the peak removal of PSM `f` between two ranks of a chimeric search, then the ranks of the peaks that are left
+__device__ __forceinline__ void localise_next_rank(const DevDbView& db, const DevScorer& sc, uint32_t wpep, uint32_t wcharge, float* pm,
+                                                   float* pi, uint8_t* rm, uint8_t* rm2, uint8_t* rank, uint32_t& P) {
+    float tic = 0.0f;
+    const uint32_t wmfc = max_fragment_charge(sc.max_fragment_charge, wcharge);
+    const uint64_t wbase = db.ion_off[wpep];
+    const uint32_t wlm1 = db.n_kinds ? (uint32_t)((db.ion_off[wpep + 1] - wbase) / db.n_kinds) : 0;
+    remove_matched_peaks_dev(pm, pi, rm, rm2, P, tic, db.ions + wbase, db.n_kinds * wlm1 * (wmfc - 1), wmfc, sc.fragment_tol);
+    build_depth_ranks(pm, pi, rank, P);
+}
+
+// n[d] of every candidate (d = 1..10): the number of its (ion, fragment charge) items whose tolerance window holds a peak of
+// depth rank <= d.  64 items per trip, one window search per item (its min-rank serves all ten depths), ten ballots per trip;
+// the counts are wave-uniform, lane k keeps those of the k-th candidate of a batch of 64 and stores them as six dwords.
+__global__ __launch_bounds__(64) void depth_counts_kernel(DevDbView db, DevScorer sc, DevBatchView b, const SageFeature* __restrict__ feats,
+                                                          const uint32_t* __restrict__ counts, const uint32_t* __restrict__ spec_list,
+                                                          uint32_t n_list, const uint64_t* __restrict__ cand_off,
+                                                          const uint32_t* __restrict__ cand_pep, const uint8_t* __restrict__ cand_charge,
+                                                          SageDepthCounts* __restrict__ out) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const uint32_t lane = lane_id();
+    if (blockIdx.x >= n_list) return;
+    const uint32_t spec = spec_list[blockIdx.x];
+    if (spec >= b.n) return;
+    float* pm = (float*)smem;
+    float* pi = pm + b.pcap;
+    uint8_t* rm = (uint8_t*)(pi + b.pcap);
+    uint8_t* rm2 = rm + b.pcap;
+    uint8_t* rk = rm2 + b.pcap;
+    const uint64_t p0 = b.peak_off[spec];
+    uint32_t P = (uint32_t)(b.peak_off[spec + 1] - p0);
+    for (uint32_t i = lane; i < P; i += WAVE) {
+        pm[i] = b.masses[p0 + i];
+        pi[i] = b.intensities[p0 + i];
+    }
+    __syncthreads();
+    build_depth_ranks(pm, pi, rk, P);
+    const uint32_t count = counts[spec];
+    const size_t slot0 = (size_t)spec * sc.report_psms;
+    uint32_t ranks = 0;  // ranks up to the last one that has candidates
+    for (uint32_t r = 0; r < count; r++)
+        if (cand_off[slot0 + r + 1] > cand_off[slot0 + r]) ranks = r + 1;
+    for (uint32_t r = 0; r < ranks; r++) {
+        const uint32_t fcharge = feats[slot0 + r].charge;
+        const uint64_t c0 = cand_off[slot0 + r], c1 = cand_off[slot0 + r + 1];
+        const uint32_t ptop = pow2_floor(P);
+        for (uint64_t cb = c0; cb < c1; cb += WAVE) {
+            const uint32_t nb = c1 - cb < WAVE ? (uint32_t)(c1 - cb) : WAVE;
+            uint32_t mine[DEPTHS] = {}, mine_items = 0;
+            for (uint32_t k = 0; k < nb; k++) {
+                const uint32_t pep = cand_pep[cb + k];
+                uint32_t z = cand_charge ? cand_charge[cb + k] : 0u;
+                if (!z) z = fcharge;
+                const uint32_t nfz = max_fragment_charge(sc.max_fragment_charge, z) - 1;
+                const uint64_t ion_base = db.ion_off[pep];
+                const uint32_t lm1 = db.n_kinds ? (uint32_t)((db.ion_off[pep + 1] - ion_base) / db.n_kinds) : 0;
+                const uint32_t n_items = db.n_kinds * lm1 * nfz;
+                uint32_t acc[DEPTHS] = {};  // the same value in every lane
+                for (uint32_t base = 0; base < n_items; base += WAVE) {
+                    const uint32_t t = base + lane;
+                    uint32_t mr = DEPTH_NO_PEAK;
+                    if (t < n_items) {
+                        const uint32_t ion = t / nfz, charge = t - ion * nfz + 1;
+                        mr = min_rank_in_window_lockstep(pm, rk, P, ptop, db.ions[ion_base + ion] / (float)charge, sc.fragment_tol);
+                    }
+#pragma unroll
+                    for (uint32_t d = 0; d < DEPTHS; d++) acc[d] += (uint32_t)__popcll(__ballot(mr <= d + 1u));
+                }
+                if (lane == k) {
+#pragma unroll
+                    for (uint32_t d = 0; d < DEPTHS; d++) mine[d] = acc[d];
+                    mine_items = n_items;
+                }
+            }
+            if (lane < nb) {  // SageDepthCounts: n[10], n_items, pad — u16 each (the host refuses a candidate of more than 65 535 items)
+                uint32_t* o = (uint32_t*)(out + cb + lane);
+#pragma unroll
+                for (uint32_t j = 0; j < DEPTHS / 2; j++) o[j] = mine[2 * j] | (mine[2 * j + 1] << 16);
+                o[DEPTHS / 2] = mine_items;
+            }
+        }
+        if (sc.chimera && r + 1 < ranks) localise_next_rank(db, sc, feats[slot0 + r].peptide_idx, fcharge, pm, pi, rm, rm2, rk, P);
+    }
+}
+
+// The site-determining items of one pair of candidates (A = pair_a, B = pair_b: positions in the slot's list) per slot: item t of
+// A and of B on the same lane; it is site-determining when the two ions differ as f32 bit patterns (before the division by the
+// fragment charge).  out[slot] = {Ns, a[1..10], b[1..10]}: their number and how many of them have min-rank <= d for A and for B,
+// eleven dwords stored by lane 0.  Slots without a pair (pair_b == 0xFFFFFFFF) are not touched.
+__global__ __launch_bounds__(64) void site_counts_kernel(DevDbView db, DevScorer sc, DevBatchView b, const SageFeature* __restrict__ feats,
+                                                         const uint32_t* __restrict__ counts, const uint32_t* __restrict__ spec_list,
+                                                         uint32_t n_list, const uint64_t* __restrict__ cand_off,
+                                                         const uint32_t* __restrict__ cand_pep, const uint8_t* __restrict__ cand_charge,
+                                                         const uint32_t* __restrict__ pair_a, const uint32_t* __restrict__ pair_b,
+                                                         DevSiteCounts* __restrict__ out) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const uint32_t lane = lane_id();
+    if (blockIdx.x >= n_list) return;
+    const uint32_t spec = spec_list[blockIdx.x];
+    if (spec >= b.n) return;
+    float* pm = (float*)smem;
+    float* pi = pm + b.pcap;
+    uint8_t* rm = (uint8_t*)(pi + b.pcap);
+    uint8_t* rm2 = rm + b.pcap;
+    uint8_t* rk = rm2 + b.pcap;
+    const uint64_t p0 = b.peak_off[spec];
+    uint32_t P = (uint32_t)(b.peak_off[spec + 1] - p0);
+    for (uint32_t i = lane; i < P; i += WAVE) {
+        pm[i] = b.masses[p0 + i];
+        pi[i] = b.intensities[p0 + i];
+    }
+    __syncthreads();
+    build_depth_ranks(pm, pi, rk, P);
+    const uint32_t count = counts[spec];
+    const size_t slot0 = (size_t)spec * sc.report_psms;
+    uint32_t ranks = 0;  // ranks up to the last one that has a pair
+    for (uint32_t r = 0; r < count; r++)
+        if (pair_b[slot0 + r] != 0xFFFFFFFFu) ranks = r + 1;
+    for (uint32_t r = 0; r < ranks; r++) {
+        const uint32_t fcharge = feats[slot0 + r].charge;
+        const uint32_t pb = pair_b[slot0 + r];
+        if (pb != 0xFFFFFFFFu) {
+            const uint64_t ca = cand_off[slot0 + r] + pair_a[slot0 + r], cb = cand_off[slot0 + r] + pb;
+            uint32_t z = cand_charge ? cand_charge[ca] : 0u;  // (the host refuses a slot whose candidates differ in item count)
+            if (!z) z = fcharge;
+            const uint32_t nfz = max_fragment_charge(sc.max_fragment_charge, z) - 1;
+            const uint32_t pep_a = cand_pep[ca], pep_b = cand_pep[cb];
+            const uint64_t base_a = db.ion_off[pep_a], base_b = db.ion_off[pep_b];
+            const uint32_t lm1 = db.n_kinds ? (uint32_t)((db.ion_off[pep_a + 1] - base_a) / db.n_kinds) : 0;
+            const uint32_t n_items = db.n_kinds * lm1 * nfz;
+            const uint32_t ptop = pow2_floor(P);
+            uint32_t na[DEPTHS] = {}, nb[DEPTHS] = {}, ns = 0;  // the same value in every lane
+            for (uint32_t base = 0; base < n_items; base += WAVE) {
+                const uint32_t t = base + lane;
+                uint32_t mra = DEPTH_NO_PEAK, mrb = DEPTH_NO_PEAK;
+                bool site = false;
+                if (t < n_items) {
+                    const uint32_t ion = t / nfz, charge = t - ion * nfz + 1;
+                    const float ia = db.ions[base_a + ion], ib = db.ions[base_b + ion];
+                    site = __float_as_uint(ia) != __float_as_uint(ib);
+                    if (site) {
+                        mra = min_rank_in_window_lockstep(pm, rk, P, ptop, ia / (float)charge, sc.fragment_tol);
+                        mrb = min_rank_in_window_lockstep(pm, rk, P, ptop, ib / (float)charge, sc.fragment_tol);
+                    }
+                }
+                ns += (uint32_t)__popcll(__ballot(site));
+#pragma unroll
+                for (uint32_t d = 0; d < DEPTHS; d++) {
+                    na[d] += (uint32_t)__popcll(__ballot(mra <= d + 1u));
+                    nb[d] += (uint32_t)__popcll(__ballot(mrb <= d + 1u));
+                }
+            }
+            if (lane == 0) {
+                DevSiteCounts* o = out + slot0 + r;
+                o->n_site_items = ns;
+#pragma unroll
+                for (uint32_t j = 0; j < DEPTHS / 2; j++) {
+                    o->a[j] = na[2 * j] | (na[2 * j + 1] << 16);
+                    o->b[j] = nb[2 * j] | (nb[2 * j + 1] << 16);
+                }
+            }
+        }
+        if (sc.chimera && r + 1 < ranks) localise_next_rank(db, sc, feats[slot0 + r].peptide_idx, fcharge, pm, pi, rm, rm2, rk, P);
+    }
+}
+
 }  // namespace
 
 size_t prelim_lds_bytes(const DevScorer& sc, const DevBatchView& b, bool huge) { return prelim_layout_bytes(sc, b, huge); }
@@ -4849,7 +5023,7 @@ int spectrum_kernel_prepare(size_t max_lds_bytes) {
                           (const void*)rescore_kernel<false, false, true, false, true>,
                           (const void*)narrow_kernel<true, true>, (const void*)narrow_kernel<true, false>,
                           (const void*)narrow_kernel<false, true>, (const void*)narrow_kernel<false, false>, (const void*)annotate_kernel,
-                          (const void*)candidates_kernel}) {
+                          (const void*)candidates_kernel, (const void*)depth_counts_kernel, (const void*)site_counts_kernel}) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes);
         if (e != hipSuccess) return (int)e;
         // (pbm_bit reads the peak bitmap through LDS address 0: the dynamic LDS of these kernels must start there)
@@ -5112,6 +5286,21 @@ void launch_candidates(const DevDbView& db, const DevScorer& sc, const DevBatchV
     if (b.n == 0 || n_list == 0) return;
     hipLaunchKernelGGL(candidates_kernel, dim3(n_list), dim3(64), candidates_lds_bytes(b), (hipStream_t)stream, db, sc, b, feats, counts,
                        spec_list, n_list, cand_off, cand_pep, cand_charge, lnfact_table, lnfact_n, out);
+}
+size_t localise_lds_bytes(const DevBatchView& b) { return ((size_t)b.pcap * 11 + 15) & ~(size_t)15; }  // pm, pi, rm, rm2, rank
+void launch_depth_counts(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const SageFeature* feats, const uint32_t* counts,
+                         const uint32_t* spec_list, uint32_t n_list, const uint64_t* cand_off, const uint32_t* cand_pep,
+                         const uint8_t* cand_charge, SageDepthCounts* out, void* stream) {
+    if (b.n == 0 || n_list == 0) return;
+    hipLaunchKernelGGL(depth_counts_kernel, dim3(n_list), dim3(64), localise_lds_bytes(b), (hipStream_t)stream, db, sc, b, feats, counts,
+                       spec_list, n_list, cand_off, cand_pep, cand_charge, out);
+}
+void launch_site_counts(const DevDbView& db, const DevScorer& sc, const DevBatchView& b, const SageFeature* feats, const uint32_t* counts,
+                        const uint32_t* spec_list, uint32_t n_list, const uint64_t* cand_off, const uint32_t* cand_pep,
+                        const uint8_t* cand_charge, const uint32_t* pair_a, const uint32_t* pair_b, DevSiteCounts* out, void* stream) {
+    if (b.n == 0 || n_list == 0) return;
+    hipLaunchKernelGGL(site_counts_kernel, dim3(n_list), dim3(64), localise_lds_bytes(b), (hipStream_t)stream, db, sc, b, feats, counts,
+                       spec_list, n_list, cand_off, cand_pep, cand_charge, pair_a, pair_b, out);
 }
 
 }  // namespace sagehip

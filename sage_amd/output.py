@@ -155,6 +155,32 @@ def write_isomers(path: str, rows: Sequence[List[str]]) -> None:
             fh.write(_record(r) + "\n")
 
 
+LOCALISATION_HEADERS = ["psm_id", "peptide", "placements", "best_placement", "peptide_score", "second_placement",
+                        "second_peptide_score", "site_determining_ions", "depth", "ascore", "reported_is_best"]
+
+
+def localisation_rows(db, features, order, psm_ids, placements, best_pep, best_score, second_pep, second_score, n_site_items, depth,
+                      ascore, reported_is_best) -> List[List[str]]:
+    """localisation.sage.tsv (an addition over the reference): one row per PSM whose peptide has positional isomers,
+    in the row order of results.sage.tsv.  The arrays are indexed like `features`; placements counts the reported peptide."""
+    rows = []
+    for i in order:
+        if int(placements[i]) == 0:
+            continue
+        rows.append([str(psm_ids[i]), db.peptide_string(int(features[i]["peptide_idx"])), str(int(placements[i])),
+                     db.peptide_string(int(best_pep[i])), ryu_f64(np.float64(best_score[i])), db.peptide_string(int(second_pep[i])),
+                     ryu_f64(np.float64(second_score[i])), str(int(n_site_items[i])), str(int(depth[i])), ryu_f64(np.float64(ascore[i])),
+                     "true" if reported_is_best[i] else "false"])
+    return rows
+
+
+def write_localisation(path: str, rows: Sequence[List[str]]) -> None:
+    with open(path, "w", newline="") as fh:
+        fh.write(_record(LOCALISATION_HEADERS) + "\n")
+        for r in rows:
+            fh.write(_record(r) + "\n")
+
+
 PIN_HEADERS = ["SpecId", "Label", "ScanNr", "ExpMass", "CalcMass", "FileName", "retentiontime", "ion_mobility", "rank", "z=2",
                "z=3", "z=4", "z=5", "z=6", "z=other", "peptide_len", "missed_cleavages", "semi_enzymatic", "isotope_error",
                "ln(precursor_ppm)", "fragment_ppm", "ln(hyperscore)", "ln(delta_next)", "ln(delta_best)", "aligned_rt",
