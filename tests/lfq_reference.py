@@ -259,7 +259,8 @@ def _seq_sum(a, axis=-1):
     a = np.asarray(a, dtype=np.float64)
     if a.shape[axis] == 0:
         return np.zeros(np.delete(a.shape, axis))
-    return np.take(np.cumsum(a, axis=axis), -1, axis=axis)
+    with np.errstate(invalid="ignore", over="ignore"):  # (inf - inf among the terms is a NaN sum, not an error)
+        return np.take(np.cumsum(a, axis=axis), -1, axis=axis)
 
 
 _acos = np.vectorize(lambda x: math.acos(x) if -1.0 <= x <= 1.0 else math.nan, otypes=[np.float64])  # libm acos
@@ -283,19 +284,29 @@ def summarize(grid, kernel):
     return dot, angle
 
 
-def find_time_warps(dot, ref: int, slack: int = 75):
-    """Traces::find_time_warps (lfq.rs:386-411): `>=` keeps the last best offset."""
+def warp_dots(dot, ref: int, slack: int = 75):
+    """the dot product of every file with the reference file at every offset -slack..=slack: [files, 2 * slack + 1]"""
     n = dot.shape[1]
     reference = dot[ref]
-    warps = []
+    offs = np.arange(-slack, slack + 1)
+    j = offs[:, None] + np.arange(n)[None, :]
+    inside = (j >= 0) & (j < n)
+    out = []
     for row in range(dot.shape[0]):
-        run = np.concatenate([np.zeros(slack), dot[row], np.zeros(slack)])
-        offs = np.arange(-slack, slack + 1)
-        prods = reference[None, :] * run[slack + offs[:, None] + np.arange(n)[None, :]]
-        # out-of-range terms are skipped by the reference; adding +0.0 to a sum that is never -0.0 changes nothing
-        dots = _seq_sum(prods, axis=1)
+        with np.errstate(invalid="ignore", over="ignore"):
+            prods = reference[None, :] * dot[row][np.clip(j, 0, n - 1)]
+        # out-of-range terms are skipped by the reference (so a non-finite reference cell never meets a padding zero);
+        # adding +0.0 in their place to a sum that is never -0.0 changes nothing
+        out.append(_seq_sum(np.where(inside, prods, 0.0), axis=1))
+    return np.array(out)
+
+
+def find_time_warps(dot, ref: int, slack: int = 75):
+    """Traces::find_time_warps (lfq.rs:386-411): `>=` keeps the last best offset."""
+    warps = []
+    for dots in warp_dots(dot, ref, slack):
         best_off, best = 0, 0.0
-        for o, d in zip(offs.tolist(), dots.tolist()):
+        for o, d in zip(range(-slack, slack + 1), dots.tolist()):
             if d >= best:
                 best_off, best = o, d
         warps.append(best_off)
@@ -311,6 +322,17 @@ def apply_time_warps(mat, warps):
             if 0 <= j < n:
                 out[row, i] = mat[row, j]
     return out
+
+
+def _div(a, b) -> float:
+    """f64 division as IEEE 754 defines it (Python's own raises on a zero divisor)"""
+    with np.errstate(all="ignore"):
+        return float(np.float64(a) / np.float64(b))
+
+
+def _sqrt(x) -> float:
+    """f64::sqrt: NaN for a negative or NaN operand (math.sqrt raises)"""
+    return math.sqrt(x) if x >= 0.0 else math.nan
 
 
 def rt_factor_table():
@@ -329,9 +351,9 @@ def scores(dot, angle, strategy: str):
         for f in range(files):
             weighted += angle[f, col] * dot[f, col]
             summed += dot[f, col]
-        spectral.append(weighted / summed)
+        spectral.append(_div(weighted, summed))
         intensity.append(summed)
-        mx = max(mx, summed)
+        mx = max(mx, summed)  # f64::max drops a NaN operand; so does this (mx is never NaN, and `nan > mx` is False)
     rtf = rt_factor_table()
     out = []
     for rt, (s, i) in enumerate(zip(spectral, intensity)):
@@ -340,9 +362,9 @@ def scores(dot, angle, strategy: str):
         elif strategy == "SpectralAngle":
             out.append(s)
         elif strategy == "Intensity":
-            out.append(math.sqrt(i / mx))
+            out.append(_sqrt(_div(i, mx)))
         else:
-            out.append(s * (s * s) * rtf[rt] * math.sqrt(i / mx))
+            out.append(s * (s * s) * rtf[rt] * _sqrt(_div(i, mx)))
     return out, spectral
 
 
@@ -381,7 +403,7 @@ def integrate(grid, settings, kernel=None):
     for f in range(dot.shape[0]):
         weighted += angle[f, best_rt] * dot[f, best_rt]
         summed += dot[f, best_rt]
-    return dict(peak=True, warps=warps, rt=best_rt, score=best, spectral_angle=weighted / summed, areas=areas, left=left,
+    return dict(peak=True, warps=warps, rt=best_rt, score=best, spectral_angle=_div(weighted, summed), areas=areas, left=left,
                 right=right)
 
 

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import lfq_reference as R
-from sage_amd import _lib as L
+from lfq_traces import features_table, isotopes_of, mz_for_mass as _mz_for_mass, ref_feats, ref_spectra, run_world
 from sage_amd.api import (ALIGNMENT_DTYPE, DatabaseParameters, LfqSettings, RawBatch, RawSpectrum, lfq, peptide_compositions)
 from sage_amd.lcms import synthetic_lcms, write_lcms
 from sage_amd.synthetic import synthetic_fasta
@@ -33,42 +33,9 @@ def db():
                               static_mods={"C": 57.0215}).build(synthetic_fasta(60, seed=11))
 
 
-def features_table(db, rows):
-    """rows: (peptide_idx, label, calcmass, file_id, aligned_rt, peptide_q) in confidence order"""
-    f = np.zeros(len(rows), dtype=L.FEATURE_DTYPE)
-    for i, (p, lab, cm, fid, _, _) in enumerate(rows):
-        f[i]["peptide_idx"], f[i]["label"], f[i]["calcmass"], f[i]["file_id"], f[i]["charge"] = p, lab, cm, fid, 2
-    art = np.array([r[4] for r in rows], np.float32)
-    pq = np.array([r[5] for r in rows], np.float32)
-    return f, art, pq
-
-
-def ref_feats(f, art, pq):
-    return dict(peptide_idx=f["peptide_idx"], label=f["label"], calcmass=f["calcmass"], file_id=f["file_id"],
-                aligned_rt=art, peptide_q=pq)
-
-
-def ref_spectra(batches):
-    out = []
-    for b in batches:
-        for i in range(b.n):
-            lo, hi = int(b.peak_off[i]), int(b.peak_off[i + 1])
-            m, it = R.process_ms1(b.mz[lo:hi], b.intensities[lo:hi])
-            out.append((int(b.file_id[i]), F32(b.scan_start_time[i]), m, it))
-    return out
-
-
-def isotopes_of(db):
-    cache = {}
-
-    def f(p):
-        if p not in cache:
-            cache[p] = R.peptide_isotopes(*R.composition(db.sequence(p)))
-        return cache[p]
-    return f
-
-
 def ulp_close(a, b, ulps=ULPS):
+    if np.isnan(a) and np.isnan(b):
+        return True
     return abs(a - b) <= ulps * np.spacing(max(abs(a), abs(b), np.finfo(np.float64).tiny))
 
 
@@ -96,42 +63,7 @@ def assert_same(dev, ref, grids, passing, n_files):
 # ---- the synthetic run --------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def run(db):
-    rng = np.random.default_rng(21)
-    files = synthetic_lcms(db, n_files=3, n_peptides=30, ms1_per_file=400, seed=2, ms1_noise=40)
-    peps, apex = files[0].peptides, files[0].apex
-    rows = []
-    others = np.flatnonzero(db.decoy != 0)[:5]
-    for p in others:  # decoy PSMs first: never selected
-        rows.append((int(p), -1, float(db.pep_mono[p]), 0, 0.5, 0.0))
-    for k, p in enumerate(peps):
-        fid = k % 3
-        if k % 4 == 0:  # a more confident PSM above the threshold: skipped, the next one counts
-            rows.append((int(p), 1, float(db.pep_mono[p]) + 1.0, fid, float(apex[k]) + 0.01, 0.5))
-        rows.append((int(p), 1, float(db.pep_mono[p]), fid, float(apex[k] + rng.normal(0, 0.0003)), 0.001 * (k % 9)))
-        if k % 5 == 0:  # a later confident PSM of the same peptide: ignored
-            rows.append((int(p), 1, float(db.pep_mono[p]), (fid + 1) % 3, float(apex[k]) + 0.002, 0.0))
-    f, art, pq = features_table(db, rows)
-    T = 60.0
-    al = np.zeros(3, ALIGNMENT_DTYPE)
-    for i, lf in enumerate(files):
-        al[i] = (i, F32(T), F32(1.0 / lf.rt_scale), F32(-lf.rt_shift / (T * lf.rt_scale)))
-    batches = []
-    for i, lf in enumerate(files):
-        ms1 = [s for s, lvl in zip(lf.spectra, lf.ms_levels) if lvl == 1]
-        if i == 1:  # decoy windows with signal (mass + 11.06 at rt - 0.01), so the precursor FDR has decoys to count
-            for k in range(0, len(peps), 3):
-                t = (float(apex[k]) - 0.01) * T * lf.rt_scale + lf.rt_shift
-                for s in ms1:
-                    if abs(s.scan_start_time - t) < 0.2:
-                        bait = (float(db.pep_mono[peps[k]]) + np.arange(3) * 1.00335) / 2 + 11.06 + 1.0072764
-                        s.mz = np.sort(np.concatenate([s.mz, bait.astype(np.float32)]))
-                        s.intensity = np.concatenate([s.intensity, rng.lognormal(11.0, 1.0, 3).astype(np.float32)])
-        if i == 0:  # an MS1 spectrum without peaks
-            ms1.insert(10, RawSpectrum(np.zeros(0, np.float32), np.zeros(0, np.float32), 0.0, None, None, ms1[10].scan_start_time, None, 0, "empty"))
-        batches.append(RawBatch(ms1))
-    c, s = peptide_compositions(db.seq_off, db.seq)
-    return dict(f=f, art=art, pq=pq, al=al, batches=batches, carbon=c, sulfur=s,
-                spectra=ref_spectra(batches), alignments=[tuple(a) for a in al.tolist()], cache={})
+    return run_world(db)
 
 
 @pytest.mark.parametrize("combine", [True, False])
@@ -165,17 +97,6 @@ def test_lfq_confidence_order_argument(db, run):
 
 
 # ---- named edge cases ----------------------------------------------------------------------------------------------------------
-def _mz_for_mass(target):
-    """an f32 m/z whose (mz - PROTON) is exactly `target` (f32), or None"""
-    mz = F32(target) + R.PROTON
-    for _ in range(64):
-        d = F32(mz - R.PROTON)
-        if d == target:
-            return mz
-        mz = np.nextafter(mz, F32(np.inf) if d < target else F32(-np.inf))
-    return None
-
-
 def _time_below(r):
     """an f32 spectrum RT s that passes r <= s + RT_TOL but lies below the grid's rt_min = r - RT_TOL: bin 0 by saturation"""
     s = F32(r - R.RT_TOL)
