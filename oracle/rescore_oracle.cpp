@@ -628,6 +628,21 @@ void orc_im_embed(const uint8_t* seq, uint64_t len, float mono, uint8_t charge, 
     im_embed(seq, len, mono, charge, map, out);
 }
 
+// the two embeddings of `n` peptides at once (rows of RT_FEATURES / IM_FEATURES doubles): the design matrices that
+// orc_predict_rt builds below, for callers that drive orc_linreg_fit themselves
+void orc_rt_embed_rows(const uint64_t* seq_off, const uint8_t* seq, const float* mono, uint64_t n, double* out) {
+    size_t map[26];
+    aa_map(map);
+    for (uint64_t i = 0; i < n; ++i) rt_embed(seq + seq_off[i], seq_off[i + 1] - seq_off[i], mono[i], map, out + i * RT_FEATURES);
+}
+void orc_im_embed_rows(const uint64_t* seq_off, const uint8_t* seq, const float* mono, const uint8_t* charge, uint64_t n,
+                       double* out) {
+    size_t map[26];
+    aa_map(map);
+    for (uint64_t i = 0; i < n; ++i)
+        im_embed(seq + seq_off[i], seq_off[i + 1] - seq_off[i], mono[i], charge[i], map, out + i * IM_FEATURES);
+}
+
 // runner.rs:513-530 on `n` Features: sort by poisson + spectrum_q_value, global_alignment, retention_model::predict,
 // mobility_model::predict.  seq_off / seq / mono: Peptide.sequence and .monoisotopic of db[f[i].peptide_idx], per Feature.
 // alignments: [n_files][3] = {max_rt, slope, intercept}.  fitted / r2: [0] retention, [1] mobility.

@@ -128,6 +128,8 @@ def load(kind=None):
     lib.orc_linreg_fit.argtypes = [dp, dp, L.c_u8_p, C.c_uint64, C.c_uint64, dp, dp]
     lib.orc_rt_embed.argtypes = [L.c_u8_p, C.c_uint64, C.c_float, dp]
     lib.orc_im_embed.argtypes = [L.c_u8_p, C.c_uint64, C.c_float, C.c_uint8, dp]
+    lib.orc_rt_embed_rows.argtypes = [L.c_u64_p, L.c_u8_p, L.c_float_p, C.c_uint64, dp]
+    lib.orc_im_embed_rows.argtypes = [L.c_u64_p, L.c_u8_p, L.c_float_p, L.c_u8_p, C.c_uint64, dp]
     lib.orc_predict_rt.argtypes = [vp, C.c_uint64, C.c_uint32, L.c_u64_p, L.c_u8_p, L.c_float_p] + [L.c_float_p] * 7 + \
         [C.POINTER(C.c_int32), dp]
     _libs[kind] = lib
@@ -409,6 +411,23 @@ def im_embed(sequence: str, mono: float, charge: int):
     seq = np.frombuffer(sequence.encode(), dtype=np.uint8).copy()
     out = np.zeros(100)
     load().orc_im_embed(L.as_ptr(seq, C.c_uint8), len(seq), mono, charge, _dptr(out))
+    return out
+
+
+def embed_rows(seq_off, seq, mono, charge=None):
+    """The design matrix of predict_rt: rt_embed of every peptide (n x 69), or im_embed with `charge` given (n x 100)."""
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    mono = np.ascontiguousarray(mono, dtype=np.float32)
+    n = len(mono)
+    if charge is None:
+        out = np.zeros((n, 69))
+        load().orc_rt_embed_rows(L.as_ptr(seq_off, C.c_uint64), L.as_ptr(seq, C.c_uint8), L.as_ptr(mono, C.c_float), n, _dptr(out))
+    else:
+        charge = np.ascontiguousarray(charge, dtype=np.uint8)
+        out = np.zeros((n, 100))
+        load().orc_im_embed_rows(L.as_ptr(seq_off, C.c_uint64), L.as_ptr(seq, C.c_uint8), L.as_ptr(mono, C.c_float),
+                                 L.as_ptr(charge, C.c_uint8), n, _dptr(out))
     return out
 
 

@@ -2,14 +2,14 @@
 block and tile seams, non-finite values, degenerate competitions.  Same helpers and bounds as tests/test_gpu_rescore.py: bit
 equality with the oracle's det=True mode (2.5e-7 relative on posterior_error), compare()'s thresholds against its det=False
 mode where the case carries that leg (tests/test_rescore_edges_cpu.py holds every such flag to the data), compare_rt()'s
-bounds for the RT block, with NaN required to meet NaN.  On the tie tables the device's own outputs are also read with numpy
+bounds for the RT block (per world, from profiles/rt_model_spread.json), with NaN required to meet NaN.  On the tie tables the device's own outputs are also read with numpy
 restatements of ml/qvalue.rs and fdr.rs that do not go through the oracle."""
 import numpy as np
 import pytest
 
 import oracle_lib
 from rescore_edge_cases import RESCORE_CASES, RT_CASES, TIE_CASES, descending_stable_order, picked_q_of, spectrum_q_of
-from test_gpu_rescore import compare, compare_rt
+from test_gpu_rescore import compare, compare_rt, rt_spread
 
 pytestmark = pytest.mark.gpu
 
@@ -40,4 +40,4 @@ def test_rescore_edge_case(gpu_required, name):
 
 @pytest.mark.parametrize("name", list(RT_CASES))
 def test_predict_rt_edge_case(gpu_required, name):
-    compare_rt(*RT_CASES[name], name)
+    compare_rt(*RT_CASES[name], name, rt_spread(name))
