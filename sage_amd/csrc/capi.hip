@@ -1935,7 +1935,8 @@ static int enqueue_compute(SageScorer* s, const DevBatchView& view_in, OutSet& o
     sc2.fast_log = 0u;
     const bool no_timing = !s->timed;  // (sage_hip_scorer_set_timing_interval)
     o.timed = s->timed;
-    o.retry_deferred = phase == 1 && o.two_pass;
+    // (phase 2 is the late launch behind a phase-1 step: the flag stays set until collect_retry has read the pass's counters)
+    if (phase != 2) o.retry_deferred = phase == 1 && o.two_pass;
     if (phase == 2) {
         // the retry list's length: the first pass left it in the counter block, the epilogue sent it home and zeroed the block
         HIP_TRY(hipMemcpyAsync(o.counters.p + CTR_RETRY, o.h_counters + CTR_RETRY, 4, hipMemcpyHostToDevice, st));

@@ -42,8 +42,9 @@ class World:
         t_first = scorer.last_timing()
         of, oc, _, _ = self.orc.score(params, batch)
         n = assert_features_equal(gf, gc, of, oc, context, rel_tol)
-        # once more on the same handle: a narrow-search step launches its exact retry pass only when the step before had something
-        # to retry (the first step of a handle finds out from the counters and launches it late) — both routes, same records
+        # once more on the same handle: the first step of a handle launches its exact retry pass; a later narrow-search step only when
+        # the step before had something to retry.  This repeat of the SAME batch reaches "left out, nothing found" or "not left out",
+        # never the late launch (left out, retries found): tests/test_gpu_handle_sequences.py walks that route
         gfb, gcb = scorer.score_resident(dbatch)
         assert np.array_equal(gc, gcb) and gf[np.arange(gf.shape[1])[None, :] < gc[:, None]].tobytes() == \
             gfb[np.arange(gf.shape[1])[None, :] < gc[:, None]].tobytes(), f"{context}: the second step on the same scorer differs"
