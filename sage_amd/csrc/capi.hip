@@ -1,1004 +1,15 @@
-// capi.hip — the C ABI declared in include/sage_hip.h.
-#include <hip/hip_runtime.h>
+// capi.hip — the scorer of the C ABI declared in include/sage_hip.h: scorer handles, batch upload, and the whole scoring engine —
+// everything a resident or streaming scoring step calls per step is in this one translation unit.  The other entry points:
+// capi_db.hip (the device database), capi_psm.hip (the steps over reported PSMs), capi_host.cpp (what takes no scorer); the
+// handle structs: capi_state.h.
 #include <algorithm>
-#include <atomic>
-#include <cmath>
 #include <chrono>
-#include <cstring>
-#include <memory>
 #include <future>
-#include <mutex>
-#include <string>
-#include <vector>
 
+#include "capi_state.h"
 #include "crlog.h"
-#include "device_types.h"
-// a failed HIP call of an entry point (HIP_TRY): the thread's error string is set, the status returned
-#define HIP_FAILED(e, what) fail(status_of(e), std::string(what) + ": " + hipGetErrorString(e))
-#include "hip_host.h"
-#include "host_db.hpp"
-
-using namespace sagehip;
-
-namespace {
-
-thread_local std::string g_last_error;
-
-int fail(int code, const std::string& msg) {
-    g_last_error = msg;
-    return code;
-}
-
-// page-locked host block, grow-only (staging of the streaming pipeline: DMA at full PCIe rate)
-struct Pinned {
-    unsigned char* p = nullptr;
-    size_t cap = 0;
-    Pinned() = default;
-    Pinned(const Pinned&) = delete;
-    Pinned& operator=(const Pinned&) = delete;
-    ~Pinned() {
-        if (p) (void)hipHostFree(p);
-    }
-    hipError_t reserve(size_t bytes) {
-        if (p && bytes <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipHostMalloc((void**)&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-};
-
-template <class T>
-T* carve(unsigned char*& cur, size_t count) {  // next 64-byte aligned array of a staging block
-    T* p = (T*)cur;
-    cur += ((count * sizeof(T) + 63) / 64) * 64;
-    return p;
-}
-
-}  // namespace
-
-static uint64_t next_db_serial() {
-    static std::atomic<uint64_t> serial{0};
-    return ++serial;
-}
-
-struct SageHostDb {
-    HostDb db;
-    // sage_hip_hostdb_isomer_groups: made by the first call (the sizing call), handed out by the ones after it
-    mutable std::mutex iso_mu;
-    mutable bool iso_made = false;
-    mutable std::vector<uint32_t> iso_of, iso_members;
-    mutable std::vector<uint64_t> iso_off;
-};
-
-struct SageGroupStrings {
-    std::vector<std::string> strings;
-};
-
-struct SageGroupGraph {
-    GroupGraph g;
-};
-
-struct SageDeviceDb {
-    int device = 0;
-    uint64_t serial = next_db_serial();  // never reused: what a batch's stored precursor windows name their index by (WindowKey)
-    DevBuf<float> pep_mono;
-    DevBuf<uint32_t> pep_lut;  // position table of pep_mono (DevDbView::pep_lut)
-    DevBuf<float> ions;
-    DevBuf<uint64_t> ion_off;
-    DevBuf<uint32_t> pep_info;
-    // peptide-major copy: the source of the tile copies while the index is built, afterwards read by the STREAM variant of the
-    // preliminary kernels only (windows of a handful of candidates) — released when the build is done (1.16 GB of C3's HBM) and
-    // made again, from a tile copy, by the first batch that takes the stream variant (ensure_pm_frag; SAGE_HIP_KEEP_PM_FRAG=1 keeps it)
-    DevBuf<SageTheoretical> pm_frag;
-    std::mutex pm_mu;
-    DevBuf<uint64_t> pm_off;
-    std::vector<float> h_pep_mono;    // host copy: window-size estimate at batch upload
-    std::vector<uint16_t> h_len;      // host copy of the residue counts: sage_hip_localise_resident's equal-length rule
-    DevBuf<SageTheoretical> tm_frag;  // tile-major copy + position table for the large-window kernel
-    DevBuf<uint32_t> tm_lut;
-    DevBuf<SageTheoretical> tm2_frag; // small-tile copy + table for the narrow kernel's per-peak lookups
-    DevBuf<sagecore::LutWord> tm2_l1;  // its position table in succinct form (core.h: LutWord): occupancy + rank per 32 cells ...
-    DevBuf<uint32_t> tm2_pos;          // ... and the run starts of the non-empty cells
-    uint32_t max_ions = 0;
-    uint32_t max_len = 0;   // residues of the longest peptide (> 1023: DevScorer::long_runs)
-    uint32_t ion_lo_bits = 0xFFFFFFFFu, ion_hi_bits = 0;  // smallest / largest |ion| of the rescoring table, as f32 bits (scorer_tol_mode)
-    DevDbView view{};
-    uint64_t bytes = 0;
-};
-
-// Device-side working set of ONE scoring pass pair (device_types.h: DevWork).  Kernels of successive batches run in order on
-// one compute stream, so a scorer needs a single set whatever the number of batches in flight.
-struct WorkSet {
-    DevBuf<uint64_t> cand;
-    DevBuf<uint32_t> cand_len, totals, status, queue, retry, item_of, ready;
-    uint32_t epoch = 0;  // of the last search_kernel launch (DevWork::epoch)
-    DevBuf<QueryRec> qrec;
-    DevBuf<uint16_t> seeds;
-    DevBuf<uint64_t> qres;
-    DevBuf<uint32_t> arena;
-    // cheap ties (device_types.h: DevWork::cnt_store): the window counts of every narrow single-query spectrum
-    DevBuf<uint32_t> cnt_store;
-    // the hand-over rows of a narrow first pass (device_types.h: DevWork::hand), one per schedule position
-    DevBuf<uint64_t> hand;
-    DevBuf<float> winbuf;   // tile_count_wing_kernel's windows (DevWork::winbuf), when a batch needs them
-    DevBuf<unsigned char> hugebuf;  // the wide-list kernels' lists in global memory (DevWork::hugebuf), when a configuration needs them
-    uint32_t cap_tie = 0;
-    uint32_t cap_hand = 0;  // rows `hand` holds
-    uint32_t cap_n = 0;     // spectra the narrow-path buffers hold
-    uint32_t cap_wide = 0;  // spectra the large-window buffers hold (0 on the second compute lane, always)
-};
-
-// What a batch leaves behind: PSM records, counters, timing events.  Double-buffered by the streaming pipeline (batch c + 1 is
-// scored while the records of batch c cross PCIe).
-struct OutSet {
-    DevBuf<SageFeature> features;
-    DevBuf<uint32_t> out_count;
-    DevBuf<uint32_t> counters;       // [2 * CTR_COUNT]: first pass, exact retry pass
-    uint32_t* h_counters = nullptr;  // pinned [2 * CTR_COUNT]
-    uint32_t* h_counters_view = nullptr;  // ... as the kernels address it
-    bool counters_clean = false;  // the last command on the counters was the epilogue kernel's reset (and the host waited for it)
-    Pinned h_out;                    // landing block for the records when the caller's arrays are pageable
-    Event ev[5];                     // start, prelim 1, rescore 1, prelim 2, rescore 2
-    Event comp_done, down_done;
-    bool in_flight = false, two_pass = false, with_rescore = false;
-    bool fused = false;          // the narrow spectra were scored by the fused kernel (ev[0] -> ev[1])
-    bool wide_launched = true;   // the large-window kernels ran behind it (else: the batch was expected to hold narrow windows only)
-    bool timed = true;           // ev[] were recorded for this launch (SageScorer::timing_every)
-    bool retry_deferred = false; // two_pass, but the retry pass has not been launched (score_resident_locked: phase 1)
-    bool huge = false;           // this launch's wide-list kernels kept their lists in WorkSet::hugebuf
-    uint32_t n = 0;
-    ~OutSet() {
-        if (h_counters) (void)hipHostFree(h_counters);
-    }
-};
-
-struct SageDeviceBatch {
-    int device = 0;
-    uint32_t n = 0;
-    DevBuf<uint64_t> peak_off;
-    DevBuf<float> masses, intensities, precursor_mz, iso_lo, iso_hi, tic, rt, ims;
-    DevBuf<uint8_t> charge, iso_kind;
-    DevBuf<uint32_t> file_id, order, sort_a, sort_b, sort_idx;
-    DevBuf<uint8_t> sort_tmp;
-    DevBuf<uint4> sched;     // DevBatchView::sched (SAGE_HIP_NO_SCHED=1: not built — the kernels go through `order`)
-    WindowKey win_key{};     // resident batches: what the windows in the records' third uint4 were computed from (DevBatchView::sched_key)
-    DevBuf<uint8_t> meta;    // streaming pipeline: the per-spectrum arrays in one block, the image of the staging block (one copy)
-    uint32_t widest = 0xFFFFFFFFu;  // candidate slots of the batch's widest precursor window (exact_window_check; else unknown)
-    bool maybe_wide = true;  // some precursor window may exceed the narrow kernel's LDS counters (estimated at upload; a wrong
-                             // "no" is noticed after the step — the queue counter — and the step is repeated with the
-                             // large-window kernels)
-    Pinned stage;      // host staging of the arrays above (everything but the peaks when those are already page-locked)
-    Event up_done;     // uploads of this batch finished (its staging block may be refilled)
-    Event sort_done;   // the per-spectrum block is up and the launch schedule sorted (on the scorer's sort stream, beside the peak copies)
-    DevBatchView view{};
-};
-
-// The depth scores of site localisation: S(n, N, d) = -10 log10 P(X >= n), X ~ Binomial(N, d / 100), by log-sum-exp
-// over k = n .. N in ascending k (N reaches several hundred, where the plain product underflows).  A search asks for the same
-// (n, N, d) again and again — some hundred thousand candidates, a few hundred distinct N —, so every value is computed once, by
-// exactly this arithmetic, and kept; lg[k] = ln Gamma(k + 1) = ln k!.
-// ln Gamma(x) for x >= 1 by the Lanczos approximation with g = 6.0246800407767296 and 13 terms (the rational form and the
-// coefficients of Boost.Math's lanczos13m53, which CPython's math.lgamma evaluates in the same way): the C library's lgamma is
-// not used, since it writes the process-wide `signgam` — two scorers localise on two host threads — and its last bits change from
-// one C library to the next, and with them the last digits of every score in localisation.sage.tsv.
-inline double lgamma_lanczos(double x) {
-    static const double NUM[13] = {23531376880.410759688572007674451636754734846804940, 42919803642.649098768957899047001988850926355848959,
-                                   35711959237.355668049440185451547166705960488635843, 17921034426.037209699919755754458931112671403265390,
-                                   6039542586.3520280050642916443072979210699388420708, 1439720407.3117216736632230727949123939715485786772,
-                                   248874557.86205415651146038641322942321632125127801, 31426415.585400194380614231628318205362874684987640,
-                                   2876370.6289353724412254090516208496135991145378768, 186056.26539522349504029498971604569928220784236328,
-                                   8071.6720023658162106380029022722506138218516325024, 210.82427775157934587250973392071336271166969580291,
-                                   2.5066282746310002701649081771338373386264310793408};
-    static const double DEN[13] = {0.0, 39916800.0, 120543840.0, 150917976.0, 105258076.0, 45995730.0, 13339535.0, 2637558.0,
-                                   357423.0, 32670.0, 1925.0, 66.0, 1.0};
-    const double g = 6.024680040776729583740234375;
-    if (x == 1.0 || x == 2.0) return 0.0;
-    double num = 0.0, den = 0.0;
-    if (x < 5.0) {
-        for (int i = 12; i >= 0; i--) {
-            num = num * x + NUM[i];
-            den = den * x + DEN[i];
-        }
-    } else {  // (in 1 / x: the powers of a large x would overflow)
-        for (int i = 0; i < 13; i++) {
-            num = num / x + NUM[i];
-            den = den / x + DEN[i];
-        }
-    }
-    double r = std::log(num / den) - g;
-    r += (x - 0.5) * (std::log(x + g - 0.5) - 1.0);
-    return r;
-}
-constexpr uint32_t LOC_NONE = 0xFFFFFFFFu;
-const double LOC_WEIGHT[10] = {0.5, 0.75, 1.0, 1.0, 1.0, 1.0, 0.75, 0.5, 0.25, 0.25};
-struct DepthScores {
-    std::vector<double> lg, terms;
-    std::vector<std::vector<double>> by_n_items;  // [N][(n - 1) * 10 + d - 1], NaN = not computed yet
-    size_t kept = 0;
-    double compute(uint32_t n, uint32_t N, uint32_t d) {
-        while (lg.size() <= N) lg.push_back(lgamma_lanczos((double)lg.size() + 1.0));
-        const double p = (double)d / 100.0, lp = std::log(p), lq = std::log(1.0 - p);
-        terms.resize((size_t)N - n + 1);
-        double m = -INFINITY;
-        for (uint32_t k = n; k <= N; k++) {
-            const double v = lg[N] - lg[k] - lg[N - k] + (double)k * lp + (double)(N - k) * lq;
-            terms[k - n] = v;
-            if (v > m) m = v;
-        }
-        double sum = 0.0;
-        for (double v : terms) sum += std::exp(v - m);
-        return -10.0 / std::log(10.0) * (m + std::log(sum));
-    }
-    double get(uint32_t n, uint32_t N, uint32_t d) {
-        if (n == 0 || N == 0) return 0.0;
-        if (kept > (1u << 23)) {  // (64 MB of values: start again)
-            by_n_items.clear();
-            kept = 0;
-        }
-        if (by_n_items.size() <= N) by_n_items.resize((size_t)N + 1);
-        std::vector<double>& t = by_n_items[N];
-        if (t.empty()) {
-            t.assign((size_t)N * 10, std::nan(""));
-            kept += t.size();
-        }
-        double& v = t[(size_t)(n - 1) * 10 + d - 1];
-        if (std::isnan(v)) v = compute(n, N, d);
-        return v;
-    }
-};
-
-struct SageScorer {
-    SageDeviceDb* db = nullptr;
-    SageScorerParams params{};
-    DevScorer dev{};
-    std::mutex mu;                   // entry points taking this handle serialise on it (clone the scorer for concurrency)
-    const uint8_t* iso_kind = nullptr;  // the call in progress (under `mu`): SAGE_TOL_* of each spectrum's isolation window, null = Da
-    hipStream_t stream = nullptr;    // compute (and, for resident batches, the result download)
-    hipStream_t up_stream = nullptr, down_stream = nullptr;  // streaming pipeline: H2D of batch c + 1, D2H of batch c - 1
-    hipStream_t side_stream = nullptr;  // kernels of one batch that may run next to each other (the two heap-replay kernels); also the
-                                        // per-spectrum block + launch-schedule sort of an UPLOADING batch, beside its peak copies
-                                        // (stage_and_upload).  Not a stream of its own for that: one more stream per scorer changed
-                                        // how HIP maps streams to hardware queues and the two parts of a small resident step
-                                        // (way streams) stopped overlapping — 62 500 C3 spectra: 0.79 -> 0.98 ms.
-    Event side_fork, side_join;
-    // a resident narrow-search step in `ways` parts, each with its own stream (part 0: `stream`): the parts' kernels overlap each
-    // other's cold starts, tails and retry chains (what two scorer handles on two host threads get, inside one call)
-    uint32_t ways = 0;               // SAGE_HIP_WAYS=1..4; 0: by batch size (score_resident_locked).  Measured on C3: two parts
-                                     // -1 % wall at 500 000 spectra, -6 % at 62 500, nothing more with three or four
-    hipStream_t way_stream[3] = {nullptr, nullptr, nullptr};
-    Event way_fork, way_join[3], way_begin, way_end[4];  // (way_end[p]: behind the last command of part p)
-    DevBuf<uint32_t> win_max;   // exact_window_check's result word
-    bool retry_likely = true;   // the last resident step had spectra to retry (or there was none yet): the next one launches its
-                                // retry pass unconditionally
-    // per-kernel HIP events of a step (SageTiming::prelim_ms / rescore_ms / retry_ms): on every `timing_every`-th scoring call
-    // (sage_hip_scorer_set_timing_interval; 1: every call, 0: never).  Eight event records and six elapsed-time queries cost a
-    // 0.65 ms step ~15 us; a step without them reports the last timed step's kernel times.
-    uint32_t timing_every = 1;
-    uint64_t timing_calls = 0;
-    bool timed = true;          // this call records events
-    float kept_prelim_ms = 0.f, kept_rescore_ms = 0.f, kept_retry_ms = 0.f;
-    DevBuf<double> lnfact;
-    DevBuf<unsigned long long> dbg;  // SAGE_HIP_PHASE_CLOCKS=1: per-phase cycle accumulators
-    uint32_t tile_blocks = 0;        // persistent workgroups of the large-window kernel (u16 counters)
-    uint32_t tile_blocks8 = 0;       // ... of its u8 instance (smaller LDS footprint: more of them per CU)
-    bool cnt8 = true;                // first pass of a search counts in u8 (SAGE_HIP_NO_U8=1 turns it off)
-    bool reuse_counts = true;        // the retry pass reuses the first pass's large-window counts (SAGE_HIP_NO_REUSE=1 turns it off)
-    SageTiming timing{};
-    bool exact_always = false;  // SAGE_HIP_EXACT=1: never use the order-free trims
-    bool one_launch = false;    // SAGE_HIP_ONE_LAUNCH=1: the first pass of narrow windows as one launch of two kinds of workgroups
-                                // (kernels.hip: search_kernel) instead of prelim_kernel, then rescore_kernel — measured slower, like
-                                // the fused kernel: the larger kernel body costs scalar-register spills
-    uint32_t kstride = 64;           // entries per query of the large-window pipeline's seed / heap arrays (DevWork::kstride)
-    bool two_lanes = true;           // streaming pipeline: two chunks of a narrow batch side by side (SAGE_HIP_ONE_LANE=1: one at a time)
-    uint32_t search_lag = 0;         // SAGE_HIP_SEARCH_LAG (DevWork::search_lag)
-    bool sched_desc_forced = false;  // SAGE_HIP_SCHED_DESC was given (else: heaviest precursors first for narrow batches only)
-    uint64_t replay_split = 0xFFFFFFFFull;  // SAGE_HIP_REPLAY_WAVE_MAX | SAGE_HIP_REPLAY_LANE_MAX << 32 (DevWork::replay_split); default: every query by wavefront
-    bool fused = false;         // SAGE_HIP_FUSED=1: the first pass of narrow windows through the fused kernel as well (measured slower
-                                // than the two kernels on MI355X — register pressure, DESIGN.md 4.7 — kept for that comparison)
-    bool zero_copy = true;      // records go straight to page-locked result arrays (SAGE_HIP_NO_ZEROCOPY=1: device buffer + copy)
-    bool fast_ties = true;      // one reported PSM, no chimera: ties at the top settled by rescore_kernel from stored window counts
-                                // (SAGE_HIP_NO_FAST_TIES=1: every tie through the exact retry pass, as in round 3)
-    uint32_t cnt_stride = 0;    // words per spectrum of WorkSet::cnt_store
-    bool hand_rows = true;      // the narrow first pass hands its lists over in schedule order (DevWork::hand) where enqueue_compute
-                                // allows it (SAGE_HIP_DEBUG_FLAGS=131072, read at scorer creation: always by spectrum)
-    bool last_hand = false;     // ... and the last first pass enqueued did (sage_hip_debug_handover_route)
-    uint32_t last_rescore = RESCORE_INST_NONE;  // the rescoring instance the last first pass (or quick_score) launched (sage_hip_debug_rescore_instance)
-    uint32_t qmax = 1;
-    WorkSet ws;                 // the working set (lane 0)
-    WorkSet ws2;                // a second one: the streaming pipeline scores two chunks of a narrow batch side by side (lane 1)
-    OutSet outs[4];             // [k % 4]: the slots of the streaming pipeline; [0..ways): the concurrent parts of a resident step
-    SageDeviceBatch slots[4];   // input buffers of the streaming pipeline (chunk k in slot k % 4: uploads run ahead of the kernels)
-    uint32_t chunk = 131072;    // spectra per pipeline stage (SAGE_HIP_CHUNK): 39.9 M spectra/s host to host on C3 against 38.2 M at 65 536 and 37.3 M at 262 144
-    // scratch of sage_hip_annotate_resident / sage_hip_quick_score_resident, grow-only
-    DevBuf<SageFeature> an_feats;
-    DevBuf<uint32_t> an_counts;
-    DevBuf<uint64_t> an_off;
-    DevBuf<uint8_t> an_kinds, keep;
-    DevBuf<int32_t> an_charges, an_ord;
-    DevBuf<float> an_int, an_calc, an_exp;
-    // ... and of sage_hip_score_candidates_resident (the features and counts go through an_feats / an_counts)
-    DevBuf<uint32_t> cs_list, cs_pep;
-    DevBuf<uint64_t> cs_off;
-    DevBuf<uint8_t> cs_charge;
-    DevBuf<SageCandidateScore> cs_out;
-    Events<4> cs_ev;  // call begin, kernel begin, kernel end, call end
-    float cs_call_ms = 0.f, cs_kernel_ms = 0.f;
-    // ... and of sage_hip_localise_resident (the lists go through the cs_* buffers above)
-    DevBuf<SageDepthCounts> lc_counts;
-    DevBuf<uint32_t> lc_list2, lc_pair_a, lc_pair_b;
-    DevBuf<DevSiteCounts> lc_site;
-    Events<6> lc_ev;  // call begin, kernel 1 begin / end, kernel 2 begin / end, call end
-    float lc_call_ms = 0.f, lc_kernel_ms = 0.f;
-    DepthScores lc_scores;
-};
 
 extern "C" {
-
-// post-search rescoring (rescore.hip)
-int sage_hip_rescore(int device, const SageRescoreInput* in, SageRescoreOutput* out) {
-    if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_rescore: null argument");
-    if (sage_hip_device_count() <= 0) return fail(SAGE_HIP_ERR_NO_DEVICE, "sage_hip_rescore: no HIP device (there is no CPU fallback)");
-    if (in->n >= (1ull << 31)) return fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_rescore: more than 2^31 features");
-    if (in->precursor_tol.kind != SAGE_TOL_PPM && in->precursor_tol.kind != SAGE_TOL_DA)
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_rescore: Pct tolerance should never be used on mz");  // linear_discriminant.rs:142
-    out->passing_spectrum = out->passing_peptide = out->passing_protein = 0;
-    out->lda_fitted = 0;
-    out->device_ms = 0.0f;
-    std::memset(out->coef, 0, sizeof(out->coef));
-    if (in->n == 0) return SAGE_HIP_OK;
-    if (!in->features || !in->peptide_key || !in->protein_key || !out->discriminant_score || !out->posterior_error ||
-        !out->spectrum_q || !out->peptide_q || !out->protein_q)
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_rescore: null array");
-    std::string err;
-    const int rc = rescore_on_device(device, *in, *out, err);
-    return rc == SAGE_HIP_OK ? rc : fail(rc, err);
-}
-
-// protein groups and picked protein-group FDR (rescore.hip, groups.cpp)
-int sage_hip_protein_groups(int device, const SageHostDb* db, const SageGroupInput* in, SageGroupOutput* out) {
-    if (!db || !in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_protein_groups: null argument");
-    if (sage_hip_device_count() <= 0)
-        return fail(SAGE_HIP_ERR_NO_DEVICE, "sage_hip_protein_groups: no HIP device (there is no CPU fallback)");
-    if (in->n >= (1ull << 31)) return fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_protein_groups: more than 2^31 features");
-    out->strings = nullptr;
-    out->n_strings = out->passing_protein_group = 0;
-    out->n_groups = out->n_meta_peptides = out->cover_rounds = 0;
-    out->device_ms = 0.0f;
-    out->host_graph_ms = 0.0;
-    if (in->n && (!in->features || !in->peptide_q || !in->discriminant_score || !out->num_protein_groups || !out->protein_group_q ||
-                  !out->string_id))
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_protein_groups: null array");
-    std::unique_ptr<SageGroupStrings> table(new SageGroupStrings);
-    if (in->n) {
-        std::string err;
-        const int rc = protein_groups_on_device(device, db->db, *in, *out, table->strings, err);
-        if (rc != SAGE_HIP_OK) return fail(rc, err);
-    }
-    out->n_strings = table->strings.size();
-    out->strings = table.release();
-    return SAGE_HIP_OK;
-}
-const char* sage_hip_group_string(const SageGroupStrings* strings, uint64_t id) {
-    return strings && id < strings->strings.size() ? strings->strings[id].c_str() : nullptr;
-}
-void sage_hip_group_strings_free(SageGroupStrings* strings) { delete strings; }
-
-int sage_hip_group_graph_build(const SageHostDb* db, const uint32_t* peptides, uint64_t n, SageGroupGraph** out) {
-    if (!db || !out || (n && !peptides)) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_group_graph_build: null argument");
-    for (uint64_t i = 0; i < n; ++i)
-        if (peptides[i] >= db->db.n_peptides() || (i && peptides[i] <= peptides[i - 1]))
-            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_group_graph_build: peptide indices must be in range, ascending and distinct");
-    std::unique_ptr<SageGroupGraph> g(new SageGroupGraph);
-    build_group_graph(db->db, NameIndex(db->db), peptides, n, g->g);
-    *out = g.release();
-    return SAGE_HIP_OK;
-}
-int sage_hip_group_graph_view(const SageGroupGraph* graph, SageGroupGraphView* out) {
-    if (!graph || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_group_graph_view: null argument");
-    const GroupGraph& g = graph->g;
-    *out = SageGroupGraphView{(uint32_t)g.protein_name.size(), g.n_meta, g.n_groups(), (uint64_t)g.edge_group.size(),
-                              g.protein_db_id.data(), g.protein_decoy.data(), g.group_off.data(), g.group_proteins.data(),
-                              g.evidence_off.data(), g.evidence.data(), g.edge_group.data(), g.edge_meta.data()};
-    return SAGE_HIP_OK;
-}
-void sage_hip_group_graph_free(SageGroupGraph* graph) { delete graph; }
-
-int sage_hip_predict_rt(int device, const SageRtInput* in, SageRtOutput* out) {
-    if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_predict_rt: null argument");
-    if (sage_hip_device_count() <= 0) return fail(SAGE_HIP_ERR_NO_DEVICE, "sage_hip_predict_rt: no HIP device (there is no CPU fallback)");
-    if (in->n >= (1ull << 31)) return fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_predict_rt: more than 2^31 features");
-    out->rt_fitted = out->ims_fitted = 0;
-    out->rt_r2 = out->ims_r2 = 0.0;
-    out->device_ms = 0.0f;
-    if (in->n_files == 0 && in->n) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_predict_rt: n_files == 0");
-    if (in->n == 0) {
-        for (uint32_t k = 0; out->alignments && k < in->n_files; ++k) out->alignments[k] = SageAlignment{k, 0.0f, 1.0f, 0.0f};
-        return SAGE_HIP_OK;
-    }
-    if (!in->features || !in->seq_off || !in->seq || !in->monoisotopic || !out->spectrum_q || !out->aligned_rt ||
-        !out->predicted_rt || !out->delta_rt_model || !out->predicted_ims || !out->delta_ims_model)
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_predict_rt: null array");
-    std::string err;
-    const int rc = predict_rt_on_device(device, *in, *out, err);
-    return rc == SAGE_HIP_OK ? rc : fail(rc, err);
-}
-
-int sage_hip_lfq(int device, const SageLfqInput* in, SageLfqOutput* out) { return sage_hip_lfq_im(device, in, nullptr, out); }
-
-int sage_hip_lfq_im(int device, const SageLfqInput* in, const SageLfqMobility* ms1_mobility, SageLfqOutput* out) {
-    if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: null argument");
-    if (sage_hip_device_count() <= 0) return fail(SAGE_HIP_ERR_NO_DEVICE, "sage_hip_lfq: no HIP device (there is no CPU fallback)");
-    const SageLfqSettings& st = in->settings;
-    if (st.min_charge < 1 || st.max_charge < st.min_charge)
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: precursor charge range must be [lo >= 1, hi >= lo]");
-    if (st.peak_scoring < SAGE_LFQ_RETENTION_TIME || st.peak_scoring > SAGE_LFQ_HYBRID || (st.integration != SAGE_LFQ_APEX &&
-                                                                                           st.integration != SAGE_LFQ_SUM))
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: unknown peak_scoring / integration strategy");
-    if ((in->n_features && (!in->features || !in->aligned_rt || !in->peptide_q)) || (in->n_files && !in->alignments) ||
-        (in->n_ms1 && !in->ms1) || (in->n_peptides && (!in->carbon || !in->sulfur)))
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: null array");
-    if (out->cap && (!out->peptide_idx || !out->charge || !out->decoy || !out->has_peak || !out->peak_rt || !out->left ||
-                     !out->right || !out->score || !out->spectral_angle || !out->q_value || (in->n_files && !out->areas)))
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: null output array");
-    for (uint32_t b = 0; b < in->n_ms1; ++b)
-        if (in->ms1[b].n_spectra && (!in->ms1[b].peak_off || !in->ms1[b].mz || !in->ms1[b].intensities))
-            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_lfq: null MS1 array");
-    std::string err;
-    const int rc = lfq_on_device(device, *in, ms1_mobility, *out, err);
-    return rc == SAGE_HIP_OK ? rc : fail(rc, err);
-}
-
-int sage_hip_write_lfq(const char* path, const SageHostDb* db, const SageLfqOutput* grids, const uint64_t* rows, uint64_t n_rows,
-                       const char* const* filenames, uint32_t n_files) {
-    if (!path || !db || !grids || (n_rows && !rows) || (n_files && !filenames))
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_lfq: null argument");
-    for (uint64_t r = 0; r < n_rows; ++r)
-        if (rows[r] >= grids->n_grids || grids->peptide_idx[rows[r]] >= db->db.n_peptides())
-            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_lfq: row out of range");
-    std::string err;
-    if (!write_lfq(path, db->db, *grids, rows, n_rows, filenames, n_files, err)) return fail(SAGE_HIP_ERR_INVALID, err);
-    return SAGE_HIP_OK;
-}
-
-const char* sage_hip_last_error(void) { return g_last_error.c_str(); }
-int sage_hip_write_tmt(const char* path, const char* const* headers, uint32_t n_labels, uint64_t n_rows, const uint32_t* file_id,
-                       const char* const* spec_ids, const float* ion_injection_time, const float* intensity,
-                       const char* const* filenames, uint32_t n_files) {
-    if (!path || (n_labels && !headers) || (n_rows && (!file_id || !spec_ids || !ion_injection_time || (n_labels && !intensity))) ||
-        (n_files && !filenames))
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_tmt: null argument");
-    for (uint64_t r = 0; r < n_rows; ++r)
-        if (file_id[r] >= n_files || !spec_ids[r]) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_tmt: file id out of range or null id");
-    std::string err;
-    if (!write_tmt(path, headers, n_labels, n_rows, file_id, spec_ids, ion_injection_time, intensity, filenames, n_files, err))
-        return fail(SAGE_HIP_ERR_INVALID, err);
-    return SAGE_HIP_OK;
-}
-int sage_hip_abi_version(void) { return SAGE_HIP_ABI_VERSION; }
-
-// ---------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------
-int sage_hip_hostdb_build(const char* fasta_text, const SageDbParams* params, SageHostDb** out) {
-    if (!fasta_text || !params || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    try {
-        auto h = std::make_unique<SageHostDb>();
-        h->db = build_database(fasta_text, config_from_params(*params));
-        *out = h.release();
-        return SAGE_HIP_OK;
-    } catch (const std::exception& e) {
-        return fail(SAGE_HIP_ERR_INVALID, e.what());
-    }
-}
-int sage_hip_hostdb_build_chunk(const char* fasta_text, const SageDbParams* params, uint64_t first_target, uint64_t n_targets,
-                                SageHostDb** out) {
-    if (!fasta_text || !params || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    try {
-        auto h = std::make_unique<SageHostDb>();
-        h->db = build_database(fasta_text, config_from_params(*params), first_target, n_targets);
-        *out = h.release();
-        return SAGE_HIP_OK;
-    } catch (const std::exception& e) {
-        return fail(SAGE_HIP_ERR_INVALID, e.what());
-    }
-}
-int sage_hip_fasta_num_targets(const char* fasta_text, const SageDbParams* params, uint64_t* out) {
-    if (!fasta_text || !params || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    *out = fasta_num_targets(fasta_text, config_from_params(*params));
-    return SAGE_HIP_OK;
-}
-int sage_hip_prefilter_chunk_size(const char* fasta_text, const SageDbParams* params, uint64_t requested, uint64_t* out) {
-    if (!fasta_text || !params || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    *out = prefilter_chunk_size(fasta_text, config_from_params(*params), requested);
-    return SAGE_HIP_OK;
-}
-int sage_hip_hostdb_merge_kept(const SageHostDb* const* chunks, const uint8_t* const* keep, uint32_t n_chunks,
-                               const SageDbParams* params, SageHostDb** out) {
-    if ((n_chunks && (!chunks || !keep)) || !params || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    try {
-        std::vector<const HostDb*> dbs;
-        std::vector<const uint8_t*> masks;
-        for (uint32_t c = 0; c < n_chunks; ++c) {
-            if (!chunks[c] || !keep[c]) return fail(SAGE_HIP_ERR_INVALID, "null chunk");
-            dbs.push_back(&chunks[c]->db);
-            masks.push_back(keep[c]);
-        }
-        auto h = std::make_unique<SageHostDb>();
-        h->db = merge_kept(dbs, masks, config_from_params(*params));
-        *out = h.release();
-        return SAGE_HIP_OK;
-    } catch (const std::exception& e) {
-        return fail(SAGE_HIP_ERR_INVALID, e.what());
-    }
-}
-void sage_hip_hostdb_free(SageHostDb* db) { delete db; }
-int sage_hip_hostdb_view(const SageHostDb* db, SageDbView* out) {
-    if (!db || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    *out = db->db.view();
-    return SAGE_HIP_OK;
-}
-static uint64_t copy_out(const std::string& s, char* out, uint64_t cap) {
-    if (out && cap >= s.size() + 1) std::memcpy(out, s.c_str(), s.size() + 1);
-    return s.size() + 1;
-}
-uint64_t sage_hip_hostdb_peptide_string(const SageHostDb* db, uint64_t i, char* out, uint64_t cap) {
-    if (!db || i >= db->db.n_peptides()) return 0;
-    return copy_out(db->db.peptide_string(i), out, cap);
-}
-uint64_t sage_hip_hostdb_peptide_proteins(const SageHostDb* db, uint64_t i, char* out, uint64_t cap) {
-    if (!db || i >= db->db.n_peptides()) return 0;
-    return copy_out(db->db.peptide_proteins(i), out, cap);
-}
-int sage_hip_hostdb_peptide_info(const SageHostDb* db, uint64_t i, uint32_t* num_proteins, uint8_t* semi_enzymatic) {
-    if (!db || i >= db->db.n_peptides()) return fail(SAGE_HIP_ERR_INVALID, "peptide index out of range");
-    if (num_proteins) *num_proteins = (uint32_t)(db->db.pep_protein_off[i + 1] - db->db.pep_protein_off[i]);
-    if (semi_enzymatic) *semi_enzymatic = db->db.semi[i];
-    return SAGE_HIP_OK;
-}
-struct SageMzml {
-    MzmlRun run;
-};
-int sage_hip_mzml_read(const char* path, uint32_t file_id, int ms_level, SageMzml** out) {
-    return sage_hip_mzml_read_sn(path, file_id, ms_level, -1, out);
-}
-int sage_hip_mzml_read_sn(const char* path, uint32_t file_id, int ms_level, int sn_level, SageMzml** out) {
-    if (!path || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mzml_read: null argument");
-    auto h = std::make_unique<SageMzml>();
-    std::string err;
-    try {
-        if (!read_mzml(path, file_id, ms_level, sn_level, h->run, err)) return fail(SAGE_HIP_ERR_INVALID, err);
-    } catch (const std::exception& e) {
-        return fail(SAGE_HIP_ERR_INVALID, e.what());
-    }
-    *out = h.release();
-    return SAGE_HIP_OK;
-}
-// Inputs the reference refuses to SEARCH (it panics while processing them; the reader itself accepts them): profile-mode MS2
-// spectra (spectrum.rs:280-286 — Representation defaults to Profile, so a spectrum without the centroid term counts) and MS2
-// spectra without a precursor (scoring.rs:466-468).  Call before preprocessing / scoring a run.
-int sage_hip_mzml_check_searchable(const SageMzml* run) {
-    if (!run) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mzml_check_searchable: null argument");
-    const MzmlRun& r = run->run;
-    for (uint64_t i = 0; i < r.n(); ++i) {
-        if (r.ms_level[i] < 2) continue;
-        const char* id = r.ids.data() + r.id_off[i];
-        if (!r.centroid[i]) return fail(SAGE_HIP_ERR_INVALID, std::string("Scan ") + id + " contains profile data! Please convert to centroid");
-        if (!r.has_precursor[i]) return fail(SAGE_HIP_ERR_INVALID, std::string("missing MS1 precursor for ") + id);
-    }
-    return SAGE_HIP_OK;
-}
-int sage_hip_mzml_view(const SageMzml* run, SageRawBatch* out) {
-    if (!run || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mzml_view: null argument");
-    const MzmlRun& r = run->run;
-    out->n_spectra = (uint32_t)r.n();
-    out->peak_off = r.peak_off.data();
-    out->mz = r.mz.data();
-    out->intensities = r.intensities.data();
-    out->precursor_mz = r.precursor_mz.data();
-    out->precursor_charge = r.precursor_charge.data();
-    out->isolation_lo = r.isolation_lo.data();
-    out->isolation_hi = r.isolation_hi.data();
-    out->scan_start_time = r.scan_start_time.data();
-    out->inverse_ion_mobility = r.inverse_ion_mobility.data();
-    out->file_id = r.file_id.data();
-    return SAGE_HIP_OK;
-}
-const char* sage_hip_mzml_spectrum_id(const SageMzml* run, uint64_t i) {
-    if (!run || i >= run->run.n()) return nullptr;
-    return run->run.ids.data() + run->run.id_off[i];
-}
-float sage_hip_mzml_ion_injection_time(const SageMzml* run, uint64_t i) {
-    if (!run || i >= run->run.n()) return NAN;
-    return run->run.ion_injection_time[i];
-}
-const char* sage_hip_mzml_precursor_ref(const SageMzml* run, uint64_t i) {
-    if (!run || i >= run->run.n()) return nullptr;
-    return run->run.precursor_refs.data() + run->run.ref_off[i];
-}
-const float* sage_hip_mzml_mobility(const SageMzml* run) {
-    if (!run || run->run.has_mobility.empty()) return nullptr;
-    return run->run.mobility.data();
-}
-int sage_hip_mzml_has_mobility(const SageMzml* run, uint8_t* out) {
-    if (!run || (!out && run->run.n())) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mzml_has_mobility: null argument");
-    const MzmlRun& r = run->run;
-    for (uint64_t i = 0; i < r.n(); ++i) out[i] = r.has_mobility.empty() ? 0 : r.has_mobility[i];
-    return SAGE_HIP_OK;
-}
-void sage_hip_mzml_free(SageMzml* run) { delete run; }
-int sage_hip_mgf_read(const char* path, uint32_t file_id, SageMzml** out) {
-    if (!path || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mgf_read: null argument");
-    auto h = std::make_unique<SageMzml>();
-    std::string err;
-    try {
-        if (!read_mgf(path, file_id, h->run, err)) return fail(SAGE_HIP_ERR_INVALID, err);
-    } catch (const std::exception& e) {
-        return fail(SAGE_HIP_ERR_INVALID, e.what());
-    }
-    *out = h.release();
-    return SAGE_HIP_OK;
-}
-int sage_hip_mzml_isolation_kinds(const SageMzml* run, uint8_t* out) {
-    if (!run || (!out && run->run.n())) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mzml_isolation_kinds: null argument");
-    const MzmlRun& r = run->run;
-    for (uint64_t i = 0; i < r.n(); ++i) out[i] = r.iso_kind.empty() ? (uint8_t)SAGE_TOL_DA : r.iso_kind[i];
-    return SAGE_HIP_OK;
-}
-int sage_hip_mzml_charge_zero(const SageMzml* run, uint8_t* out) {
-    if (!run || (!out && run->run.n())) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_mzml_charge_zero: null argument");
-    const MzmlRun& r = run->run;
-    for (uint64_t i = 0; i < r.n(); ++i) out[i] = r.charge_zero.empty() ? 0 : r.charge_zero[i];
-    return SAGE_HIP_OK;
-}
-int sage_hip_parse_f32(const char* token, uint64_t len, float* out) {
-    if ((!token && len) || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_parse_f32: null argument");
-    return parse_f32_rust(token, token + len, *out) ? SAGE_HIP_OK : fail(SAGE_HIP_ERR_INVALID, "invalid float literal");
-}
-int sage_hip_write_results(const char* path, int format, const SageHostDb* db, const SageFeature* features, uint64_t n,
-                           const uint64_t* order, const uint64_t* psm_id, const char* const* filenames, uint32_t n_files,
-                           const char* const* spec_ids, const SagePostColumns* post) {
-    if (!path || !db || (n && (!features || !psm_id || !filenames || !spec_ids)))
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results: null argument");
-    if (format != SAGE_FORMAT_TSV && format != SAGE_FORMAT_PIN) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results: unknown format");
-    for (uint64_t r = 0; order && r < n; ++r)
-        if (order[r] >= n) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results: order entry out of range");
-    std::string err;
-    if (!write_results(path, format, db->db, features, n, order, psm_id, filenames, n_files, spec_ids, post, err))
-        return fail(SAGE_HIP_ERR_INVALID, err);
-    return SAGE_HIP_OK;
-}
-int sage_hip_write_results_grouped(const char* path, int format, const SageHostDb* db, const SageFeature* features, uint64_t n,
-                                   const uint64_t* order, const uint64_t* psm_id, const char* const* filenames, uint32_t n_files,
-                                   const char* const* spec_ids, const SagePostColumns* post, const SageGroupColumns* groups) {
-    if (!path || !db || (n && (!features || !psm_id || !filenames || !spec_ids)))
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results_grouped: null argument");
-    if (format != SAGE_FORMAT_TSV && format != SAGE_FORMAT_PIN)
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results_grouped: unknown format");
-    for (uint64_t r = 0; order && r < n; ++r)
-        if (order[r] >= n) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results_grouped: order entry out of range");
-    for (uint64_t s = 0; groups && groups->strings && s < groups->n_strings; ++s)
-        if (!groups->strings[s]) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_results_grouped: null string");
-    std::string err;
-    if (!write_results_grouped(path, format, db->db, features, n, order, psm_id, filenames, n_files, spec_ids, post, groups, err))
-        return fail(SAGE_HIP_ERR_INVALID, err);
-    return SAGE_HIP_OK;
-}
-uint64_t sage_hip_hostdb_protein_name(const SageHostDb* db, uint64_t id, char* out, uint64_t cap) {
-    if (!db || id >= db->db.protein_names.size()) return 0;
-    return copy_out(db->db.protein_names[id], out, cap);
-}
-int sage_hip_hostdb_feature_peptides(const SageHostDb* db, const uint32_t* peptide_idx, uint64_t n, uint64_t* seq_off, uint8_t* seq,
-                                     float* monoisotopic) {
-    if (!db || (n && !peptide_idx) || !seq_off) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_hostdb_feature_peptides: null argument");
-    const HostDb& d = db->db;
-    uint64_t off = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (peptide_idx[i] >= d.n_peptides()) return fail(SAGE_HIP_ERR_INVALID, "peptide index out of range");
-        const uint64_t p = peptide_idx[i], len = d.seq_off[p + 1] - d.seq_off[p];
-        seq_off[i] = off;
-        if (seq) std::memcpy(seq + off, d.seq.data() + d.seq_off[p], len);
-        if (monoisotopic) monoisotopic[i] = d.pep_mono[p];
-        off += len;
-    }
-    seq_off[n] = off;
-    return SAGE_HIP_OK;
-}
-int sage_hip_hostdb_isomer_groups(const SageHostDb* db, uint32_t* group_of, uint64_t* group_off, uint32_t* members, uint64_t* n_groups,
-                                  uint64_t* n_members) {
-    if (!db || !n_groups || !n_members) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_hostdb_isomer_groups: null argument");
-    std::lock_guard<std::mutex> lock(db->iso_mu);
-    if (!db->iso_made) {
-        db->db.isomer_groups(db->iso_of, db->iso_off, db->iso_members);
-        db->iso_made = true;
-    }
-    const std::vector<uint32_t>&of = db->iso_of, &mem = db->iso_members;
-    const std::vector<uint64_t>& off = db->iso_off;
-    const bool sizing = !group_off && !members;
-    if (!sizing) {
-        if (!group_off || (!members && !mem.empty())) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_hostdb_isomer_groups: group_off and members go together");
-        std::memcpy(group_off, off.data(), off.size() * sizeof(uint64_t));
-        if (!mem.empty()) std::memcpy(members, mem.data(), mem.size() * sizeof(uint32_t));
-    }
-    if (group_of && !of.empty()) std::memcpy(group_of, of.data(), of.size() * sizeof(uint32_t));
-    *n_groups = off.size() - 1;
-    *n_members = mem.size();
-    return SAGE_HIP_OK;
-}
-int sage_hip_hostdb_competition_keys(const SageHostDb* db, const uint32_t* peptide_idx, uint64_t n, uint32_t* peptide_key,
-                                     uint32_t* n_peptide_keys, uint32_t* protein_key, uint32_t* n_protein_keys) {
-    if (!db || (n && (!peptide_idx || !peptide_key || !protein_key)) || !n_peptide_keys || !n_protein_keys)
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_hostdb_competition_keys: null argument");
-    for (uint64_t i = 0; i < n; ++i)
-        if (peptide_idx[i] >= db->db.n_peptides()) return fail(SAGE_HIP_ERR_INVALID, "peptide index out of range");
-    db->db.competition_keys(peptide_idx, n, peptide_key, *n_peptide_keys, protein_key, *n_protein_keys);
-    return SAGE_HIP_OK;
-}
-uint64_t sage_hip_process_ms2(uint64_t take_top_n, int deisotope, float min_deisotope_mz, const float* mz,
-                              const float* intensity, uint64_t n, uint8_t precursor_charge, float* out_mass,
-                              float* out_intensity, float* out_tic) {
-    return process_ms2(take_top_n, deisotope != 0, min_deisotope_mz, mz, intensity, n, precursor_charge, out_mass,
-                       out_intensity, out_tic);
-}
-
-// ---------------------------------------------------------------------------------------------
-// device side
-// ---------------------------------------------------------------------------------------------
-int sage_hip_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-int sage_hip_db_create(const SageDbView* v, int device, SageDeviceDb** out) {
-    if (!v || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    if (v->n_peptides >= 0xFFFFFFFFull) return fail(SAGE_HIP_ERR_UNSUPPORTED, "more than 2^32-2 peptides");
-    if (v->n_ion_kinds > 8) return fail(SAGE_HIP_ERR_INVALID, "more than 8 ion kinds");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(SAGE_HIP_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(SAGE_HIP_ERR_INVALID, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
-    auto d = std::make_unique<SageDeviceDb>();
-    d->device = device;
-    const uint64_t np = v->n_peptides;
-    const uint32_t nk = v->n_ion_kinds;
-
-    // complete ion table for rescoring (IonSeries for every configured kind, ion_series.rs:36-85)
-    std::vector<uint64_t> ion_off(np + 1, 0);
-    std::vector<uint32_t> info(np);
-    uint32_t max_ions = 0, max_len = 0;
-    d->h_len.reserve(np);
-    for (uint64_t i = 0; i < np; i++) {
-        const uint64_t len = v->seq_off[i + 1] - v->seq_off[i];
-        // (the production rescoring kernel keeps a candidate's longest-run state in 10-bit fields — kernels.hip, run_matched_packed —;
-        // a database with longer peptides is scored by the general instances: scorer_init, DevScorer::long_runs)
-        if (len > 65535) return fail(SAGE_HIP_ERR_UNSUPPORTED, "peptide longer than 65535 residues");  // (pep_info: 16 bits)
-        max_len = std::max<uint32_t>(max_len, (uint32_t)len);
-        d->h_len.push_back((uint16_t)len);
-        const uint64_t cnt = (len ? len - 1 : 0) * nk;
-        ion_off[i + 1] = ion_off[i] + cnt;
-        max_ions = std::max<uint32_t>(max_ions, (uint32_t)cnt);
-        info[i] = (uint32_t)len | ((uint32_t)(v->decoy[i] ? 1 : 0) << 16) | ((uint32_t)v->missed_cleavages[i] << 24);
-    }
-    uint32_t tile_shift = TILE_SHIFT_MAX;
-    if (const char* e = getenv("SAGE_HIP_TILE_SHIFT")) tile_shift = (uint32_t)std::min((int)TILE_SHIFT_MAX, std::max(11, atoi(e)));
-    const uint64_t n_tiles = std::max<uint64_t>(1, (np + (1ull << tile_shift) - 1) >> tile_shift);
-    // 1/256 Da cells.  The scale is a power of two, so `m/z * scale` is exact in f32 and a fragment-tolerance window
-    // [lo, hi] maps to the cell range [floor(lo*scale), floor(hi*scale)] with no safety margin.
-    const float lut_scale = 256.0f;
-    uint32_t lut_stride = 0;
-    uint64_t nf = v->n_fragments;
-    std::vector<uint64_t> host_pm_off;  // fragment offset of every peptide (either branch)
-    d->h_pep_mono.assign(v->pep_mono, v->pep_mono + np);
-    if (!v->fragments) {
-        // ---- Parameters::build_from_peptides (database.rs:265-346) on the device: index_build.hip ----
-        std::vector<uint64_t> pm_off(np + 1, 0);
-        for (uint64_t i = 0; i < np; i++) {
-            const uint64_t len = v->seq_off[i + 1] - v->seq_off[i], lm1 = len ? len - 1 : 0;
-            pm_off[i + 1] = pm_off[i] + (lm1 > v->min_ion_index ? lm1 - v->min_ion_index : 0) * nk;  // database.rs:281-292
-        }
-        nf = pm_off[np];
-        if (nf >= 0xFFFFFFF0ull) return fail(SAGE_HIP_ERR_UNSUPPORTED, "more than 2^32-16 fragments");
-        std::vector<uint64_t> tile_off(n_tiles + 1, 0);
-        for (uint64_t t = 0; t < n_tiles; t++) tile_off[t + 1] = pm_off[std::min<uint64_t>(np, (t + 1) << tile_shift)];
-        const uint64_t total_res = np ? v->seq_off[np] : 0;
-        DevBuf<uint64_t> d_seq_off, d_tile_off;
-        DevBuf<uint8_t> d_seq, d_kinds;
-        DevBuf<float> d_mods, d_nterm;
-        HIP_TRY(d_seq_off.upload(v->seq_off, np + 1));
-        HIP_TRY(d_seq.upload(v->seq, total_res));
-        HIP_TRY(d_mods.upload(v->mods, total_res));
-        HIP_TRY(d_nterm.upload(v->nterm, np));
-        HIP_TRY(d_kinds.upload(v->ion_kinds, nk));
-        HIP_TRY(d_tile_off.upload(tile_off.data(), n_tiles + 1));
-        HIP_TRY(d->pep_mono.upload(v->pep_mono, np));
-        HIP_TRY(d->ion_off.upload(ion_off.data(), np + 1));
-        HIP_TRY(d->pm_off.upload(pm_off.data(), np + 1));
-        HIP_TRY(d->ions.alloc(ion_off[np] + 8));  // (padded: the rescoring kernel reads ions four at a time)
-        HIP_TRY(d->pm_frag.alloc(nf));
-        HIP_TRY(d->tm_frag.alloc(nf + 2));
-        hipError_t be = (hipError_t)generate_fragments_on_device(np, nk, d_kinds.p, d_seq_off.p, d_seq.p, d_mods.p, d_nterm.p, d->pep_mono.p,
-                                                                v->min_ion_index, d->ion_off.p, d->pm_off.p, d->ions.p, d->pm_frag.p, nullptr);
-        if (be == hipSuccess)
-            be = (hipError_t)build_tile_copy_on_device(d->pm_frag.p, nf, tile_shift, (uint32_t)n_tiles, d_tile_off.p, lut_scale,
-                                                       d->tm_frag.p, d->tm_lut, &lut_stride, nullptr);
-        if (be != hipSuccess) return fail(status_of(be), std::string("device index build: ") + hipGetErrorString(be));
-        host_pm_off.swap(pm_off);
-        HIP_TRY(d->pep_info.upload(info.data(), np));
-    } else {
-        // group IndexedDatabase.fragments by peptide (counting sort): tiles are runs of 2^tile_shift consecutive peptides
-        std::vector<uint64_t> pm_off(np + 1, 0);
-        for (uint64_t i = 0; i < nf; i++) {
-            if (v->fragments[i].peptide_index >= np) return fail(SAGE_HIP_ERR_INVALID, "fragment peptide_index out of range");
-            pm_off[v->fragments[i].peptide_index + 1]++;
-        }
-        for (uint64_t i = 0; i < np; i++) pm_off[i + 1] += pm_off[i];
-        std::vector<SageTheoretical> tm(nf + 2, SageTheoretical{0xFFFFFFFFu, 0.0f});
-        {
-            std::vector<uint64_t> cur(pm_off.begin(), pm_off.end() - 1);
-            for (uint64_t i = 0; i < nf; i++) tm[cur[v->fragments[i].peptide_index]++] = v->fragments[i];
-        }
-        HIP_TRY(d->pm_frag.upload(tm.data(), nf));  // (before the tiles are re-sorted by m/z below)
-        HIP_TRY(d->pm_off.upload(pm_off.data(), np + 1));
-        d->h_pep_mono.assign(v->pep_mono, v->pep_mono + np);
-        std::vector<float> ions(ion_off[np] + 8);  // (padded: the rescoring kernel reads ions four at a time)
-        parallel_for(np, 4096, [&](size_t ib, size_t ie, unsigned) {
-            for (size_t i = ib; i < ie; i++) {
-                const uint64_t len = v->seq_off[i + 1] - v->seq_off[i];
-                const uint64_t lm1 = len ? len - 1 : 0;
-                for (uint32_t k = 0; k < nk; k++)
-                    ion_series_flat(v->seq + v->seq_off[i], v->mods + v->seq_off[i], len, v->nterm[i], v->pep_mono[i],
-                                    v->ion_kinds[k], ions.data() + ion_off[i] + (uint64_t)k * lm1);
-            }
-        });
-        // tile-major copy for large precursor windows: tile = peptide_index >> tile_shift, (m/z, peptide) order inside a
-        // tile, and a per-tile position table tm_lut[t][c] = first position of tile t with m/z >= c / lut_scale.
-        if (nf >= 0xFFFFFFF0ull) return fail(SAGE_HIP_ERR_UNSUPPORTED, "more than 2^32-16 fragments");
-        std::vector<uint64_t> tile_off(n_tiles + 1, 0);
-        for (uint64_t t = 0; t < n_tiles; t++) tile_off[t + 1] = pm_off[std::min<uint64_t>(np, (t + 1) << tile_shift)];
-        parallel_for(n_tiles, 1, [&](size_t tb, size_t te, unsigned) {
-            for (size_t t = tb; t < te; t++)
-                std::sort(tm.begin() + tile_off[t], tm.begin() + tile_off[t + 1], [](const SageTheoretical& x, const SageTheoretical& y) {
-                    const int32_t kx = sagecore::order_key(x.fragment_mz), ky = sagecore::order_key(y.fragment_mz);
-                    return kx != ky ? kx < ky : x.peptide_index < y.peptide_index;
-                });
-        });
-        float max_mz = 0.0f;
-        for (uint64_t i = 0; i < nf; i++)
-            if (tm[i].fragment_mz > max_mz && std::isfinite(tm[i].fragment_mz)) max_mz = tm[i].fragment_mz;
-        lut_stride = (uint32_t)std::min<double>(std::ceil((double)max_mz * lut_scale) + 3.0, 64.0e6);
-        if ((double)n_tiles * lut_stride > 4.0e9) return fail(SAGE_HIP_ERR_UNSUPPORTED, "tile position table larger than 16 GB");
-        std::vector<uint32_t> lut((size_t)n_tiles * lut_stride, (uint32_t)tile_off[n_tiles]);
-        parallel_for(n_tiles, 1, [&](size_t tb, size_t te, unsigned) {
-            for (size_t t = tb; t < te; t++) {
-                uint64_t pos = tile_off[t];
-                const uint64_t tend = tile_off[t + 1];
-                auto cell = [&](uint32_t c) -> uint32_t& { return lut[tm_lut_index((uint32_t)t, c, lut_stride)]; };
-                for (uint32_t c = 0; c < lut_stride; c++) {
-                    const double edge = (double)c / (double)lut_scale;
-                    // NaN and m/z beyond the table (non-finite or > 250 kDa) compare false and stay in the last cell's run
-                    while (pos < tend && (double)tm[pos].fragment_mz < edge) pos++;
-                    cell(c) = (uint32_t)pos;
-                }
-                cell(0) = (uint32_t)tile_off[t];  // a window starting below cell 0 starts at the tile's first entry
-                cell(lut_stride - 1) = (uint32_t)tend;
-            }
-        });
-        HIP_TRY(d->tm_frag.upload(tm.data(), tm.size()));
-        HIP_TRY(d->tm_lut.upload(lut.data(), lut.size()));
-        HIP_TRY(d->pep_mono.upload(v->pep_mono, np));
-        HIP_TRY(d->ions.upload(ions.data(), ions.size()));
-        HIP_TRY(d->ion_off.upload(ion_off.data(), np + 1));
-        HIP_TRY(d->pep_info.upload(info.data(), np));
-        host_pm_off.swap(pm_off);
-    }
-    {
-        // small-tile copy for the narrow kernel (device_types.h: tm2_*), sorted on the device from the peptide-major list
-        // 2^11 peptides per small tile (round 4; 2^12 before): a +-10 ppm window of a human digest holds ~200 candidates, so of a
-        // tile's run for one fragment window only candidates / tile-size are inside the precursor window — the rest is fetched and
-        // thrown away, and prelim_kernel follows its line traffic.  C3, prelim ms per 500 000 spectra by shift 13 / 12 / 11 / 10 / 9 / 8:
-        // 2.26 / 1.86 / 1.68 / 1.67 / 1.83 / 2.20 (smaller tiles: more table rows, each reused by fewer spectra; 62 500-spectrum
-        // steps favour 11 over 10).  The table doubles to 1.5 GB for C3.
-        uint32_t tile2_shift = 11;
-        if (const char* e = getenv("SAGE_HIP_TILE2_SHIFT")) tile2_shift = (uint32_t)std::min(16, std::max(6, atoi(e)));
-        float lut2_scale = 32.0f;  // cells per Da (a power of two, like lut_scale)
-        if (const char* e = getenv("SAGE_HIP_LUT2_SCALE")) {  // (experiments: 8 .. 256, rounded down to a power of two)
-            const int v = std::min(256, std::max(8, atoi(e)));
-            lut2_scale = (float)(1 << (31 - __builtin_clz((unsigned)v)));
-        }
-        const uint64_t n_tiles2 = std::max<uint64_t>(1, (np + (1ull << tile2_shift) - 1) >> tile2_shift);
-        std::vector<uint64_t> tile2_off(n_tiles2 + 1, 0);
-        for (uint64_t t = 0; t < n_tiles2; t++) tile2_off[t + 1] = host_pm_off[std::min<uint64_t>(np, (t + 1) << tile2_shift)];
-        DevBuf<uint64_t> d_tile2_off;
-        HIP_TRY(d_tile2_off.upload(tile2_off.data(), n_tiles2 + 1));
-        HIP_TRY(d->tm2_frag.alloc(nf + 2));
-        DevBuf<uint32_t> lut2;  // the row-major table
-        uint32_t lut2_stride = 0;
-        const hipError_t be = (hipError_t)build_tile_copy_on_device(d->pm_frag.p, nf, tile2_shift, (uint32_t)n_tiles2, d_tile2_off.p,
-                                                                    lut2_scale, d->tm2_frag.p, lut2, &lut2_stride, nullptr);
-        if (be != hipSuccess) return fail(status_of(be), std::string("device index build: ") + hipGetErrorString(be));
-        // the table in succinct form (index_build.hip: build_succinct_lut_on_device; the row-major table is its input only —
-        // 1.5 GB for C3 that the narrow kernel no longer reads a line of per lookup)
-        uint32_t lut2_words = 0;
-        const hipError_t se = (hipError_t)build_succinct_lut_on_device(lut2.p, (uint32_t)n_tiles2, lut2_stride, d->tm2_l1, d->tm2_pos, &lut2_words, nullptr);
-        lut2.release();
-        if (se != hipSuccess) return fail(status_of(se), std::string("device index build (succinct table): ") + hipGetErrorString(se));
-        d->view.tm2_frag = d->tm2_frag.p;
-        d->view.tm2_l1 = d->tm2_l1.p;
-        d->view.tm2_pos = d->tm2_pos.p;
-        d->view.lut2_words = lut2_words;
-        d->view.tile2_shift = tile2_shift;
-        d->view.n_tiles2 = (uint32_t)n_tiles2;
-        d->view.lut2_stride = lut2_stride;
-        d->view.lut2_scale = lut2_scale;
-    }
-    d->max_ions = max_ions;
-    d->max_len = max_len;
-    HIP_TRY((hipError_t)ion_abs_range_on_device(d->ions.p, ion_off[np], &d->ion_lo_bits, &d->ion_hi_bits));
-    {  // the position table of the precursor-window search key
-        uint32_t bins = 0;
-        float inv_w = 0.0f;
-        // (SAGE_HIP_NO_PEP_LUT=1: without — every window through the full search; tests hold the two against each other)
-        const bool off = getenv("SAGE_HIP_NO_PEP_LUT") && getenv("SAGE_HIP_NO_PEP_LUT")[0] == '1';
-        const hipError_t be = off ? hipSuccess
-                                  : (hipError_t)build_peptide_mass_lut(d->pep_mono.p, (uint32_t)np, np ? d->h_pep_mono[np - 1] : 0.0f, d->pep_lut, &bins, &inv_w, nullptr);
-        if (be != hipSuccess) return fail(status_of(be), std::string("peptide-mass table: ") + hipGetErrorString(be));
-        d->view.pep_lut = d->pep_lut.p;
-        d->view.pep_lut_bins = bins;
-        d->view.pep_lut_inv_w = inv_w;
-    }
-    d->view.pep_mono = d->pep_mono.p;
-    d->view.np = (uint32_t)np;
-    d->view.pm_frag = d->pm_frag.p;
-    d->view.pm_off = d->pm_off.p;
-    d->view.ions = d->ions.p;
-    d->view.ion_off = d->ion_off.p;
-    d->view.pep_info = d->pep_info.p;
-    d->view.tm_frag = d->tm_frag.p;
-    d->view.tm_lut = d->tm_lut.p;
-    d->view.tile_shift = tile_shift;
-    d->view.n_tiles = (uint32_t)n_tiles;
-    d->view.lut_stride = lut_stride;
-    d->view.lut_scale = lut_scale;
-    d->view.nf = nf;
-    std::memset(d->view.ion_kinds, 0, sizeof d->view.ion_kinds);
-    for (uint32_t k = 0; k < nk; k++) d->view.ion_kinds[k] = v->ion_kinds[k];
-    d->view.n_kinds = nk;
-    if (!getenv("SAGE_HIP_KEEP_PM_FRAG")) {
-        d->pm_frag.release();
-        d->view.pm_frag = nullptr;
-    }
-    d->bytes = d->pep_mono.bytes() + d->pep_lut.bytes() + d->pm_frag.bytes() + d->pm_off.bytes() + d->ions.bytes() + d->ion_off.bytes() +
-               d->pep_info.bytes() + d->tm_frag.bytes() + d->tm_lut.bytes() + d->tm2_frag.bytes() + d->tm2_l1.bytes() + d->tm2_pos.bytes();
-    *out = d.release();
-    return SAGE_HIP_OK;
-}
-
-// the peptide-major fragment list for a batch that takes the stream variant of the preliminary kernels (SageDeviceDb::pm_frag)
-static int ensure_pm_frag(SageDeviceDb* db) {
-    std::lock_guard<std::mutex> lock(db->pm_mu);
-    if (db->view.pm_frag) return SAGE_HIP_OK;
-    HIP_TRY(db->pm_frag.alloc((size_t)db->view.nf + 2));
-    const hipError_t be = (hipError_t)rebuild_peptide_major_on_device(db->tm_frag.p, db->view.nf, db->pm_frag.p, nullptr);
-    if (be != hipSuccess) {
-        db->pm_frag.release();
-        return fail(status_of(be), std::string("peptide-major fragment list: ") + hipGetErrorString(be));
-    }
-    db->bytes += db->pm_frag.bytes();
-    db->view.pm_frag = db->pm_frag.p;
-    return SAGE_HIP_OK;
-}
-
-void sage_hip_db_destroy(SageDeviceDb* db) {
-    if (!db) return;
-    (void)hipSetDevice(db->device);
-    delete db;
-}
-uint64_t sage_hip_db_device_bytes(const SageDeviceDb* db) { return db ? db->bytes : 0; }
 
 // DevScorer::tol_mode (core.h: TolMode).  TOL_SYM: a symmetric ppm fragment tolerance — one division per Tolerance::bounds
 // (mass.rs:21-35).  TOL_FAST: the rescoring instance with the short divisions by 1e6 and by 3 (core.h: div_const_fast —
@@ -1665,14 +676,6 @@ int sage_hip_batch_download(SageDeviceBatch* b, uint64_t* peak_off, float* masse
     return SAGE_HIP_OK;
 }
 
-// TMT reporter ions (tmt.hip)
-int sage_hip_tmt(int device, const SageTmtInput* in, SageTmtOutput* out) {
-    if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_tmt: null argument");
-    if (sage_hip_device_count() <= 0) return fail(SAGE_HIP_ERR_NO_DEVICE, "sage_hip_tmt: no HIP device (there is no CPU fallback)");
-    std::string err;
-    const int rc = tmt_on_device(device, *in, *out, err);
-    return rc == SAGE_HIP_OK ? rc : fail(rc, err);
-}
 
 void sage_hip_batch_free(SageDeviceBatch* b) {
     if (!b) return;
@@ -1998,6 +1001,25 @@ retry_pass:
     return SAGE_HIP_OK;
 }
 
+// the kernel times of a retry pass: a2 preliminary, r2 rescoring (one figure, a2, where the large-window kernels did not run)
+static int retry_pass_times(const OutSet& o, float& a2, float& r2) {
+    if (o.wide_launched) {
+        HIP_TRY(hipEventElapsedTime(&a2, o.ev[2].e, o.ev[3].e));
+        HIP_TRY(hipEventElapsedTime(&r2, o.ev[3].e, o.ev[4].e));
+    } else {
+        HIP_TRY(hipEventElapsedTime(&a2, o.ev[2].e, o.ev[4].e));
+    }
+    return SAGE_HIP_OK;
+}
+// what a pass's overflow counters are refused with
+static int arena_exhausted(const SageScorer* s) {
+    return fail(SAGE_HIP_ERR_UNSUPPORTED, "large-window candidate arena exhausted (" + std::to_string(s->ws.arena.n >> 18) +
+                                              " MiB): score this batch in smaller pieces or raise SAGE_HIP_ARENA_MB");
+}
+static int list_capacity_exceeded(uint32_t spectra) {
+    return fail(SAGE_HIP_ERR_UNSUPPORTED, "preliminary candidate list capacity exceeded (" + std::to_string(spectra) + " spectra)");
+}
+
 // counters + timing of a finished batch (its comp_done / down_done event has completed); accumulates into s->timing.
 // *redo_wide: the batch was launched without the large-window kernels and turned out to need them — nothing is accumulated.
 static int collect(SageScorer* s, OutSet& o, bool* arena_overflow, bool* redo_wide = nullptr) {
@@ -2015,14 +1037,9 @@ static int collect(SageScorer* s, OutSet& o, bool* arena_overflow, bool* redo_wi
     if (!o.timed) goto counters;
     HIP_TRY(hipEventElapsedTime(&a, o.ev[0].e, o.ev[1].e));
     HIP_TRY(hipEventElapsedTime(&r, o.ev[1].e, o.ev[2].e));
-    if (o.two_pass && o.retry_deferred) {
-        // (the retry pass has not run: collect_retry adds its share if it does)
-    } else if (o.two_pass && o.wide_launched) {
-        HIP_TRY(hipEventElapsedTime(&a2, o.ev[2].e, o.ev[3].e));
-        HIP_TRY(hipEventElapsedTime(&r2, o.ev[3].e, o.ev[4].e));
-    } else if (o.two_pass) {
-        HIP_TRY(hipEventElapsedTime(&a2, o.ev[2].e, o.ev[4].e));
-    }
+    // (a deferred retry pass has not run: collect_retry adds its share if it does)
+    if (o.two_pass && !o.retry_deferred)
+        if (const int rc = retry_pass_times(o, a2, r2)) return rc;
 counters:
     SageTiming& t = s->timing;
     t.prelim_ms += a + a2;
@@ -2041,12 +1058,9 @@ counters:
             *arena_overflow = true;
             return SAGE_HIP_OK;
         }
-        return fail(SAGE_HIP_ERR_UNSUPPORTED, "large-window candidate arena exhausted (" + std::to_string(s->ws.arena.n >> 18) +
-                                                  " MiB): score this batch in smaller pieces or raise SAGE_HIP_ARENA_MB");
+        return arena_exhausted(s);
     }
-    if (c1[CTR_LIST_OVERFLOW] || c2[CTR_LIST_OVERFLOW])
-        return fail(SAGE_HIP_ERR_UNSUPPORTED, "preliminary candidate list capacity exceeded (" +
-                                                  std::to_string(c1[CTR_LIST_OVERFLOW] + c2[CTR_LIST_OVERFLOW]) + " spectra)");
+    if (c1[CTR_LIST_OVERFLOW] || c2[CTR_LIST_OVERFLOW]) return list_capacity_exceeded(c1[CTR_LIST_OVERFLOW] + c2[CTR_LIST_OVERFLOW]);
     return SAGE_HIP_OK;
 }
 
@@ -2058,12 +1072,7 @@ static int collect_retry(SageScorer* s, OutSet& o) {
     SageTiming& t = s->timing;
     if (o.timed) {
         float a2 = 0, r2 = 0;
-        if (o.wide_launched) {
-            HIP_TRY(hipEventElapsedTime(&a2, o.ev[2].e, o.ev[3].e));
-            HIP_TRY(hipEventElapsedTime(&r2, o.ev[3].e, o.ev[4].e));
-        } else {
-            HIP_TRY(hipEventElapsedTime(&a2, o.ev[2].e, o.ev[4].e));
-        }
+        if (const int rc = retry_pass_times(o, a2, r2)) return rc;
         t.prelim_ms += a2;
         t.rescore_ms += o.with_rescore ? r2 : 0.f;
         t.total_ms += a2 + (o.with_rescore ? r2 : 0.f);
@@ -2071,11 +1080,8 @@ static int collect_retry(SageScorer* s, OutSet& o) {
     }
     t.n_launches += 1 + (o.wide_launched ? 5 : 0);
     t.arena_entries = std::max(t.arena_entries, c2[CTR_ARENA_PTR]);
-    if (c2[CTR_ARENA_OVERFLOW])
-        return fail(SAGE_HIP_ERR_UNSUPPORTED, "large-window candidate arena exhausted (" + std::to_string(s->ws.arena.n >> 18) +
-                                                  " MiB): score this batch in smaller pieces or raise SAGE_HIP_ARENA_MB");
-    if (c2[CTR_LIST_OVERFLOW])
-        return fail(SAGE_HIP_ERR_UNSUPPORTED, "preliminary candidate list capacity exceeded (" + std::to_string(c2[CTR_LIST_OVERFLOW]) + " spectra)");
+    if (c2[CTR_ARENA_OVERFLOW]) return arena_exhausted(s);
+    if (c2[CTR_LIST_OVERFLOW]) return list_capacity_exceeded(c2[CTR_LIST_OVERFLOW]);
     return SAGE_HIP_OK;
 }
 
@@ -2484,349 +1490,6 @@ static int score_batch(SageScorer* s, const SageSpectrumBatch* b, const uint8_t*
     return SAGE_HIP_OK;
 }
 
-int sage_hip_annotate_resident(SageScorer* s, SageDeviceBatch* b, const SageFeature* features, const uint32_t* counts,
-                               SageFragments* out) {
-    if (!s || !b || !features || !counts || !out || !out->psm_off) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    if (b->device != s->db->device) return fail(SAGE_HIP_ERR_INVALID, "batch and scorer live on different devices");
-    std::lock_guard<std::mutex> lock(s->mu);
-    HIP_TRY(hipSetDevice(s->db->device));
-    const uint32_t n = b->n, rp = s->params.report_psms;
-    const size_t slots = (size_t)n * rp;
-    // a PSM's Fragments hold exactly matched_b + matched_y entries (scoring.rs:725-752) == Feature.matched_peaks
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++)
-        for (uint32_t r = 0; r < rp; r++) {
-            out->psm_off[(size_t)i * rp + r] = total;
-            if (r < counts[i]) {
-                if (features[(size_t)i * rp + r].peptide_idx >= s->db->view.np) return fail(SAGE_HIP_ERR_INVALID, "feature peptide_idx out of range");
-                total += features[(size_t)i * rp + r].matched_peaks;
-            }
-        }
-    out->psm_off[slots] = total;
-    if (total > out->capacity) return fail(SAGE_HIP_ERR_INVALID, "SageFragments.capacity is smaller than the sum of matched_peaks");
-    if (total && (!out->kinds || !out->charges || !out->fragment_ordinals || !out->intensities || !out->mz_calculated || !out->mz_experimental))
-        return fail(SAGE_HIP_ERR_INVALID, "missing SageFragments arrays");
-    if (n == 0 || total == 0) return SAGE_HIP_OK;
-    HIP_TRY(s->an_feats.reserve(slots));
-    HIP_TRY(s->an_counts.reserve(n));
-    HIP_TRY(s->an_off.reserve(slots + 1));
-    HIP_TRY(s->an_kinds.reserve(total));
-    HIP_TRY(s->an_charges.reserve(total));
-    HIP_TRY(s->an_ord.reserve(total));
-    HIP_TRY(s->an_int.reserve(total));
-    HIP_TRY(s->an_calc.reserve(total));
-    HIP_TRY(s->an_exp.reserve(total));
-    hipStream_t st = s->stream;
-    HIP_TRY(hipMemcpyAsync(s->an_feats.p, features, slots * sizeof(SageFeature), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->an_counts.p, counts, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->an_off.p, out->psm_off, (slots + 1) * 8, hipMemcpyHostToDevice, st));
-    DevFragments df{total, s->an_kinds.p, s->an_charges.p, s->an_ord.p, s->an_int.p, s->an_calc.p, s->an_exp.p};
-    launch_annotate(s->db->view, s->dev, b->view, s->an_feats.p, s->an_counts.p, s->an_off.p, df, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out->kinds, s->an_kinds.p, total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->charges, s->an_charges.p, total * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->fragment_ordinals, s->an_ord.p, total * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->intensities, s->an_int.p, total * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->mz_calculated, s->an_calc.p, total * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->mz_experimental, s->an_exp.p, total * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SAGE_HIP_OK;
-}
-
-}  // extern "C"
-// The argument rules of the calls that take candidate lists per PSM slot (sage_hip_score_candidates_resident,
-// sage_hip_localise_resident): everything their kernels index with is checked here — bad input is an error, never a device
-// fault.  total: the number of candidates (0: nothing to do); list: the spectra that have one.
-static int check_candidate_lists(const std::string& who, const SageScorer* s, const SageDeviceBatch* b, const SageFeature* features,
-                                 const uint32_t* counts, const uint64_t* cand_off, const uint32_t* cand_pep, const uint8_t* cand_charge,
-                                 bool out_given, uint64_t& total, std::vector<uint32_t>& list) {
-    const uint32_t n = b->n, rp = s->params.report_psms;
-    const size_t slots = (size_t)n * rp;
-    const uint64_t np = s->db->view.np;
-    if (cand_off[0] != 0) return fail(SAGE_HIP_ERR_INVALID, who + ": cand_off[0] must be 0");
-    for (size_t t = 0; t < slots; t++)
-        if (cand_off[t + 1] < cand_off[t]) return fail(SAGE_HIP_ERR_INVALID, who + ": cand_off decreases at slot " + std::to_string(t));
-    total = cand_off[slots];
-    if (total == 0) return SAGE_HIP_OK;
-    if (!features || !counts || !cand_pep || !out_given) return fail(SAGE_HIP_ERR_INVALID, who + ": null argument");
-    for (uint32_t i = 0; i < n; i++) {
-        const size_t s0 = (size_t)i * rp;
-        if (cand_off[s0 + rp] == cand_off[s0]) continue;
-        if (counts[i] > rp) return fail(SAGE_HIP_ERR_INVALID, who + ": counts[" + std::to_string(i) + "] exceeds report_psms");
-        for (uint32_t r = 0; r < rp; r++) {
-            if (r >= counts[i]) {
-                if (cand_off[s0 + r + 1] != cand_off[s0 + r])
-                    return fail(SAGE_HIP_ERR_INVALID, who + ": candidates on slot " + std::to_string(s0 + r) +
-                                                          ", which holds no PSM (rank >= counts[" + std::to_string(i) + "])");
-                continue;
-            }
-            const SageFeature& f = features[s0 + r];
-            if (f.peptide_idx >= np) return fail(SAGE_HIP_ERR_INVALID, who + ": feature peptide_idx out of range");
-            if (f.charge > 254) return fail(SAGE_HIP_ERR_INVALID, who + ": feature charge above 254");
-        }
-        list.push_back(i);
-    }
-    for (uint64_t c = 0; c < total; c++) {
-        if (cand_pep[c] >= np)
-            return fail(SAGE_HIP_ERR_INVALID, who + ": cand_pep[" + std::to_string(c) + "] is not a peptide of the database");
-        if (cand_charge && cand_charge[c] > 254)
-            return fail(SAGE_HIP_ERR_INVALID, who + ": cand_charge[" + std::to_string(c) + "] above 254");
-    }
-    return SAGE_HIP_OK;
-}
-extern "C" {
-int sage_hip_score_candidates_resident(SageScorer* s, SageDeviceBatch* b, const SageFeature* features, const uint32_t* counts,
-                                       const uint64_t* cand_off, const uint32_t* cand_pep, const uint8_t* cand_charge,
-                                       SageCandidateScore* out) {
-    if (!s || !b || !cand_off) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_score_candidates_resident: null argument");
-    if (b->device != s->db->device) return fail(SAGE_HIP_ERR_INVALID, "batch and scorer live on different devices");
-    std::lock_guard<std::mutex> lock(s->mu);
-    const uint32_t n = b->n, rp = s->params.report_psms;
-    const size_t slots = (size_t)n * rp;
-    s->cs_call_ms = s->cs_kernel_ms = 0.f;
-    uint64_t total = 0;
-    std::vector<uint32_t> list;
-    if (const int rc = check_candidate_lists("sage_hip_score_candidates_resident", s, b, features, counts, cand_off, cand_pep, cand_charge,
-                                             out != nullptr, total, list))
-        return rc;
-    if (total == 0) return SAGE_HIP_OK;
-    if (candidates_lds_bytes(b->view) > 160 * 1024)
-        return fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_score_candidates_resident: a spectrum of the batch has more peaks than a compute unit's LDS holds");
-    HIP_TRY(hipSetDevice(s->db->device));
-    HIP_TRY(s->cs_ev.create());
-    HIP_TRY(s->an_feats.reserve(slots));
-    HIP_TRY(s->an_counts.reserve(n));
-    HIP_TRY(s->cs_off.reserve(slots + 1));
-    HIP_TRY(s->cs_list.reserve(list.size()));
-    HIP_TRY(s->cs_pep.reserve(total));
-    if (cand_charge) HIP_TRY(s->cs_charge.reserve(total));
-    HIP_TRY(s->cs_out.reserve(total));
-    hipStream_t st = s->stream;
-    HIP_TRY(hipEventRecord(s->cs_ev[0], st));
-    HIP_TRY(hipMemcpyAsync(s->an_feats.p, features, slots * sizeof(SageFeature), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->an_counts.p, counts, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->cs_off.p, cand_off, (slots + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->cs_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->cs_pep.p, cand_pep, total * 4, hipMemcpyHostToDevice, st));
-    if (cand_charge) HIP_TRY(hipMemcpyAsync(s->cs_charge.p, cand_charge, total, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(s->cs_ev[1], st));
-    launch_candidates(s->db->view, s->dev, b->view, s->an_feats.p, s->an_counts.p, s->cs_list.p, (uint32_t)list.size(), s->cs_off.p,
-                      s->cs_pep.p, cand_charge ? s->cs_charge.p : nullptr, s->lnfact.p, (uint32_t)s->lnfact.n, s->cs_out.p, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s->cs_ev[2], st));
-    HIP_TRY(hipMemcpyAsync(out, s->cs_out.p, total * sizeof(SageCandidateScore), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(s->cs_ev[3], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&s->cs_call_ms, s->cs_ev[0], s->cs_ev[3]));
-    HIP_TRY(hipEventElapsedTime(&s->cs_kernel_ms, s->cs_ev[1], s->cs_ev[2]));
-    return SAGE_HIP_OK;
-}
-int sage_hip_last_candidates_timing(const SageScorer* s, float* call_ms, float* kernel_ms) {
-    if (!s || !call_ms || !kernel_ms) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_last_candidates_timing: null argument");
-    *call_ms = s->cs_call_ms;
-    *kernel_ms = s->cs_kernel_ms;
-    return SAGE_HIP_OK;
-}
-
-}  // extern "C"
-// ---- site localisation: the f64 arithmetic over the integer counts the device returns ----
-namespace {
-double peptide_score(DepthScores& ds, const uint16_t* n, uint32_t N) {
-    double sum = 0.0;
-    for (uint32_t d = 1; d <= 10; d++) sum += LOC_WEIGHT[d - 1] * ds.get(n[d - 1], N, d);
-    return sum / 7.0;
-}
-// d*: the depth with the largest a[d] - b[d] (signed), ties to the smallest; the Ascore there
-double ascore_of(DepthScores& ds, const uint16_t* a, const uint16_t* b, uint32_t Ns, uint8_t& depth) {
-    depth = 1;
-    if (Ns == 0) return 0.0;
-    int best = (int)a[0] - (int)b[0];
-    for (uint32_t d = 2; d <= 10; d++)
-        if ((int)a[d - 1] - (int)b[d - 1] > best) {
-            best = (int)a[d - 1] - (int)b[d - 1];
-            depth = (uint8_t)d;
-        }
-    return ds.get(a[depth - 1], Ns, depth) - ds.get(b[depth - 1], Ns, depth);
-}
-}  // namespace
-extern "C" {
-int sage_hip_ascore_from_counts(const uint16_t* n, uint32_t n_items, const uint16_t* a, const uint16_t* b, uint32_t n_site_items,
-                                double* depth_scores, double* peptide_score_out, uint8_t* depth, double* ascore) {
-    DepthScores ds;
-    if (n) {
-        for (int d = 0; d < 10; d++)
-            if (n[d] > n_items) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_ascore_from_counts: a count exceeds n_items");
-        if (depth_scores)
-            for (uint32_t d = 1; d <= 10; d++) depth_scores[d - 1] = ds.get(n[d - 1], n_items, d);
-        if (peptide_score_out) *peptide_score_out = peptide_score(ds, n, n_items);
-    } else if (depth_scores || peptide_score_out) {
-        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_ascore_from_counts: depth_scores / peptide_score need n");
-    }
-    if (a || b || depth || ascore) {
-        if (!a || !b || !depth || !ascore) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_ascore_from_counts: a, b, depth and ascore go together");
-        for (int d = 0; d < 10; d++)
-            if (a[d] > n_site_items || b[d] > n_site_items)
-                return fail(SAGE_HIP_ERR_INVALID, "sage_hip_ascore_from_counts: a count exceeds n_site_items");
-        *ascore = ascore_of(ds, a, b, n_site_items, *depth);
-    }
-    return SAGE_HIP_OK;
-}
-
-int sage_hip_localise_resident(SageScorer* s, SageDeviceBatch* b, const SageFeature* features, const uint32_t* counts,
-                               const uint64_t* cand_off, const uint32_t* cand_pep, const uint8_t* cand_charge,
-                               SageDepthCounts* per_candidate, SageLocalisation* per_slot) {
-    const std::string who = "sage_hip_localise_resident";
-    if (!s || !b || !cand_off) return fail(SAGE_HIP_ERR_INVALID, who + ": null argument");
-    if (b->device != s->db->device) return fail(SAGE_HIP_ERR_INVALID, "batch and scorer live on different devices");
-    std::lock_guard<std::mutex> lock(s->mu);
-    const uint32_t n = b->n, rp = s->params.report_psms;
-    const size_t slots = (size_t)n * rp;
-    s->lc_call_ms = s->lc_kernel_ms = 0.f;
-    uint64_t total = 0;
-    std::vector<uint32_t> list;
-    if (const int rc = check_candidate_lists(who, s, b, features, counts, cand_off, cand_pep, cand_charge, per_slot != nullptr, total, list))
-        return rc;
-    if (total == 0) return SAGE_HIP_OK;
-    // the pair's items are compared position by position: one residue count and one number of fragment charges per slot
-    const std::vector<uint16_t>& len = s->db->h_len;
-    const uint32_t nk = s->db->view.n_kinds;
-    for (uint32_t i : list)
-        for (uint32_t r = 0; r < counts[i]; r++) {
-            const size_t slot = (size_t)i * rp + r;
-            uint32_t len0 = 0, nfz0 = 0;
-            for (uint64_t c = cand_off[slot]; c < cand_off[slot + 1]; c++) {
-                const uint32_t z = cand_charge && cand_charge[c] ? cand_charge[c] : features[slot].charge;
-                const uint32_t nfz = sagecore::max_fragment_charge(s->dev.max_fragment_charge, z) - 1, l = len[cand_pep[c]];
-                if (c == cand_off[slot]) {
-                    len0 = l;
-                    nfz0 = nfz;
-                }
-                if (l != len0 || nfz != nfz0)
-                    return fail(SAGE_HIP_ERR_INVALID, who + ": the candidates of slot " + std::to_string(slot) +
-                                                          " differ in residue count or in fragment charges (cand_pep[" + std::to_string(c) + "])");
-                if ((uint64_t)nk * (l ? l - 1 : 0) * nfz > 65535)
-                    return fail(SAGE_HIP_ERR_UNSUPPORTED, who + ": cand_pep[" + std::to_string(c) + "] has more than 65535 items");
-            }
-        }
-    if (localise_lds_bytes(b->view) > 160 * 1024)
-        return fail(SAGE_HIP_ERR_UNSUPPORTED, who + ": a spectrum of the batch has more peaks than a compute unit's LDS holds");
-    std::vector<SageDepthCounts> own;
-    if (!per_candidate) {
-        own.resize(total);
-        per_candidate = own.data();
-    }
-    HIP_TRY(hipSetDevice(s->db->device));
-    HIP_TRY(s->lc_ev.create());
-    HIP_TRY(s->an_feats.reserve(slots));
-    HIP_TRY(s->an_counts.reserve(n));
-    HIP_TRY(s->cs_off.reserve(slots + 1));
-    HIP_TRY(s->cs_list.reserve(list.size()));
-    HIP_TRY(s->lc_list2.reserve(list.size()));
-    HIP_TRY(s->cs_pep.reserve(total));
-    if (cand_charge) HIP_TRY(s->cs_charge.reserve(total));
-    HIP_TRY(s->lc_counts.reserve(total));
-    HIP_TRY(s->lc_pair_a.reserve(slots));
-    HIP_TRY(s->lc_pair_b.reserve(slots));
-    HIP_TRY(s->lc_site.reserve(slots));
-    hipStream_t st = s->stream;
-    HIP_TRY(hipEventRecord(s->lc_ev[0], st));
-    HIP_TRY(hipMemcpyAsync(s->an_feats.p, features, slots * sizeof(SageFeature), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->an_counts.p, counts, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->cs_off.p, cand_off, (slots + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->cs_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->cs_pep.p, cand_pep, total * 4, hipMemcpyHostToDevice, st));
-    if (cand_charge) HIP_TRY(hipMemcpyAsync(s->cs_charge.p, cand_charge, total, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(s->lc_ev[1], st));
-    launch_depth_counts(s->db->view, s->dev, b->view, s->an_feats.p, s->an_counts.p, s->cs_list.p, (uint32_t)list.size(), s->cs_off.p,
-                        s->cs_pep.p, cand_charge ? s->cs_charge.p : nullptr, s->lc_counts.p, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s->lc_ev[2], st));
-    HIP_TRY(hipMemcpyAsync(per_candidate, s->lc_counts.p, total * sizeof(SageDepthCounts), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // best and second peptide score per slot: a plain f64 `>`, ties to the smaller position
-    std::vector<uint32_t> pair_a(slots, LOC_NONE), pair_b(slots, LOC_NONE), list2;
-    for (size_t slot = 0; slot < slots; slot++) {
-        SageLocalisation& o = per_slot[slot];
-        std::memset(&o, 0, sizeof o);
-        o.best = o.second = LOC_NONE;
-        o.ascore = std::nan("");
-    }
-    for (uint32_t i : list) {
-        bool pairs = false;
-        for (uint32_t r = 0; r < counts[i]; r++) {
-            const size_t slot = (size_t)i * rp + r;
-            const uint64_t c0 = cand_off[slot], c1 = cand_off[slot + 1];
-            if (c1 == c0) continue;
-            SageLocalisation& o = per_slot[slot];
-            double ps1 = 0.0, ps2 = 0.0;
-            uint32_t i1 = LOC_NONE, i2 = LOC_NONE;
-            for (uint64_t c = c0; c < c1; c++) {
-                const double ps = peptide_score(s->lc_scores, per_candidate[c].n, per_candidate[c].n_items);
-                const uint32_t at = (uint32_t)(c - c0);
-                if (i1 == LOC_NONE || ps > ps1) {
-                    ps2 = ps1;
-                    i2 = i1;
-                    ps1 = ps;
-                    i1 = at;
-                } else if (i2 == LOC_NONE || ps > ps2) {
-                    ps2 = ps;
-                    i2 = at;
-                }
-            }
-            o.best = i1;
-            o.best_score = ps1;
-            o.depth = 0;
-            if (i2 != LOC_NONE) {
-                o.second = i2;
-                o.second_score = ps2;
-                pair_a[slot] = i1;
-                pair_b[slot] = i2;
-                pairs = true;
-            }
-        }
-        if (pairs) list2.push_back(i);
-    }
-    std::vector<DevSiteCounts> site(slots);
-    if (!list2.empty()) {
-        HIP_TRY(hipMemcpyAsync(s->lc_list2.p, list2.data(), list2.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(s->lc_pair_a.p, pair_a.data(), slots * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(s->lc_pair_b.p, pair_b.data(), slots * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(s->lc_site.p, 0, slots * sizeof(DevSiteCounts), st));
-        HIP_TRY(hipEventRecord(s->lc_ev[3], st));
-        launch_site_counts(s->db->view, s->dev, b->view, s->an_feats.p, s->an_counts.p, s->lc_list2.p, (uint32_t)list2.size(), s->cs_off.p,
-                           s->cs_pep.p, cand_charge ? s->cs_charge.p : nullptr, s->lc_pair_a.p, s->lc_pair_b.p, s->lc_site.p, st);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(s->lc_ev[4], st));
-        HIP_TRY(hipMemcpyAsync(site.data(), s->lc_site.p, slots * sizeof(DevSiteCounts), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipEventRecord(s->lc_ev[5], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (size_t slot = 0; slot < slots; slot++) {
-        if (pair_b[slot] == LOC_NONE) continue;
-        SageLocalisation& o = per_slot[slot];
-        const DevSiteCounts& c = site[slot];
-        o.n_site_items = c.n_site_items;
-        for (int j = 0; j < 5; j++) {
-            o.a[2 * j] = (uint16_t)(c.a[j] & 0xFFFFu);
-            o.a[2 * j + 1] = (uint16_t)(c.a[j] >> 16);
-            o.b[2 * j] = (uint16_t)(c.b[j] & 0xFFFFu);
-            o.b[2 * j + 1] = (uint16_t)(c.b[j] >> 16);
-        }
-        o.ascore = ascore_of(s->lc_scores, o.a, o.b, o.n_site_items, o.depth);
-    }
-    HIP_TRY(hipEventElapsedTime(&s->lc_call_ms, s->lc_ev[0], s->lc_ev[5]));
-    float k1 = 0.f, k2 = 0.f;
-    HIP_TRY(hipEventElapsedTime(&k1, s->lc_ev[1], s->lc_ev[2]));
-    if (!list2.empty()) HIP_TRY(hipEventElapsedTime(&k2, s->lc_ev[3], s->lc_ev[4]));
-    s->lc_kernel_ms = k1 + k2;
-    return SAGE_HIP_OK;
-}
-int sage_hip_last_localise_timing(const SageScorer* s, float* call_ms, float* kernel_ms) {
-    if (!s || !call_ms || !kernel_ms) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_last_localise_timing: null argument");
-    *call_ms = s->lc_call_ms;
-    *kernel_ms = s->lc_kernel_ms;
-    return SAGE_HIP_OK;
-}
 
 int sage_hip_quick_score_resident(SageScorer* s, SageDeviceBatch* b, int prefilter_low_memory, uint8_t* keep) {
     if (!s || !b || !keep) return fail(SAGE_HIP_ERR_INVALID, "null argument");
@@ -2897,65 +1560,41 @@ int sage_hip_initial_hits(SageScorer* s, SageDeviceBatch* b, uint64_t* packed, u
 int sage_hip_debug_phase_cycles(SageScorer* s, unsigned long long* out32) {
     if (!s || !out32) return fail(SAGE_HIP_ERR_INVALID, "null argument");
     if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
-    std::vector<unsigned long long> all(4096 * 32);
+    std::vector<unsigned long long> all((size_t)DBG_BLOCKS * 32);
     HIP_TRY(hipMemcpy(all.data(), s->dbg.p, all.size() * 8, hipMemcpyDeviceToHost));
     for (int k = 0; k < 32; k++) out32[k] = 0;
-    for (size_t b = 0; b < 4096; b++)
+    for (size_t b = 0; b < DBG_BLOCKS; b++)
         for (int k = 0; k < 32; k++) out32[k] += all[b * 32 + k];
+    return SAGE_HIP_OK;
+}
+
+// the sums over all rows of words [first_word, first_word + count) of the block behind the phase cycles (device_types.h: DBG_PRUNE_WORDS)
+static int sum_dbg_words(SageScorer* s, uint32_t first_word, uint32_t count, unsigned long long* out) {
+    if (!s || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
+    if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
+    std::vector<unsigned long long> all((size_t)DBG_BLOCKS * DBG_PRUNE_WORDS);
+    HIP_TRY(hipMemcpy(all.data(), s->dbg.p + (size_t)DBG_BLOCKS * 32, all.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < count; k++) out[k] = 0;
+    for (size_t b = 0; b < DBG_BLOCKS; b++)
+        for (uint32_t k = 0; k < count; k++) out[k] += all[b * DBG_PRUNE_WORDS + first_word + k];
     return SAGE_HIP_OK;
 }
 
 // debugging aid: what the rescoring prune dropped so far — candidates, their (ion, charge) items, scoring rounds that left early,
 // rounds with a passing candidate beside pruned ones (kernels.hip: DBG_PRUNE_*)
-int sage_hip_debug_prune_counters(SageScorer* s, unsigned long long* out4) {
-    if (!s || !out4) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
-    std::vector<unsigned long long> all((size_t)DBG_BLOCKS * DBG_PRUNE_WORDS);
-    HIP_TRY(hipMemcpy(all.data(), s->dbg.p + (size_t)DBG_BLOCKS * 32, all.size() * 8, hipMemcpyDeviceToHost));
-    for (uint32_t k = 0; k < 4; k++) out4[k] = 0;
-    for (size_t b = 0; b < DBG_BLOCKS; b++)
-        for (uint32_t k = 0; k < 4; k++) out4[k] += all[b * DBG_PRUNE_WORDS + k];
-    return SAGE_HIP_OK;
-}
+int sage_hip_debug_prune_counters(SageScorer* s, unsigned long long* out4) { return sum_dbg_words(s, 0, 4, out4); }
 // debugging aid: the trips of the bitmap filter in front of the prune (kernels.hip: DBG_FILTER_*) — 64-ion chunks that took the
 // flat route, their trips of 8 ions, the trips of 4 ions the per-lane filter would have made of those chunks, and the trips of 4
 // ions of the chunks that took the per-lane route
-int sage_hip_debug_filter_counters(SageScorer* s, unsigned long long* out4) {
-    if (!s || !out4) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
-    std::vector<unsigned long long> all((size_t)DBG_BLOCKS * DBG_PRUNE_WORDS);
-    HIP_TRY(hipMemcpy(all.data(), s->dbg.p + (size_t)DBG_BLOCKS * 32, all.size() * 8, hipMemcpyDeviceToHost));
-    for (uint32_t k = 0; k < 4; k++) out4[k] = 0;
-    for (size_t b = 0; b < DBG_BLOCKS; b++)
-        for (uint32_t k = 0; k < 4; k++) out4[k] += all[b * DBG_PRUNE_WORDS + 4 + k];
-    return SAGE_HIP_OK;
-}
+int sage_hip_debug_filter_counters(SageScorer* s, unsigned long long* out4) { return sum_dbg_words(s, 4, 4, out4); }
 
 // debugging aid: the cooperative path behind the prune (kernels.hip: DBG_HEAVY_*) — chunks of heavy candidates the wavefront took
 // together, and the (ion, charge) matches it added up for them
-int sage_hip_debug_heavy_counters(SageScorer* s, unsigned long long* out2) {
-    if (!s || !out2) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
-    std::vector<unsigned long long> all((size_t)DBG_BLOCKS * DBG_PRUNE_WORDS);
-    HIP_TRY(hipMemcpy(all.data(), s->dbg.p + (size_t)DBG_BLOCKS * 32, all.size() * 8, hipMemcpyDeviceToHost));
-    out2[0] = out2[1] = 0;
-    for (size_t b = 0; b < DBG_BLOCKS; b++)
-        for (uint32_t k = 0; k < 2; k++) out2[k] += all[b * DBG_PRUNE_WORDS + 8 + k];
-    return SAGE_HIP_OK;
-}
+int sage_hip_debug_heavy_counters(SageScorer* s, unsigned long long* out2) { return sum_dbg_words(s, 8, 2, out2); }
 
 // debugging aid: which route the chunks of sage_hip_debug_heavy_counters took (kernels.hip: DBG_HEAVY_ONE_TRIP / _PER_CHARGE) — all
 // items in one lookup trip with the sums from LDS, or a trip per fragment charge with the sums by readlane
-int sage_hip_debug_heavy_routes(SageScorer* s, unsigned long long* out2) {
-    if (!s || !out2) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    if (!s->dbg.p) return fail(SAGE_HIP_ERR_INVALID, "set SAGE_HIP_PHASE_CLOCKS=1 before creating the scorer");
-    std::vector<unsigned long long> all((size_t)DBG_BLOCKS * DBG_PRUNE_WORDS);
-    HIP_TRY(hipMemcpy(all.data(), s->dbg.p + (size_t)DBG_BLOCKS * 32, all.size() * 8, hipMemcpyDeviceToHost));
-    out2[0] = out2[1] = 0;
-    for (size_t b = 0; b < DBG_BLOCKS; b++)
-        for (uint32_t k = 0; k < 2; k++) out2[k] += all[b * DBG_PRUNE_WORDS + 10 + k];
-    return SAGE_HIP_OK;
-}
+int sage_hip_debug_heavy_routes(SageScorer* s, unsigned long long* out2) { return sum_dbg_words(s, 10, 2, out2); }
 
 // debugging aid: 1 if the last first pass this scorer enqueued handed its preliminary lists over in rows by schedule position
 // (DevWork::hand), 0 if in the arrays by spectrum
@@ -2978,61 +1617,6 @@ int sage_hip_debug_rescore_instance(SageScorer* s, uint32_t* out) {
     return SAGE_HIP_OK;
 }
 
-// debugging aid: the scalars of the device database's layout (what DevDbView and SageDeviceDb hold beside the table pointers)
-int sage_hip_debug_db_layout(SageDeviceDb* db, SageDbLayout* out) {
-    if (!db || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    const DevDbView& v = db->view;
-    std::memset(out, 0, sizeof *out);
-    out->np = v.np;
-    out->nf = v.nf;
-    out->tile_shift = v.tile_shift;
-    out->n_tiles = v.n_tiles;
-    out->lut_stride = v.lut_stride;
-    out->lut_scale = v.lut_scale;
-    out->tile2_shift = v.tile2_shift;
-    out->n_tiles2 = v.n_tiles2;
-    out->lut2_stride = v.lut2_stride;
-    out->lut2_scale = v.lut2_scale;
-    out->lut2_words = v.lut2_words;
-    out->pep_lut_bins = v.pep_lut_bins;
-    out->pep_lut_inv_w = v.pep_lut_inv_w;
-    out->ion_lo_bits = db->ion_lo_bits;
-    out->ion_hi_bits = db->ion_hi_bits;
-    out->max_ions = db->max_ions;
-    out->max_len = db->max_len;
-    out->tm2_pos_len = db->tm2_pos.n;
-    return SAGE_HIP_OK;
-}
-
-// debugging aid: one table of the device database, as it lies in HBM (include/sage_hip.h: SAGE_DB_*)
-int sage_hip_debug_db_table(SageDeviceDb* db, int table, void* out, uint64_t cap_bytes, uint64_t* out_bytes) {
-    if (!db || !out_bytes) return fail(SAGE_HIP_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(db->device));
-    if (table == SAGE_DB_PM_FRAG)
-        if (int rc = ensure_pm_frag(db)) return rc;
-    const void* src = nullptr;
-    uint64_t bytes = 0;
-    switch (table) {
-        case SAGE_DB_IONS: src = db->ions.p; bytes = db->ions.bytes() - 8 * sizeof(float); break;  // (padded: sage_hip_db_create)
-        case SAGE_DB_ION_OFF: src = db->ion_off.p; bytes = db->ion_off.bytes(); break;
-        case SAGE_DB_PM_OFF: src = db->pm_off.p; bytes = db->pm_off.bytes(); break;
-        case SAGE_DB_PEP_INFO: src = db->pep_info.p; bytes = db->pep_info.bytes(); break;
-        case SAGE_DB_PEP_MONO: src = db->pep_mono.p; bytes = db->pep_mono.bytes(); break;
-        case SAGE_DB_PEP_LUT: src = db->pep_lut.p; bytes = db->pep_lut.bytes(); break;  // (never allocated: no table)
-        case SAGE_DB_PM_FRAG: src = db->pm_frag.p; bytes = db->pm_frag.bytes(); break;
-        case SAGE_DB_TM_FRAG: src = db->tm_frag.p; bytes = db->tm_frag.bytes(); break;
-        case SAGE_DB_TM2_FRAG: src = db->tm2_frag.p; bytes = db->tm2_frag.bytes(); break;
-        case SAGE_DB_TM_LUT: src = db->tm_lut.p; bytes = db->tm_lut.bytes(); break;
-        case SAGE_DB_TM2_L1: src = db->tm2_l1.p; bytes = db->tm2_l1.bytes(); break;
-        case SAGE_DB_TM2_POS: src = db->tm2_pos.p; bytes = db->tm2_pos.bytes(); break;
-        default: return fail(SAGE_HIP_ERR_INVALID, "sage_hip_debug_db_table: unknown table id");
-    }
-    *out_bytes = bytes;
-    if (!out || !bytes) return SAGE_HIP_OK;
-    if (cap_bytes < bytes) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_debug_db_table: buffer smaller than the table");
-    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
-    return SAGE_HIP_OK;
-}
 
 int sage_hip_host_alloc(uint64_t bytes, void** out) {
     if (!out) return fail(SAGE_HIP_ERR_INVALID, "null argument");

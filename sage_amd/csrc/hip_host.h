@@ -93,7 +93,7 @@ struct Ctx {
 
 // HIP_TRY(expr): when the HIP call fails, return HIP_FAILED(error, "expr") from the enclosing function.  By default that notes the
 // failure in the Ctx named cx and returns false.  A file whose functions return something else defines HIP_FAILED before it
-// includes this header: capi.hip (the status, with the thread's error string set), index_build.hip (the hipError_t itself).
+// includes this header: capi_state.h (the status, with the thread's error string set), index_build.hip (the hipError_t itself).
 #ifndef HIP_FAILED
 #define HIP_FAILED(e, what) cx.check((e), (what))
 #endif

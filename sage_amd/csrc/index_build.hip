@@ -352,7 +352,7 @@ int build_succinct_lut_on_device(const uint32_t* d_lut, uint32_t n_tiles, uint32
         HIP_TRY(hipMemcpyAsync(&last_rank, ranks.p + (n - 1), 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipMemcpyAsync(&last_count, counts.p + (n - 1), 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(pos.alloc((uint64_t)last_rank + last_count));  // (>= 1, <= entries + tiles < 2^32: capi.hip refuses more fragments)
+        HIP_TRY(pos.alloc((uint64_t)last_rank + last_count));  // (>= 1, <= entries + tiles < 2^32: capi_db.hip refuses more fragments)
         hipLaunchKernelGGL(lut_fill_kernel, grid, dim3(256), 0, stream, d_lut, n_tiles, lut_stride, words, ranks.p, l1.p, pos.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));

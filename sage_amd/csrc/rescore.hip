@@ -2056,7 +2056,7 @@ bool protein_groups_impl(Ctx& cx, const HostDb& db, const SageGroupInput& in, Sa
 
 }  // namespace
 
-// entry point used by capi.hip; returns a SAGE_HIP_* status, message in `err`
+// entry point used by capi_host.cpp; returns a SAGE_HIP_* status, message in `err`
 int rescore_on_device(int device, const SageRescoreInput& in, SageRescoreOutput& out, std::string& err) {
     Ctx cx;
     if (hipSetDevice(device) != hipSuccess) {

@@ -1,5 +1,5 @@
 """A plain numpy restatement of the fragment index that sage_hip_db_create derives in HBM, written from the
-reference's source lines and from the layouts' definitions — not from index_build.hip or capi.hip:
+reference's source lines and from the layouts' definitions — not from index_build.hip or capi_db.hip:
 
 * the ion table: IonSeries::new / next (ion_series.rs:36-85) of every peptide and configured kind, an f32 running sum in sequence
   order (np.cumsum over a 1-D f32 array accumulates sequentially), residue masses of mass.rs:64-76;

@@ -1,4 +1,4 @@
-"""Every table sage_hip_db_create derives in HBM (index_build.hip's kernels, capi.hip's host branch), read back through
+"""Every table sage_hip_db_create derives in HBM (index_build.hip's kernels, capi_db.hip's host branch), read back through
 sage_hip_debug_db_layout / sage_hip_debug_db_table and compared entry for entry, cell for cell and bit for bit with the numpy
 restatement of tests/index_reference.py — which tests/test_index_reference_cpu.py anchors to the oracle.  No tolerance anywhere:
 every step is the reference's f32 arithmetic or integer work.

@@ -118,7 +118,7 @@ def test_narrow_kernel_variants(small_world, monkeypatch, variant):
 @pytest.mark.parametrize("keep_pm", [None, "1"])
 def test_stream_variant_with_the_kept_and_the_rebuilt_fragment_list(small_world, monkeypatch, keep_pm):
     """The stream variant walks the peptide-major fragment list.  By default the index build releases it and the first batch
-    of the stream variant makes it again from a tile copy (capi.hip: ensure_pm_frag); SAGE_HIP_KEEP_PM_FRAG=1 keeps the one
+    of the stream variant makes it again from a tile copy (capi_db.hip: ensure_pm_frag); SAGE_HIP_KEEP_PM_FRAG=1 keeps the one
     the index was built from.  Both orders give the oracle's records (a new DeviceDatabase: the switch is read when the
     database is created)."""
     if keep_pm:

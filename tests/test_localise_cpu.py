@@ -109,7 +109,7 @@ def test_host_arithmetic_in_closed_form():
 def test_host_arithmetic_equals_the_restatement_on_random_counts():
     """1e-12 relative to max(|S|, 1), the tolerance tests/test_gpu_isomers.py grants an f64.  A small S is a difference of
     log-gammas of up to 3 200 whose last bit weighs 4.5e-13, so two log-gamma functions that differ in their last bits do not
-    hold it: the library evaluates the Lanczos approximation math.lgamma evaluates (capi.hip: lgamma_lanczos), not the C
+    hold it: the library evaluates the Lanczos approximation math.lgamma evaluates (localise_math.h: lgamma_lanczos), not the C
     library's lgamma, and log and exp are the C library's on both sides."""
     rng = np.random.default_rng(11)
     cases = [(np.zeros(10, np.uint16), 0), (np.zeros(10, np.uint16), 600), (np.full(10, 600, np.uint16), 600),
@@ -147,6 +147,18 @@ def test_ascore_and_depth_equal_the_restatement_on_random_counts():
         depth, score = LR.ascore([int(x) for x in a], [int(x) for x in b], Ns)
         assert got["depth"] == depth and LR.close(got["ascore"], score), (a, b, Ns, got, depth, score)
     assert ascore_from_counts(a=[0] * 10, b=[0] * 10, n_site_items=0) == dict(depth=1, ascore=0.0)
+
+
+def test_host_arithmetic_stand_alone_under_sanitizers(tmp_path):
+    """localise_math.h as a program of its own (tests/hostemu/localise_math_emu.cpp), with AddressSanitizer and
+    UndefinedBehaviorSanitizer: the depth-score cache starts again past 2^23 values and hands out the same bits before, after and
+    from a fresh cache; ascore_of without site-determining items and with a tie between depths"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "localise_math_emu_san")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(here, "hostemu", "localise_math_emu.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "localise_math_emu ok" in r.stdout, r.stdout + r.stderr
 
 
 def test_counts_above_their_total_are_refused():
