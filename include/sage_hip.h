@@ -848,6 +848,58 @@ int sage_hip_ascore_from_counts(const uint16_t* n, uint32_t n_items, const uint1
  * back and the host's pair selection between the two kernels included) and the two kernels alone. */
 int sage_hip_last_localise_timing(const SageScorer* scorer, float* call_ms, float* kernel_ms);
 
+/* ---- protein-level label-free quantification (MaxLFQ: Cox et al. 2014; the roll-up `iq::fast_MaxLFQ` performs on lfq.tsv).  An
+ * addition over the reference, additive to ABI 6; the contract is DESIGN.md 7g, stated again in tests/protein_lfq_reference.py.
+ * All arithmetic is IEEE f64 without FMA.  For one protein, its rows r in ascending row index, files j, k:
+ *   1. L[r][j] = the correctly rounded ln(area) (crlog.h) where area > 0 && area < +inf, else missing.
+ *   2. for j < k: d = L[r][j] - L[r][k] over the rows present in both, c_jk their number; the pair is valid when
+ *      c_jk >= max(min_ratio_count, 1); m_jk = the median (odd count: the middle element; even: (lo + hi) * 0.5).
+ *   3. components of the graph of valid pairs over the files; a component's label is its smallest file index.
+ *   4. normal equations of min sum_valid (m_jk - (x_j - x_k))^2: A[j][j] += 1, A[k][k] += 1, A[j][k] -= 1, A[k][j] -= 1,
+ *      b[j] = sum_k +-m from +0.0 in ascending k (+m_jk for j < k, -m_kj for k < j); every file that is its component's label is
+ *      grounded: row and column zeroed, diagonal 1, b 0.
+ *   5. forward elimination without pivoting, pivot row p ascending, rows i > p ascending; a row with A[i][p] == 0.0 is left
+ *      untouched, else f = A[i][p] / A[p][p], A[i][c] -= f * A[p][c] for c = p .. n_files - 1 ascending, b[i] -= f * b[p].  Back
+ *      substitution, i descending: s = b[i]; s -= A[i][c] * x[c] for c ascending from i + 1; x[i] = s / A[i][i].  A zero or
+ *      non-finite pivot: SAGE_HIP_ERR_INTERNAL.
+ *   6. col[j] = sum_r L[r][j] from +0.0 in ascending r, cnt[j] the number of present rows; per component over its members in
+ *      ascending j: T = sum col, N = sum cnt, S = sum x; N == 0: every member NaN; else x[j] + (T / N - S / |component|).
+ * log_abundance: natural log, NaN = not quantified; component: the label, 0xFFFFFFFF where not quantified; n_rows_used: the rows
+ * whose protein_of_row names the protein; n_components: among quantified files; intensity = det_exp(log_abundance) (detmath.h),
+ * 0.0 where not quantified.  pair_median / pair_count (each may be NULL): [n_proteins * n_files (n_files - 1) / 2], (j, k) in
+ * lexicographic order; the median is NaN where the pair is not valid.
+ * protein_of_row: ids 0 .. n_proteins - 1 in any row order, 0xFFFFFFFF = the row is ignored; another id >= n_proteins or a NULL
+ * array: SAGE_HIP_ERR_INVALID.  More than 65 535 files: SAGE_HIP_ERR_UNSUPPORTED.  n_proteins == 0: SAGE_HIP_OK, nothing
+ * written; n_rows == 0 or n_files == 0: SAGE_HIP_OK without a launch, every protein not quantified.
+ * Proteins go through the device in batches whose tables stay below SAGE_HIP_PLFQ_WORKSPACE_MB; n_batches counts
+ * them.  log_ms: upload, grouping and logarithms; median_ms / solve_ms: the two kernels summed over the batches; device_ms: all
+ * of it, copies back included (HIP events). */
+typedef struct SageProteinLfqInput {
+    uint64_t n_rows;
+    uint32_t n_files, n_proteins, min_ratio_count;
+    const double* areas;              /* [n_rows * n_files] */
+    const uint32_t* protein_of_row;   /* [n_rows] */
+} SageProteinLfqInput;
+
+typedef struct SageProteinLfqOutput {
+    double* log_abundance;            /* [n_proteins * n_files] */
+    double* intensity;
+    uint32_t* component;
+    uint32_t* n_rows_used;            /* [n_proteins] */
+    uint32_t* n_components;
+    double* pair_median;              /* optional */
+    uint32_t* pair_count;
+    float log_ms, median_ms, solve_ms, device_ms;
+    uint32_t n_batches;
+} SageProteinLfqOutput;
+
+int sage_hip_protein_lfq(int device, const SageProteinLfqInput* in, SageProteinLfqOutput* out);
+
+/* protein_lfq.tsv: proteins, n_precursors, n_components, then one intensity per file (ryu f64; 0.0 where not quantified), one row
+ * per entry of `rows` (protein ids of `result`, in the order given); protein_names[id] is written as the `proteins` field. */
+int sage_hip_write_protein_lfq(const char* path, const char* const* protein_names, uint32_t n_proteins, const uint32_t* rows,
+                               uint32_t n_out, const SageProteinLfqOutput* result, const char* const* filenames, uint32_t n_files);
+
 const char* sage_hip_last_error(void);
 int sage_hip_abi_version(void);
 

@@ -252,6 +252,18 @@ class SageTmtOutput(C.Structure):
                 ("extract_ms", C.c_float), ("device_ms", C.c_float)]
 
 
+class SageProteinLfqInput(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_files", C.c_uint32), ("n_proteins", C.c_uint32), ("min_ratio_count", C.c_uint32),
+                ("areas", C.POINTER(C.c_double)), ("protein_of_row", c_u32_p)]
+
+
+class SageProteinLfqOutput(C.Structure):
+    _fields_ = [("log_abundance", C.POINTER(C.c_double)), ("intensity", C.POINTER(C.c_double)), ("component", c_u32_p),
+                ("n_rows_used", c_u32_p), ("n_components", c_u32_p), ("pair_median", C.POINTER(C.c_double)), ("pair_count", c_u32_p),
+                ("log_ms", C.c_float), ("median_ms", C.c_float), ("solve_ms", C.c_float), ("device_ms", C.c_float),
+                ("n_batches", C.c_uint32)]
+
+
 class SagePostColumns(C.Structure):
     _fields_ = [(k, c_float_p) for k in ("discriminant_score", "posterior_error", "spectrum_q", "peptide_q", "protein_q",
                                          "aligned_rt", "predicted_rt", "delta_rt_model", "predicted_ims", "delta_ims_model")]
@@ -410,6 +422,9 @@ def load():
         "sage_hip_localise_resident": (C.c_int, [vp, vp, vp, c_u32_p, c_u64_p, c_u32_p, c_u8_p, vp, vp]),
         "sage_hip_ascore_from_counts": (C.c_int, [vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp]),
         "sage_hip_last_localise_timing": (C.c_int, [vp, c_float_p, c_float_p]),
+        "sage_hip_protein_lfq": (C.c_int, [C.c_int, C.POINTER(SageProteinLfqInput), C.POINTER(SageProteinLfqOutput)]),
+        "sage_hip_write_protein_lfq": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, c_u32_p, C.c_uint32,
+                                                 C.POINTER(SageProteinLfqOutput), C.POINTER(C.c_char_p), C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
@@ -437,6 +452,7 @@ EXPORTED_SYMBOLS = [
     "sage_hip_group_graph_view", "sage_hip_group_graph_free", "sage_hip_hostdb_protein_name", "sage_hip_write_results_grouped",
     "sage_hip_hostdb_isomer_groups", "sage_hip_score_candidates_resident", "sage_hip_last_candidates_timing",
     "sage_hip_localise_resident", "sage_hip_ascore_from_counts", "sage_hip_last_localise_timing",
+    "sage_hip_protein_lfq", "sage_hip_write_protein_lfq",
 ]
 
 

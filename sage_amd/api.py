@@ -1251,6 +1251,56 @@ def lfq_im(features, order, aligned_rt, peptide_q, alignments, ms1, carbon, sulf
                ion_mobility=True)
 
 
+@dataclass
+class ProteinLfqResult:
+    """Outputs of sage_hip_protein_lfq, one row per protein id.  log_abundance (natural log, NaN = not quantified),
+    intensity (0.0 = not quantified) and component (0xFFFFFFFF = not quantified): [n_proteins, n_files]; pair_median / pair_count
+    (debug=True, else None): [n_proteins, n_files (n_files - 1) / 2], (j, k) in lexicographic order."""
+    log_abundance: np.ndarray
+    intensity: np.ndarray
+    component: np.ndarray
+    n_rows_used: np.ndarray
+    n_components: np.ndarray
+    pair_median: Optional[np.ndarray]
+    pair_count: Optional[np.ndarray]
+    n_batches: int
+    stage_ms: dict
+
+    def to_c(self, keep: list) -> "L.SageProteinLfqOutput":
+        arr = lambda a, t: (keep.append(a), L.as_ptr(a, t))[1]
+        return L.SageProteinLfqOutput(arr(self.log_abundance, C.c_double), arr(self.intensity, C.c_double),
+                                      arr(self.component, C.c_uint32), arr(self.n_rows_used, C.c_uint32),
+                                      arr(self.n_components, C.c_uint32),
+                                      None if self.pair_median is None else arr(self.pair_median, C.c_double),
+                                      None if self.pair_count is None else arr(self.pair_count, C.c_uint32))
+
+
+def protein_lfq(areas, protein_of_row, n_proteins: int, min_ratio_count: int = 1, device: int = 0,
+                debug: bool = False) -> ProteinLfqResult:
+    """MaxLFQ over precursor rows (sage_hip_protein_lfq).  areas: [n_rows, n_files] f64 (a value that is not a
+    positive finite number is missing); protein_of_row: [n_rows] dense ids below n_proteins, 0xFFFFFFFF = the row is ignored.
+    debug: also the tables of pair medians and shared-row counts."""
+    a = np.ascontiguousarray(areas, dtype=np.float64)
+    assert a.ndim == 2
+    n_rows, n_files = a.shape
+    por = np.ascontiguousarray(protein_of_row, dtype=np.uint32).reshape(-1)
+    assert len(por) == n_rows
+    n_proteins = int(n_proteins)
+    pairs = n_files * (n_files - 1) // 2
+    r = ProteinLfqResult(np.full((n_proteins, n_files), np.nan), np.zeros((n_proteins, n_files)),
+                         np.full((n_proteins, n_files), 0xFFFFFFFF, np.uint32), np.zeros(n_proteins, np.uint32),
+                         np.zeros(n_proteins, np.uint32), np.full((n_proteins, pairs), np.nan) if debug else None,
+                         np.zeros((n_proteins, pairs), np.uint32) if debug else None, 0, {})
+    cin = L.SageProteinLfqInput(n_rows, n_files, n_proteins, int(min_ratio_count), L.as_ptr(a, C.c_double), L.as_ptr(por, C.c_uint32))
+    keep = []
+    cout = r.to_c(keep)
+    L.check(L.load().sage_hip_protein_lfq(device, C.byref(cin), C.byref(cout)))
+    r.n_batches = int(cout.n_batches)
+    r.stage_ms = {"log_ms": float(cout.log_ms), "median_ms": float(cout.median_ms), "solve_ms": float(cout.solve_ms),
+                  "device_ms": float(cout.device_ms)}
+    return r
+
+
 # ---- TMT reporter-ion quantification (sage_hip_tmt) ----------------------------------------------------------------------------
 # tmt.rs:216-231, as f32
 TMT6PLEX = np.array([126.127726, 127.124761, 128.134436, 129.131471, 130.141145, 131.138180], dtype=np.float32)

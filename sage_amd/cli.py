@@ -7,7 +7,8 @@ crates/sage-cli/src/input.rs (Input -> Search, :298-385; `database` = sage-core 
 flow of runner.rs (read mzML -> SpectrumProcessor::process -> keep MS2 with >= min_peaks peaks -> Scorer::score,
 :311-325, :398-461) and the `results.sage.tsv` / `matched_fragments.sage.tsv` writers (:687-935).  Everything downstream
 of Scorer::score is limited to the LDA rescoring, q-values and picked peptide / protein FDR (runner.rs:536-541, on the
-device: rescore.hip), label-free MS1 quantification when `quant.lfq` is true (runner.rs:562-575, lfq.hip: `lfq.tsv`),
+device: rescore.hip), label-free MS1 quantification when `quant.lfq` is true (runner.rs:562-575, lfq.hip: `lfq.tsv`) and its
+MaxLFQ roll-up to proteins when `quant.protein_lfq` is true too (an addition, protein_lfq.hip: `protein_lfq.tsv`),
 isobaric-tag (TMT) reporter-ion quantification when `quant.tmt` is set (runner.rs:334-359, 398-410, tmt.hip: `tmt.tsv`),
 IDPicker protein groups with the picked protein-group FDR when the configuration names `protein_grouping` or
 `protein_grouping_peptide_fdr` (runner.rs:539-549, rescore.hip + groups.cpp; see run()) and the optional percolator .pin file;
@@ -25,7 +26,7 @@ from . import output
 from ._lib import FEATURE_DTYPE as L_FEATURE_DTYPE
 from .api import (LFQ_INTEGRATION, LFQ_SCORING, DatabaseParameters, DeviceDatabase, Isobaric, LfqSettings, RawBatch, Scorer,
                   ScorerParams, SpectrumBatch, SpectrumProcessor, TmtSettings, Tolerance, device_count, lfq, peptide_compositions,
-                  predict_rt, protein_groups, rescore, tmt)
+                  predict_rt, protein_groups, protein_lfq, rescore, tmt)
 from .mgf import TOL_DA, is_mgf, read_mgf_native, read_spectra
 
 
@@ -84,6 +85,21 @@ def quant_settings(cfg: dict, log=print):
         log("lfq_settings.peptide_q_value is higher than expected, expect increased runtime and memory usage")
     if st.peptide_q_value < 0.01:
         log("lfq_settings.peptide_q_value is lower than expected, not all identified peptides will have MS1 intensities extracted")
+    return on, st
+
+
+def protein_lfq_settings(cfg: dict):
+    """quant.protein_lfq / quant.protein_lfq_settings — an addition over the reference, whose serde structs ignore the keys
+    (DESIGN.md 7g): (on, {"min_ratio_count", "precursor_q_value"}).  The roll-up reads lfq.tsv's rows, so it needs quant.lfq."""
+    q = cfg.get("quant") or {}
+    on = bool(q.get("protein_lfq")) if q.get("protein_lfq") is not None else False
+    o = q.get("protein_lfq_settings") or {}
+    st = {"min_ratio_count": 1 if o.get("min_ratio_count") is None else int(o["min_ratio_count"]),
+          "precursor_q_value": 0.05 if o.get("precursor_q_value") is None else float(o["precursor_q_value"])}
+    if st["min_ratio_count"] < 0:
+        raise SystemExit("quant.protein_lfq_settings.min_ratio_count must not be negative")
+    if on and not (q.get("lfq") is not None and bool(q.get("lfq"))):
+        raise SystemExit("`quant.protein_lfq: true` needs `quant.lfq: true`: the protein roll-up reads the precursor areas of lfq.tsv")
     return on, st
 
 
@@ -436,6 +452,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         raise SystemExit("sage_amd.cli: no HIP device visible — libsage_hip has no CPU fallback")
     sp = search_parameters(cfg)
     lfq_on, lfq_settings = quant_settings(cfg, log)
+    protein_lfq_on, protein_lfq_st = protein_lfq_settings(cfg)
     isobaric, tmt_st = tmt_settings(cfg, log)
     # runner.rs:391-410: S/N division at the quant level; at level 2 the reporter region is kept out of deisotoping
     sn_level = tmt_st.level if (isobaric is not None and tmt_st.sn) else None
@@ -689,6 +706,19 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         lp = os.path.join(output_directory, "lfq.tsv")
         output.write_lfq_native(lp, host, lfq_result, filenames)
         paths.append(lp)
+    protein_lfq_summary = {}
+    if lfq_result is not None and protein_lfq_on:  # MaxLFQ over lfq.tsv's rows, one protein (group) per peptide
+        t0 = time.time()
+        used, ids, names = output.protein_lfq_assignment(host, lfq_result, flat, groups, protein_lfq_st["precursor_q_value"])
+        rolled = protein_lfq(lfq_result.areas[used.astype(np.int64)].reshape(len(used), len(filenames)), ids, len(names),
+                             protein_lfq_st["min_ratio_count"], device=device)
+        pp = os.path.join(output_directory, "protein_lfq.tsv")
+        n_written = output.write_protein_lfq_native(pp, names, rolled, filenames)
+        paths.append(pp)
+        protein_lfq_ms = (time.time() - t0) * 1000.0
+        log(f"- protein roll-up (MaxLFQ): {int(protein_lfq_ms):8d} ms ({n_written} proteins from {len(used)} precursors)")
+        protein_lfq_summary = {"protein_lfq_rows": n_written, "protein_lfq_ms": protein_lfq_ms,
+                               "protein_lfq_device_ms": rolled.stage_ms["device_ms"]}
     if write_pin:  # runner.rs:655-660
         pp = os.path.join(output_directory, "results.sage.pin")
         output.write_results_native(pp, "pin", host, flat, list(order), psm_ids, filenames, spec_ids, [rtp, post])
@@ -704,7 +734,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     stage_totals["total_after_index_ms"] = (time.time() - t_run) * 1e3
     summary = {"version": "sage-hip 0.1 (search-and-score path of sage 0.15.0-beta.2)", "psms": len(flat),
                "spectra_searched": n_searched, "search_ms": search_ms, "stages": stage_totals, "output_paths": paths, **rescore_summary,
-               **lfq_summary, **tmt_summary, **isomer_summary, **localise_summary}
+               **lfq_summary, **tmt_summary, **isomer_summary, **localise_summary, **protein_lfq_summary}
     with open(os.path.join(output_directory, "results.json"), "w") as fh:
         json.dump(dict(cfg, output_paths=paths, summary=summary), fh, indent=2, default=str)
     return summary

@@ -172,6 +172,61 @@ int sage_hip_tmt(int device, const SageTmtInput* in, SageTmtOutput* out) {
     return rc == SAGE_HIP_OK ? rc : fail(rc, err);
 }
 
+// protein-level label-free quantification, MaxLFQ (protein_lfq.hip)
+int sage_hip_protein_lfq(int device, const SageProteinLfqInput* in, SageProteinLfqOutput* out) {
+    if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_protein_lfq: null argument");
+    out->log_ms = out->median_ms = out->solve_ms = out->device_ms = 0.0f;
+    out->n_batches = 0;
+    if (in->n_files > 65535u) return fail(SAGE_HIP_ERR_UNSUPPORTED, "sage_hip_protein_lfq: more than 65535 files");
+    if (in->n_rows && (!in->protein_of_row || (in->n_files && !in->areas)))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_protein_lfq: null input array");
+    if (in->n_proteins == 0) {
+        for (uint64_t r = 0; r < in->n_rows; ++r)
+            if (in->protein_of_row[r] != 0xFFFFFFFFu)
+                return fail(SAGE_HIP_ERR_INVALID, "sage_hip_protein_lfq: a protein id that is not below n_proteins (0)");
+        return SAGE_HIP_OK;
+    }
+    if (!out->n_rows_used || !out->n_components || (in->n_files && (!out->log_abundance || !out->intensity || !out->component)))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_protein_lfq: null output array");
+    if (in->n_rows == 0 || in->n_files == 0) {  // nothing to launch: no file of any protein is quantified
+        const uint64_t nf = in->n_files, cells = (uint64_t)in->n_proteins * nf, pairs = nf ? in->n_proteins * (nf * (nf - 1) / 2) : 0;
+        for (uint32_t p = 0; p < in->n_proteins; ++p) out->n_rows_used[p] = out->n_components[p] = 0;
+        for (uint64_t r = 0; r < in->n_rows; ++r) {
+            const uint32_t p = in->protein_of_row[r];
+            if (p == 0xFFFFFFFFu) continue;
+            if (p >= in->n_proteins) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_protein_lfq: a protein id that is not below n_proteins");
+            ++out->n_rows_used[p];
+        }
+        for (uint64_t i = 0; i < cells; ++i) {
+            out->log_abundance[i] = std::nan("");
+            out->intensity[i] = 0.0;
+            out->component[i] = 0xFFFFFFFFu;
+        }
+        for (uint64_t i = 0; i < pairs; ++i) {
+            if (out->pair_median) out->pair_median[i] = std::nan("");
+            if (out->pair_count) out->pair_count[i] = 0;
+        }
+        return SAGE_HIP_OK;
+    }
+    if (const int rc = stage_guard("sage_hip_protein_lfq", in->n_rows)) return rc;
+    std::string err;
+    const int rc = protein_lfq_on_device(device, *in, *out, err);
+    return rc == SAGE_HIP_OK ? rc : fail(rc, err);
+}
+
+int sage_hip_write_protein_lfq(const char* path, const char* const* protein_names, uint32_t n_proteins, const uint32_t* rows,
+                               uint32_t n_out, const SageProteinLfqOutput* result, const char* const* filenames, uint32_t n_files) {
+    if (!path || !result || (n_out && (!rows || !protein_names || !result->n_rows_used || !result->n_components ||
+                                       (n_files && !result->intensity))) || (n_files && !filenames))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_protein_lfq: null argument");
+    for (uint32_t r = 0; r < n_out; ++r)
+        if (rows[r] >= n_proteins || !protein_names[rows[r]])
+            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_protein_lfq: protein id out of range or null name");
+    std::string err;
+    if (!write_protein_lfq(path, protein_names, rows, n_out, *result, filenames, n_files, err)) return fail(SAGE_HIP_ERR_INVALID, err);
+    return SAGE_HIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------

@@ -112,6 +112,8 @@ bool write_lfq(const char* path, const HostDb& db, const SageLfqOutput& g, const
 bool write_tmt(const char* path, const char* const* headers, uint32_t n_labels, uint64_t n_rows, const uint32_t* file_id,
                const char* const* spec_ids, const float* ion_injection_time, const float* intensity, const char* const* filenames,
                uint32_t n_files, std::string& err);
+bool write_protein_lfq(const char* path, const char* const* protein_names, const uint32_t* rows, uint32_t n_out,
+                       const SageProteinLfqOutput& result, const char* const* filenames, uint32_t n_files, std::string& err);
 
 // groups.cpp: the host half of protein grouping (protein_grouping.rs:159-231 ProteinGrouper::build)
 struct GroupGraph {

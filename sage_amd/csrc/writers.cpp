@@ -357,4 +357,37 @@ bool write_tmt(const char* path, const char* const* headers, uint32_t n_labels, 
     return ok;
 }
 
+// protein_lfq.tsv: one row per protein id of `rows`; the intensities as ryu f64, 0.0 where not quantified.
+bool write_protein_lfq(const char* path, const char* const* protein_names, const uint32_t* rows, uint32_t n_out,
+                       const SageProteinLfqOutput& result, const char* const* filenames, uint32_t n_files, std::string& err) {
+    FILE* fh = std::fopen(path, "wb");
+    if (!fh) {
+        err = std::string("cannot open ") + path;
+        return false;
+    }
+    std::string out = "proteins\tn_precursors\tn_components";
+    for (uint32_t f = 0; f < n_files; ++f) {
+        out += '\t';
+        field(out, filenames[f]);
+    }
+    out += '\n';
+    bool ok = true;
+    for (uint32_t r = 0; r < n_out && ok; ++r) {
+        const uint64_t p = rows[r];
+        str(out, protein_names[p]);
+        itoa(out, result.n_rows_used[p]);
+        itoa(out, result.n_components[p]);
+        for (uint32_t f = 0; f < n_files; ++f) f64(out, result.intensity[p * n_files + f]);
+        out.back() = '\n';
+        if (out.size() >= (1 << 20)) {
+            ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+            out.clear();
+        }
+    }
+    if (ok && !out.empty()) ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+    if (std::fclose(fh) != 0) ok = false;
+    if (!ok && err.empty()) err = std::string("write to ") + path + " failed";
+    return ok;
+}
+
 }  // namespace sagehip

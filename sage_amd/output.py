@@ -316,6 +316,70 @@ def write_lfq_native(path: str, db, result, filenames: Sequence[str], rows=None)
                                         len(filenames)))
 
 
+PROTEIN_LFQ_HEADERS = ["proteins", "n_precursors", "n_components"]
+
+
+def protein_lfq_assignment(db, lfq_result, features=None, groups=None, precursor_q_value: float = 0.05):
+    """The input of api.protein_lfq from a run's LfqResult: (grid rows used, protein id of each, protein names by
+    id).  Rows: lfq.tsv's (LfqResult.target_rows()) with q_value <= precursor_q_value whose peptide belongs to one protein only —
+    with `groups` (a ProteinGroupResult over `features`, the run's PSMs) the peptide's protein_groups string where its
+    num_protein_groups == 1, else the peptide's `proteins` string where its num_proteins == 1.  Shared peptides are left out.
+    Ids by first appearance in grid order."""
+    by_peptide = {}
+    if groups is not None:
+        for i, pep in enumerate(np.asarray(features["peptide_idx"]).tolist()):
+            if pep not in by_peptide:
+                by_peptide[pep] = (groups.protein_groups(i), int(groups.num_protein_groups[i]))
+    rows, ids, names, id_of = [], [], [], {}
+    for i in lfq_result.target_rows().tolist():
+        if not lfq_result.q_value[i] <= np.float32(precursor_q_value):
+            continue
+        pep = int(lfq_result.peptide_idx[i])
+        if groups is not None:
+            name, count = by_peptide.get(pep, ("", 0))
+        else:
+            name, count = db.peptide_proteins(pep), db.peptide_info(pep)[0]
+        if count != 1:
+            continue
+        if name not in id_of:
+            id_of[name] = len(names)
+            names.append(name)
+        rows.append(i)
+        ids.append(id_of[name])
+    return np.array(rows, np.uint64), np.array(ids, np.uint32), names
+
+
+def protein_lfq_rows(names: Sequence[str], result, rows=None) -> List[List[str]]:
+    """protein_lfq.tsv's rows for a ProteinLfqResult-like object (n_rows_used, n_components, intensity): one per protein id of
+    `rows` (default: every protein with at least one used row, in id order); the intensities as ryu f64, 0.0 = not quantified."""
+    rows = np.flatnonzero(np.asarray(result.n_rows_used) > 0) if rows is None else rows
+    return [[names[int(p)], str(int(result.n_rows_used[int(p)])), str(int(result.n_components[int(p)]))] +
+            [ryu_f64(np.float64(x)) for x in result.intensity[int(p)]] for p in rows]
+
+
+def write_protein_lfq(path: str, filenames: Sequence[str], rows: Sequence[List[str]]) -> None:
+    with open(path, "w", newline="") as fh:
+        fh.write(_record(PROTEIN_LFQ_HEADERS + list(filenames)) + "\n")
+        for r in rows:
+            fh.write(_record(r) + "\n")
+
+
+def write_protein_lfq_native(path: str, names: Sequence[str], result, filenames: Sequence[str], rows=None) -> int:
+    """protein_lfq.tsv through the C++ writer (sage_hip_write_protein_lfq): the bytes of protein_lfq_rows + write_protein_lfq.
+    Returns the number of rows written."""
+    import ctypes as C
+
+    from . import _lib as L
+    rows = np.ascontiguousarray(np.flatnonzero(np.asarray(result.n_rows_used) > 0) if rows is None else rows, dtype=np.uint32)
+    keep = []
+    cout = result.to_c(keep)
+    table = (C.c_char_p * max(len(names), 1))(*[s.encode() for s in names])
+    files = (C.c_char_p * max(len(filenames), 1))(*[s.encode() for s in filenames])
+    L.check(L.load().sage_hip_write_protein_lfq(path.encode(), table, len(names), L.as_ptr(rows, C.c_uint32), len(rows), C.byref(cout),
+                                                files, len(filenames)))
+    return len(rows)
+
+
 TMT_HEADERS = ["filename", "scannr", "ion_injection_time"]
 
 
