@@ -647,7 +647,9 @@ SAGE_HD void lut_cells(float lo, float hi, float scale, uint32_t stride, uint32_
     float cl = __builtin_floorf(lo * scale);
     float ch = __builtin_floorf(hi * scale) + 1.0f;
     cl = cl > 0.0f ? cl : 0.0f;  // also maps NaN to 0
-    ch = ch > 0.0f ? ch : 0.0f;
+    // every m/z below zero lies in cell 0's run (row entry 0 is the tile's start): a window that ends below zero still reads that
+    // run, so the end cell is 1 at the least (tests/test_index_search_cpu.py: windows aimed at negative entries)
+    ch = ch > 1.0f ? ch : 1.0f;
     // a window beyond the table starts at the last real cell (stride - 2), whose run also holds every entry beyond the table
     // (a table capped below the largest m/z); it ends with the tile
     icl = cl < (float)(stride - 2) ? (uint32_t)cl : stride - 2;
@@ -692,8 +694,9 @@ SAGE_HD uint32_t lut_rank(const LutWord& w, uint32_t c) {
 }
 
 // ---- select_most_intense_peak through a direct-index table (rescore_kernel) ------------------------------------------------
-// plut[b] = number of peaks with mass < b * W (total order).  W is a power of two, so bin(lo) = floor(lo / W) and b * W are
-// exact and plut[bin(lo)] <= partition_point(mass < lo): a short forward walk finishes the job.  Same peaks considered and
+// plut[b] = number of peaks with mass < b * W (total order) for b >= 1, plut[0] = 0.  W is a power of two, so bin(lo) =
+// max(floor(lo / W), 0) and b * W are exact and plut[bin(lo)] <= partition_point(mass < lo), for a negative lo too: a short
+// forward walk finishes the job.  Same peaks considered and
 // the same filtered scan as select_most_intense_peak above.
 constexpr uint32_t PLUT_BINS = 256;
 SAGE_HD float peak_lut_width(float top) {  // a power of two w >= 1 with PLUT_BINS * w > the largest mass (any power of two is CORRECT:
@@ -719,6 +722,9 @@ SAGE_HD float pow2_reciprocal(float w) {  // exact 1 / w for a normal power of t
     return r;
 }
 SAGE_HD uint32_t peak_lut_entry(const float* pm, uint32_t P, uint32_t b, float w) {
+    // (bin 0 also takes every window that starts below zero — select_peak_lut clamps its bin there — so it starts at the first
+    // peak, not behind the negative masses: tests/test_index_search_cpu.py)
+    if (b == 0) return 0;
     const int32_t edge = order_key((float)b * w);
     uint32_t lo = 0, hi = P;
     while (lo < hi) {

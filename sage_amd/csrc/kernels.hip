@@ -2876,8 +2876,9 @@ __device__ __forceinline__ uint4 fresh_zero4() {
 __device__ __forceinline__ void build_peak_lut(uint32_t* plut, float& inv_w, const float* pm, uint32_t P) {
     // plut[b] = number of peaks with mass < b * W in the total order (core.h: peak_lut_entry) — by counting instead of 256
     // binary searches: W is a power of two, so bin(m) = floor(m / W) is exact and `mass < b * W` <=> bin(m) < b; masses below
-    // +0.0 in the total order (negative, -0.0, negative NaN) lie before every edge, +inf / NaN behind every edge.  A histogram
-    // shifted by one bin, then its inclusive prefix sum.
+    // +0.0 in the total order (negative, -0.0, negative NaN) lie before every edge but edge 0 (plut[0] == 0: a window that
+    // starts below zero reads bin 0 and must meet them), +inf / NaN behind every edge.  A histogram shifted by one bin, then its
+    // inclusive prefix sum.
     const uint32_t lane = lane_id();
     const float w = peak_lut_width(P ? pm[P - 1] : 0.0f);
     inv_w = pow2_reciprocal(w);
@@ -2888,7 +2889,7 @@ __device__ __forceinline__ void build_peak_lut(uint32_t* plut, float& inv_w, con
     for (uint32_t i = lane; i < P; i += WAVE) {
         const float m = pm[i];
         if (order_key(m) < 0) {
-            atomicAdd(&plut[0], 1u);  // before every edge
+            atomicAdd(&plut[1], 1u);  // before every edge from 1 on
         } else if (m == m) {
             const float f = __builtin_floorf(m * inv_w);
             if (f < (float)(PLUT_BINS - 1)) atomicAdd(&plut[(uint32_t)f + 1u], 1u);  // bin f: counted from edge f + 1 on

@@ -18,6 +18,34 @@ def product_process(top_n, deiso, min_mz, mz, it, z):
     return out.masses, out.intensities, out.total_ion_current
 
 
+def check(dev, orc, batch, params, context, hits=True, every=1):
+    """One scorer configuration on a ready device database, oracle and batch: the preliminary lists, every Feature field, a second
+    step on the same handle and the host-to-host entry point.  Returns (PSMs, the first step's timing)."""
+    # OpenMSHyperScore goes through f32 ln_1p: device libm and glibc may differ by an f32 ulp (~6e-8 relative).
+    # SageHyperScore uses f64 ln only — correctly rounded on both sides: the f64 fields are held to EQUALITY
+    # (parity_utils.assert_features_equal).  North-star tolerance: 1e-4.
+    rel_tol = 1e-6 if params.score_type == "OpenMSHyperScore" else None
+    scorer = Scorer(dev, params)
+    dbatch = scorer.upload(batch)
+    if hits:
+        assert_initial_hits_equal(scorer, dbatch, orc, params, batch, context, every)
+    gf, gc = scorer.score_resident(dbatch)
+    gf, gc = gf.copy(), gc.copy()
+    t_first = scorer.last_timing()
+    of, oc, _, _ = orc.score(params, batch)
+    n = assert_features_equal(gf, gc, of, oc, context, rel_tol)
+    # once more on the same handle: the first step of a handle launches its exact retry pass; a later narrow-search step only when
+    # the step before had something to retry.  This repeat of the SAME batch reaches "left out, nothing found" or "not left out",
+    # never the late launch (left out, retries found): tests/test_gpu_handle_sequences.py walks that route
+    gfb, gcb = scorer.score_resident(dbatch)
+    assert np.array_equal(gc, gcb) and gf[np.arange(gf.shape[1])[None, :] < gc[:, None]].tobytes() == \
+        gfb[np.arange(gf.shape[1])[None, :] < gc[:, None]].tobytes(), f"{context}: the second step on the same scorer differs"
+    assert scorer.last_timing()["n_retry"] == t_first["n_retry"], context
+    gf2, gc2 = scorer.score(batch)  # the upload+score+download entry point
+    assert_features_equal(gf2, gc2, of, oc, context + " (score_batch)", rel_tol)
+    return n, t_first
+
+
 class World:
     def __init__(self, fasta, db_params, spectra_kwargs, n_spectra, seed, max_peaks=150):
         self.host = db_params.build(fasta)
@@ -28,30 +56,7 @@ class World:
         self.batch = SpectrumBatch.from_spectra([sp.process(r) for r in raw])
 
     def check(self, params, context, hits=True, batch=None, every=1, dev=None):
-        # OpenMSHyperScore goes through f32 ln_1p: device libm and glibc may differ by an f32 ulp (~6e-8 relative).
-        # SageHyperScore uses f64 ln only — correctly rounded on both sides: the f64 fields are held to EQUALITY
-        # (parity_utils.assert_features_equal).  North-star tolerance: 1e-4.
-        rel_tol = 1e-6 if params.score_type == "OpenMSHyperScore" else None
-        batch = batch or self.batch
-        scorer = Scorer(dev or self.dev, params)
-        dbatch = scorer.upload(batch)
-        if hits:
-            assert_initial_hits_equal(scorer, dbatch, self.orc, params, batch, context, every)
-        gf, gc = scorer.score_resident(dbatch)
-        gf, gc = gf.copy(), gc.copy()
-        t_first = scorer.last_timing()
-        of, oc, _, _ = self.orc.score(params, batch)
-        n = assert_features_equal(gf, gc, of, oc, context, rel_tol)
-        # once more on the same handle: the first step of a handle launches its exact retry pass; a later narrow-search step only when
-        # the step before had something to retry.  This repeat of the SAME batch reaches "left out, nothing found" or "not left out",
-        # never the late launch (left out, retries found): tests/test_gpu_handle_sequences.py walks that route
-        gfb, gcb = scorer.score_resident(dbatch)
-        assert np.array_equal(gc, gcb) and gf[np.arange(gf.shape[1])[None, :] < gc[:, None]].tobytes() == \
-            gfb[np.arange(gf.shape[1])[None, :] < gc[:, None]].tobytes(), f"{context}: the second step on the same scorer differs"
-        assert scorer.last_timing()["n_retry"] == t_first["n_retry"], context
-        gf2, gc2 = scorer.score(batch)  # the upload+score+download entry point
-        assert_features_equal(gf2, gc2, of, oc, context + " (score_batch)", rel_tol)
-        return n, t_first
+        return check(dev or self.dev, self.orc, batch or self.batch, params, context, hits, every)
 
 
 @pytest.fixture(scope="module")
