@@ -80,7 +80,7 @@ static int scorer_init(SageScorer* sp, SageDeviceDb* db, const SageScorerParams*
     // (bit 31: heaviest precursors first — the default since round 6: the expensive spectra start first and the step's tail is made
     // of cheap ones; a rank's 62 500-spectrum C3 shard -7 %, C2 -4 %, 500 000 spectra -1 %: scripts/experiments/r06_lab/gpu_r7y.sh)
     // Batches that may hold large windows keep the ascending order unless the variable asks (C4 +1 % with it, C5 -0.5 %: their
-    // steps are the count kernel's, which takes the spectra in queue order): enqueue_compute.
+    // steps are the count kernel's, which takes the spectra in queue order): plan_step.
     {
         const char* e = getenv("SAGE_HIP_SCHED_DESC");
         if (!e || atoi(e)) d.xcd_chunk |= 0x80000000u;
@@ -134,8 +134,6 @@ static int scorer_init(SageScorer* sp, SageDeviceDb* db, const SageScorerParams*
         s->ways = 1;
     }
     for (hipStream_t& ws : s->way_stream) HIP_TRY(hipStreamCreateWithFlags(&ws, hipStreamNonBlocking));
-    HIP_TRY(s->way_fork.create(false));
-    for (Event& e : s->way_join) HIP_TRY(e.create(false));
     HIP_TRY(s->way_begin.create(true));
     for (Event& e : s->way_end) HIP_TRY(e.create(true));
     HIP_TRY(s->side_fork.create(false));
@@ -200,7 +198,7 @@ int sage_hip_scorer_create(SageDeviceDb* db, const SageScorerParams* p, SageScor
     if (!db || !p || !out) return fail(SAGE_HIP_ERR_INVALID, "null argument");
     if (p->report_psms == 0) return fail(SAGE_HIP_ERR_INVALID, "report_psms must be >= 1");
     // (trim_hits keeps max(50, 2 * report_psms) candidates, scoring.rs:322-329, and the reference has no cap; lists that no longer fit
-    // a compute unit's LDS live in a global-memory workspace — enqueue_compute: hugebuf.  16-bit fields of the large-window
+    // a compute unit's LDS live in a global-memory workspace — plan_step: hugebuf.  16-bit fields of the large-window
     // records bound the list at 65 534 entries.)
     if (p->report_psms > 32767) return fail(SAGE_HIP_ERR_UNSUPPORTED, "report_psms > 32767");
     if (p->min_isotope_err > p->max_isotope_err) return fail(SAGE_HIP_ERR_INVALID, "min_isotope_err > max_isotope_err");
@@ -518,7 +516,7 @@ static int check_batch_args(const SageSpectrumBatch* b) {
 // step ten empty launches, the second part's overlap, and a longer host turn-around (round 5: 0.75 against 0.69 ms per 62 500
 // C3 spectra).  The streaming pipeline keeps the estimate (it decides before the spectra are on the device).
 // A device batch may be scored by any handle; the windows in its records hold for a scorer with the uploading handle's index,
-// precursor tolerance, wide_window, isotope-error range, charge range and override only (every other scorer searches: enqueue_compute).
+// precursor tolerance, wide_window, isotope-error range, charge range and override only (every other scorer searches: plan_step).
 static WindowKey window_key(const SageScorer* s) {
     WindowKey k;
     std::memset(&k, 0, sizeof k);  // (compared as bytes)
@@ -536,7 +534,7 @@ static WindowKey window_key(const SageScorer* s) {
 }
 static int exact_window_check(SageScorer* s, SageDeviceBatch* d, hipStream_t st) {
     // (tests force the estimate's answer.  The records' third uint4 then stays unwritten — and unread: without a sched_key no
-    // scorer is told that the records hold windows, enqueue_compute)
+    // scorer is told that the records hold windows, plan_step)
     if (getenv("SAGE_HIP_ASSUME_NARROW") || d->n == 0) return SAGE_HIP_OK;
     HIP_TRY(s->win_max.reserve(1));
     HIP_TRY(hipMemsetAsync(s->win_max.p, 0, 4, st));
@@ -694,7 +692,7 @@ static uint64_t arena_entries_for(const SageScorer* s, uint32_t n) {
 }
 
 // The scorer's narrow first pass may hand its lists over in rows by schedule position (DevWork::hand): the production kernels with a
-// list and its header in one row of a word per lane.  (Which launches do: enqueue_compute.)
+// list and its header in one row of a word per lane.  (Which launches do: plan_step.)
 static bool hand_rows_possible(const SageScorer* s) {
     return s->hand_rows && s->dev.kmax <= HAND_LIST_MAX && !s->dev.big_path && !s->fused && !s->one_launch && !s->exact_always;
 }
@@ -782,7 +780,7 @@ static DevWork make_work(SageScorer* s, OutSet& o, int pass, int lane = 0) {
     w.kstride = s->kstride;
     w.reuse = 0;
     w.arena_ptr = w.n_deferred + CTR_ARENA_PTR;
-    w.cnt_store = nullptr;  // (enqueue_compute switches the cheap ties on for the first pass of a production search)
+    w.cnt_store = nullptr;  // (plan_step switches the cheap ties on for the first pass of a production search)
     w.cnt_stride = s->cnt_stride;
     w.tile_blocks = s->tile_blocks;
     w.qrec = ws.qrec.p;
@@ -800,31 +798,70 @@ enum { MODE_SCORE = 0,  // order-free trims, then the exact retry pass over the 
        MODE_EXACT = 1,  // every trim replays bounded_min_heapify: one pass
        MODE_FAST = 2 }; // order-free trims only (quick_score: which peptides survive does not depend on heap layouts)
 
-// Enqueue the kernels of one batch on `st` — nothing here waits for the device.
+// What a caller asks of the kernels of one batch: the batch, the OutSet and the stream, and by name whatever differs from the values here.
+struct StepRequest {
+    DevBatchView view;
+    OutSet* out;
+    hipStream_t stream;
+    StepRequest(const DevBatchView& v, OutSet& o, hipStream_t st) : view(v), out(&o), stream(st) {}
+    int mode = MODE_SCORE;
+    bool with_rescore = true;
+    // where the PSM records go — device memory (null: the OutSet's buffer) or the device-side view of page-locked host memory
+    SageFeature* rec = nullptr;
+    // false skips the ten launches of the large-window path: the caller checks the queue counter afterwards and repeats the
+    // batch with wide == true if the guess was wrong
+    bool wide = true;
+    // a part of a batch scored next to other parts (score_resident_locked): its queue / retry lists start at that offset of the
+    // shared arrays, and the PSM counts of all parts go to one buffer (they are indexed by spectrum; null: the OutSet's)
+    uint32_t list_off = 0;
+    uint32_t* count_buf = nullptr;
+    // which of the scorer's two working sets (a lane-1 batch never takes the large-window path: the replay kernels' side stream
+    // is lane 0's)
+    int lane = 0;
+    uint32_t widest = 0xFFFFFFFFu;  // SageDeviceBatch::widest, where the batch knows it
+};
+// Which passes of a request are enqueued now (resident steps, score_resident_locked).
+enum class Passes {
+    Both,        // the first pass and, behind it, the exact retry pass
+    FirstOnly,   // the exact retry pass is launched later if it turns out to have anything to do
+    RetryOnly,   // that retry pass alone (the first pass of this very request has completed)
+};
+// What plan_step decided for a request: everything the launches take, and which of them there will be.
+struct StepPlan {
+    DevScorer sc1{}, sc2{};    // first pass, exact retry pass
+    DevBatchView view{}, v2{}; // ... the retry pass walks the retry list, not the schedule
+    DevWork w1{}, w2{};
+    SageFeature* rec = nullptr;
+    uint32_t* count_buf = nullptr;
+    bool wide = false;        // the large-window kernels are launched (the request's, or any launch sequence but the production one)
+    bool fused = false;       // SAGE_HIP_FUSED=1: narrow_kernel as the first pass, too
+    bool one_launch = false;  // SAGE_HIP_ONE_LAUNCH=1: search_kernel as the first pass
+    bool two_pass = false;    // the exact retry pass belongs to this request
+    bool huge = false;        // the wide-list kernels keep their lists in WorkSet::hugebuf
+    bool wing = false;        // tile_count_wing_kernel counts (its windows in WorkSet::winbuf)
+    bool hand_on = false;     // the first pass hands its lists over in rows by schedule position (DevWork::hand)
+    bool later = false;       // queue_kernel builds the large-window queue behind prelim_kernel (DevWork::queue_later)
+};
+
+// Decide the launches of one request — nothing here enqueues a kernel; the working set grows if it has to (ensure_work, which
+// may wait for the stream), and the OutSet is told what collect will need.
 //   MODE_SCORE with rescoring, the production path.  First pass, order-free trims: prelim_kernel scores the narrow windows and
 //   queues the others; when `wide`, the large-window kernels take the queue; rescore_kernel reports every spectrum except those
 //   whose reported ranks tie in hyperscore, which it lists.  Exact retry pass over that list, launched unconditionally — the
 //   list and its COUNT live on the device (the first pass's CTR_RETRY counter), so no host round trip separates the passes, and
 //   with no tied spectrum its blocks exit at once: narrow_kernel (matching with bounded_min_heapify replayed + rescoring, one
 //   launch) reports the narrow ones and queues the others; when `wide`, the large-window kernels and rescore_kernel follow.
-//   `wide` == false skips the ten launches of the large-window path: the caller checks the queue counter afterwards and
-//   repeats the batch with wide == true if the guess was wrong.  SAGE_HIP_FUSED=1: narrow_kernel as the first pass, too.
+//   SAGE_HIP_FUSED=1: narrow_kernel as the first pass, too.
 //   Other modes: preliminary kernel, large-window kernels, rescoring kernel.
-// `rec`: where the PSM records go — device memory (null: the OutSet's buffer) or the device-side view of page-locked host memory.
-// `list_off` / `count_buf`: a part of a batch scored next to other parts (score_resident_locked): its queue / retry lists start
-// at that offset of the shared arrays, and the PSM counts of all parts go to one buffer (they are indexed by spectrum).
-// `lane`: which of the scorer's two working sets (a lane-1 batch never takes the large-window path: the replay kernels' side
-// stream is lane 0's).
-static int enqueue_compute(SageScorer* s, const DevBatchView& view_in, OutSet& o, bool with_rescore, int mode, hipStream_t st,
-                           SageFeature* rec = nullptr, bool wide = true, uint32_t list_off = 0, uint32_t* count_buf = nullptr,
-                           int lane = 0, int phase = 0, uint32_t widest = 0xFFFFFFFFu) {
-    // `phase` (resident steps, score_resident_locked): 0 both passes; 1 the first pass only — the exact retry pass is launched
-    // later if it turns out to have anything to do; 2 that retry pass alone (the first pass of this very launch has completed).
-    if (lane && wide) return fail(SAGE_HIP_ERR_INTERNAL, "large windows on the second working set");
-    WorkSet& wset = lane ? s->ws2 : s->ws;
+static int plan_step(SageScorer* s, const StepRequest& rq, Passes passes, StepPlan& p) {
+    OutSet& o = *rq.out;
+    p.wide = rq.wide;
+    if (rq.lane && p.wide) return fail(SAGE_HIP_ERR_INTERNAL, "large windows on the second working set");
+    WorkSet& wset = rq.lane ? s->ws2 : s->ws;
     DevScorer sc = s->dev;
-    if (wide && !s->sched_desc_forced) sc.xcd_chunk &= 0x7FFFFFFFu;  // (heaviest-first is the narrow search's default: scorer_init)
-    DevBatchView view = view_in;
+    if (p.wide && !s->sched_desc_forced) sc.xcd_chunk &= 0x7FFFFFFFu;  // (heaviest-first is the narrow search's default: scorer_init)
+    DevBatchView& view = p.view;
+    view = rq.view;
     {  // the records' windows are this scorer's only if they were computed from what it would compute them from
         const WindowKey mine = window_key(s);
         view.sched_win = view.sched && view.sched_stride == SCHED_RECORD_WINDOW && view.sched_key && std::memcmp(view.sched_key, &mine, sizeof mine) == 0;
@@ -836,93 +873,94 @@ static int enqueue_compute(SageScorer* s, const DevBatchView& view_in, OutSet& o
         const int rc_pm = ensure_pm_frag(s->db);
         if (rc_pm != SAGE_HIP_OK) return rc_pm;
     }
-    const bool production = mode == MODE_SCORE && with_rescore;
-    const bool fused = s->fused && production;
-    if (!production) wide = true;
-    int rc = ensure_work(s, view.n, lane, wide, st);
+    const bool production = rq.mode == MODE_SCORE && rq.with_rescore;
+    p.fused = s->fused && production;
+    if (!production) p.wide = true;
+    int rc = ensure_work(s, view.n, rq.lane, p.wide, rq.stream);
     if (rc != SAGE_HIP_OK) return rc;
-    rc = ensure_out(s, o, view.n, rec == nullptr);
+    rc = ensure_out(s, o, view.n, rq.rec == nullptr);
     if (rc != SAGE_HIP_OK) return rc;
-    if (!rec) rec = o.features.p;
-    if (!count_buf) count_buf = o.out_count.p;
-    const bool one_launch = production && !fused && s->one_launch;
+    p.rec = rq.rec ? rq.rec : o.features.p;
+    p.count_buf = rq.count_buf ? rq.count_buf : o.out_count.p;
+    p.one_launch = production && !p.fused && s->one_launch;
     // Lists wider than a wavefront (report_psms > 32) live in LDS while they fit a compute unit's 160 KB; a configuration whose
     // lists, heaps or per-candidate arrays do not — report_psms in the hundreds x many precursor-window queries per spectrum,
     // report_psms beyond ~500, thousands of peaks on top — gets them in a global-memory workspace, a slice per workgroup of the
     // (then capped) grids.  Slower again, and never a refusal.
-    bool huge = false;
+    p.huge = false;
     if (sc.big_path) {
         const size_t cap = (size_t)160 * 1024;
-        huge = prelim_lds_bytes(sc, view) > cap || rescore_lds_bytes(sc, view, s->db->max_ions, true) > cap || assemble_lds_bytes(sc) > cap ||
+        p.huge = prelim_lds_bytes(sc, view) > cap || rescore_lds_bytes(sc, view, s->db->max_ions, true) > cap || assemble_lds_bytes(sc) > cap ||
                (size_t)s->kstride * 8 + 256 > cap || getenv("SAGE_HIP_FORCE_HUGE") != nullptr;  // (tests force the workspace on small lists)
     }
-    const size_t lds_p = sc.big_path ? prelim_lds_bytes(sc, view, huge)
-                                     : std::max(production ? std::max(narrow_lds_bytes(sc, view), one_launch ? search_lds_bytes(sc, view) : (size_t)0) : (size_t)0, prelim_lds_bytes(sc, view)),
-                 lds_r = rescore_lds_bytes(sc, view, s->db->max_ions, true, huge);
+    const size_t lds_p = sc.big_path ? prelim_lds_bytes(sc, view, p.huge)
+                                     : std::max(production ? std::max(narrow_lds_bytes(sc, view), p.one_launch ? search_lds_bytes(sc, view) : (size_t)0) : (size_t)0, prelim_lds_bytes(sc, view)),
+                 lds_r = rescore_lds_bytes(sc, view, s->db->max_ions, true, p.huge);
     // the large-window count kernel keeps a window per (peak, fragment charge) in LDS next to a tile's counters; when that does not
     // fit a compute unit, the instance with the windows in global memory takes the batch (tile_count_wing_kernel)
-    const bool wing = wide && tile_lds_bytes(s->db->view, sc, view) > 160 * 1024;
-    const size_t lds_t = wide ? tile_lds_bytes(s->db->view, sc, view, false, wing) : 0;
+    p.wing = p.wide && tile_lds_bytes(s->db->view, sc, view) > 160 * 1024;
+    const size_t lds_t = p.wide ? tile_lds_bytes(s->db->view, sc, view, false, p.wing) : 0;
     // (every per-spectrum kernel may take a whole CU's LDS: spectrum_kernel_prepare / bigk_kernel_prepare at scorer creation)
     const size_t lds_cap = (size_t)160 * 1024;
-    const size_t lds_a = sc.big_path && !huge ? assemble_lds_bytes(sc) : 0;
+    const size_t lds_a = sc.big_path && !p.huge ? assemble_lds_bytes(sc) : 0;
     if (lds_p > lds_cap || lds_r > lds_cap || lds_a > lds_cap || lds_t > 160 * 1024)
         return fail(SAGE_HIP_ERR_UNSUPPORTED,
                     sc.big_path ? "candidate lists too long for the LDS of a compute unit (report_psms x precursor-window queries per spectrum, or peaks x "
                                    "fragment charges): lower report_psms or narrow the charge / isotope-error ranges"
                                  : "spectrum too large for the LDS of a compute unit (~15 000 peaks per processed spectrum): lower max_peaks");
-    if (huge) {
+    if (p.huge) {
         // (a slice per workgroup of the capped grids — and a batch of fewer spectra launches fewer workgroups: ADVICE r05)
         // (the per-query kernels launch min(spectra x queries per spectrum, cap) workgroups, the per-spectrum ones fewer)
         const uint64_t blocks = std::max<uint64_t>((uint64_t)view.n * std::max<uint32_t>(s->qmax, 1u), 1u);
         const size_t need = (size_t)std::min<uint64_t>(huge_grid(), blocks) * huge_stride_bytes(sc);
         if (wset.hugebuf.n < need) {
-            HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipStreamSynchronize(rq.stream));
             HIP_TRY(wset.hugebuf.reserve(need));
         }
     }
-    if (wing) {  // [tile_blocks][2][fzcap * pcap] floats
+    if (p.wing) {  // [tile_blocks][2][fzcap * pcap] floats
         const size_t need = (size_t)std::max(s->tile_blocks, s->tile_blocks8) * 2 * view.fzcap * view.pcap;
         if (wset.winbuf.n < need) {
-            HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipStreamSynchronize(rq.stream));
             HIP_TRY(wset.winbuf.reserve(need));
         }
     }
-    o.two_pass = production && !(fused && !wide);  // (the fused first pass settles the ties of narrow spectra itself)
-    o.with_rescore = with_rescore;
-    o.fused = fused || one_launch;
-    o.wide_launched = wide;
-    o.n = view.n;
-    DevBatchView v2 = view;
+    p.two_pass = production && !(p.fused && !p.wide);  // (the fused first pass settles the ties of narrow spectra itself)
+    o.two_pass = p.two_pass;
+    o.with_rescore = rq.with_rescore;
+    o.wide_launched = p.wide;
+    DevBatchView& v2 = p.v2;
+    v2 = view;
     v2.sched = nullptr;  // (the retry list is not the schedule)
     v2.sched_win = 0;
-    v2.order = wset.retry.p + list_off;  // filled by the rescoring kernel of the first pass, in no particular order
+    v2.order = wset.retry.p + rq.list_off;  // filled by the rescoring kernel of the first pass, in no particular order
     v2.n_dev = o.counters.p + CTR_RETRY;
-    if (one_launch && ++wset.epoch == 0) wset.epoch = 1;
-    DevWork w1 = make_work(s, o, 0, lane), w2 = make_work(s, o, 1, lane);
+    if (p.one_launch && ++wset.epoch == 0) wset.epoch = 1;
+    DevWork &w1 = p.w1, &w2 = p.w2;
+    w1 = make_work(s, o, 0, rq.lane);
+    w2 = make_work(s, o, 1, rq.lane);
     for (DevWork* w : {&w1, &w2}) {
-        w->queue += list_off;
-        w->retry += list_off;
+        w->queue += rq.list_off;
+        w->retry += rq.list_off;
     }
-    const bool fast_ties = s->fast_ties && production && !fused && !one_launch && o.two_pass;
+    const bool fast_ties = s->fast_ties && production && !p.fused && !p.one_launch && p.two_pass;
     if (fast_ties) {  // (each part of a step owns the rows / entries [list_off, list_off + n) of these arrays)
-        w1.cnt_store = wset.cnt_store.p + (size_t)list_off * s->cnt_stride;  // (rows by schedule position within the part)
+        w1.cnt_store = wset.cnt_store.p + (size_t)rq.list_off * s->cnt_stride;  // (rows by schedule position within the part)
     }
     // The first pass's hand-over in schedule order (DevWork::hand), one trip earlier for rescore_kernel: where the pass is
     // prelim_kernel then rescore_kernel and nothing else — no large-window kernels behind prelim_kernel (they write and read the
     // arrays by spectrum), schedule records to read the row beside, a list and its header in 64 words.  Every other launch sequence
     // — the retry pass, quick_score and initial_hits (not `production`), SAGE_HIP_NO_SCHED=1 — keeps the arrays by spectrum.
-    const bool hand_on = production && !fused && !one_launch && !wide && !huge && view.sched != nullptr && hand_rows_possible(s) &&
-                         (uint64_t)list_off + view.n <= wset.cap_hand;
-    if (hand_on) w1.hand = wset.hand.p + (size_t)list_off * HAND_ROW_WORDS;  // (rows by schedule position within the part)
-    if (phase != 2) s->last_hand = hand_on;
-    if (wing) w1.winbuf = w2.winbuf = wset.winbuf.p;
-    o.huge = huge;
-    if (huge) {
+    p.hand_on = production && !p.fused && !p.one_launch && !p.wide && !p.huge && view.sched != nullptr && hand_rows_possible(s) &&
+                         (uint64_t)rq.list_off + view.n <= wset.cap_hand;
+    if (p.hand_on) w1.hand = wset.hand.p + (size_t)rq.list_off * HAND_ROW_WORDS;  // (rows by schedule position within the part)
+    if (passes != Passes::RetryOnly) s->last_hand = p.hand_on;
+    if (p.wing) w1.winbuf = w2.winbuf = wset.winbuf.p;
+    if (p.huge) {
         w1.hugebuf = w2.hugebuf = wset.hugebuf.p;
         w1.huge_stride = w2.huge_stride = (uint32_t)huge_stride_bytes(sc);
     }
-    if (production && s->cnt8 && !wing) {  // (only a pass that is followed by the retry pass may count in u8)
+    if (production && s->cnt8 && !p.wing) {  // (only a pass that is followed by the retry pass may count in u8)
         w1.cnt8 = 1;
         w1.tile_blocks = s->tile_blocks8;
     }
@@ -930,32 +968,8 @@ static int enqueue_compute(SageScorer* s, const DevBatchView& view_in, OutSet& o
         w2.reuse = 1;
         w2.arena_ptr = w1.arena_ptr;
     }
-    const SideStream side{s->side_stream, s->side_fork.e, s->side_join.e};
-    DevScorer sc1 = sc, sc2 = sc;
-    sc1.exact = mode == MODE_EXACT ? 1u : 0u;
-    sc1.fast_log = o.two_pass ? 1u : 0u;  // (an undecided logarithm is settled by the retry pass: launch_rescore)
-    sc2.exact = 1u;
-    sc2.fast_log = 0u;
-    const bool no_timing = !s->timed;  // (sage_hip_scorer_set_timing_interval)
-    o.timed = s->timed;
-    // (phase 2 is the late launch behind a phase-1 step: the flag stays set until collect_retry has read the pass's counters)
-    if (phase != 2) o.retry_deferred = phase == 1 && o.two_pass;
-    if (phase == 2) {
-        // the retry list's length: the first pass left it in the counter block, the epilogue sent it home and zeroed the block
-        HIP_TRY(hipMemcpyAsync(o.counters.p + CTR_RETRY, o.h_counters + CTR_RETRY, 4, hipMemcpyHostToDevice, st));
-        o.counters_clean = false;
-        if (!no_timing) HIP_TRY(hipEventRecord(o.ev[2].e, st));
-        goto retry_pass;
-    }
-    // (score_resident's epilogue kernel leaves the counters zeroed for the next step: one command less ahead of the first kernel)
-    if (!o.counters_clean) HIP_TRY(hipMemsetAsync(o.counters.p, 0, 2 * CTR_COUNT * 4, st));
-    o.counters_clean = false;
-    if (!no_timing) HIP_TRY(hipEventRecord(o.ev[0].e, st));
-    if (fused)
-        launch_narrow(s->db->view, sc1, view, w1, s->lnfact.p, (uint32_t)s->lnfact.n, rec, count_buf, st);
-    else if (one_launch)
-        launch_search(s->db->view, sc1, view, w1, s->lnfact.p, (uint32_t)s->lnfact.n, rec, count_buf, st);
-    else {
+    p.later = false;
+    if (!p.fused && !p.one_launch) {
         // With the large-window kernels behind it the preliminary kernel may only MARK the spectra it hands over, one small kernel
         // building their queue in ascending precursor mass (DevWork::queue_later) — where the batch's windows are known to lie
         // within a few tiles (a wide-window / DIA search).  One returning atomic per spectrum on the queue's counter costs
@@ -965,50 +979,124 @@ static int enqueue_compute(SageScorer* s, const DevBatchView& view_in, OutSet& o
         // tile_count8_kernel, the same binary: not understood) — scripts/experiments/r06_lab/RESULTS.md, r8e - r8m.
         // (the line between the two: 16 tiles — C5's widest window, charge 4 of a 12 Da isolation window, holds ~4 tiles' worth of
         // candidates, C4's +-500 Da ~55)
-        bool later = wide && widest <= (16u << s->db->view.tile_shift);
-        if (const char* e = getenv("SAGE_HIP_QUEUE_LATER")) later = wide && atoi(e) != 0;  // (tests and experiments force either way)
-        w1.queue_later = later ? 1u : 0u;
-        launch_prelim(s->db->view, sc1, view, w1, st);
-        if (later) launch_queue(sc1, view, w1, st);
+        p.later = p.wide && rq.widest <= (16u << s->db->view.tile_shift);
+        if (const char* e = getenv("SAGE_HIP_QUEUE_LATER")) p.later = p.wide && atoi(e) != 0;  // (tests and experiments force either way)
+        w1.queue_later = p.later ? 1u : 0u;
     }
-    HIP_TRY(hipGetLastError());  // (a failed launch must not let the kernels downstream of it run on stale records)
-    if (wide) {
-        launch_prelim_tile(s->db->view, sc1, view, w1, st, &side);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!no_timing) HIP_TRY(hipEventRecord(o.ev[1].e, st));
-    if (with_rescore && (wide || !(fused || one_launch))) {  // (behind search_kernel / the fused kernel: only the spectra the large-window kernels assembled)
-        s->last_rescore = rescore_instance_code(sc1, w1, false);
-        HIP_TRY((hipError_t)launch_rescore(s->db->view, sc1, view, w1, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, rec, count_buf, nullptr, st));
-    }
-    if (!no_timing) HIP_TRY(hipEventRecord(o.ev[2].e, st));
-retry_pass:
-    if (o.two_pass && phase != 1) {
-        launch_narrow(s->db->view, sc2, v2, w2, s->lnfact.p, (uint32_t)s->lnfact.n, rec, count_buf, st);
-        HIP_TRY(hipGetLastError());
-        if (wide) {
-            launch_prelim_tile(s->db->view, sc2, v2, w2, st, &side);
-            HIP_TRY(hipGetLastError());
-        }
-        if (wide) {  // (without the large-window kernels the retry pass is ONE launch: no marker inside it)
-            if (!no_timing) HIP_TRY(hipEventRecord(o.ev[3].e, st));
-            HIP_TRY((hipError_t)launch_rescore(s->db->view, sc2, v2, w2, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, rec, count_buf, nullptr, st));
-        }
-        if (!no_timing) HIP_TRY(hipEventRecord(o.ev[4].e, st));
-    }
-    HIP_TRY(hipGetLastError());
-    o.in_flight = true;
+    p.sc1 = p.sc2 = sc;
+    p.sc1.exact = rq.mode == MODE_EXACT ? 1u : 0u;
+    p.sc1.fast_log = p.two_pass ? 1u : 0u;  // (an undecided logarithm is settled by the retry pass: launch_rescore)
+    p.sc2.exact = 1u;
+    p.sc2.fast_log = 0u;
+    o.timed = s->timed;  // (sage_hip_scorer_set_timing_interval)
+    // (RetryOnly is the late launch behind a FirstOnly step: the flag stays set until collect_retry has read the pass's counters)
+    if (passes != Passes::RetryOnly) o.retry_deferred = passes == Passes::FirstOnly && p.two_pass;
     return SAGE_HIP_OK;
 }
 
-// the kernel times of a retry pass: a2 preliminary, r2 rescoring (one figure, a2, where the large-window kernels did not run)
-static int retry_pass_times(const OutSet& o, float& a2, float& r2) {
-    if (o.wide_launched) {
-        HIP_TRY(hipEventElapsedTime(&a2, o.ev[2].e, o.ev[3].e));
-        HIP_TRY(hipEventElapsedTime(&r2, o.ev[3].e, o.ev[4].e));
-    } else {
-        HIP_TRY(hipEventElapsedTime(&a2, o.ev[2].e, o.ev[4].e));
+// The first pass of a planned request on `st`, behind the reset of its counters — nothing here waits for the device.
+// OutSet::launches: what SageTiming::n_launches reports of a pass, counted where the launches are — one for the preliminary (or
+// fused, or search) kernel, four for the large-window path, one for the rescoring kernel; the retry pass alike with five for the
+// large-window path and its rescoring kernel.  A nominal count, as it always was: queue_kernel and the further launches inside
+// launch_prelim_tile (the large-window path is ten launches) are not in it.
+static int enqueue_first_pass(SageScorer* s, const StepPlan& p, OutSet& o, hipStream_t st) {
+    const SideStream side{s->side_stream, s->side_fork.e, s->side_join.e};
+    o.launches[0] = o.launches[1] = 0;
+    // (score_resident's epilogue kernel leaves the counters zeroed for the next step: one command less ahead of the first kernel)
+    if (!o.counters_clean) HIP_TRY(hipMemsetAsync(o.counters.p, 0, 2 * CTR_COUNT * 4, st));
+    o.counters_clean = false;
+    if (o.timed) HIP_TRY(hipEventRecord(o.ev[0].e, st));
+    if (p.fused)
+        launch_narrow(s->db->view, p.sc1, p.view, p.w1, s->lnfact.p, (uint32_t)s->lnfact.n, p.rec, p.count_buf, st);
+    else if (p.one_launch)
+        launch_search(s->db->view, p.sc1, p.view, p.w1, s->lnfact.p, (uint32_t)s->lnfact.n, p.rec, p.count_buf, st);
+    else {
+        launch_prelim(s->db->view, p.sc1, p.view, p.w1, st);
+        if (p.later) launch_queue(p.sc1, p.view, p.w1, st);
     }
+    o.launches[0] += 1;
+    HIP_TRY(hipGetLastError());  // (a failed launch must not let the kernels downstream of it run on stale records)
+    if (p.wide) {
+        launch_prelim_tile(s->db->view, p.sc1, p.view, p.w1, st, &side);
+        o.launches[0] += 4;
+        HIP_TRY(hipGetLastError());
+    }
+    if (o.timed) HIP_TRY(hipEventRecord(o.ev[1].e, st));
+    if (o.with_rescore && (p.wide || !(p.fused || p.one_launch))) {  // (behind search_kernel / the fused kernel: only the spectra the large-window kernels assembled)
+        s->last_rescore = rescore_instance_code(p.sc1, p.w1, false);
+        HIP_TRY((hipError_t)launch_rescore(s->db->view, p.sc1, p.view, p.w1, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, p.rec, p.count_buf, nullptr, st));
+        o.launches[0] += 1;
+    }
+    if (o.timed) HIP_TRY(hipEventRecord(o.ev[2].e, st));
+    return SAGE_HIP_OK;
+}
+
+// The exact retry pass of a planned request (StepPlan::two_pass) on `st`, behind ev[2].
+static int enqueue_retry_pass(SageScorer* s, const StepPlan& p, OutSet& o, hipStream_t st) {
+    const SideStream side{s->side_stream, s->side_fork.e, s->side_join.e};
+    launch_narrow(s->db->view, p.sc2, p.v2, p.w2, s->lnfact.p, (uint32_t)s->lnfact.n, p.rec, p.count_buf, st);
+    o.launches[1] += 1;
+    HIP_TRY(hipGetLastError());
+    if (p.wide) {
+        launch_prelim_tile(s->db->view, p.sc2, p.v2, p.w2, st, &side);
+        o.launches[1] += 4;
+        HIP_TRY(hipGetLastError());
+        // (without the large-window kernels the retry pass is ONE launch: no marker inside it)
+        if (o.timed) HIP_TRY(hipEventRecord(o.ev[3].e, st));
+        HIP_TRY((hipError_t)launch_rescore(s->db->view, p.sc2, p.v2, p.w2, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, p.rec, p.count_buf, nullptr, st));
+        o.launches[1] += 1;
+    }
+    if (o.timed) HIP_TRY(hipEventRecord(o.ev[4].e, st));
+    HIP_TRY(hipGetLastError());
+    return SAGE_HIP_OK;
+}
+
+// Plan a request and enqueue its kernels on its stream: the first pass, and the retry pass behind it unless `passes` leaves it
+// for later.  `plan` (may be null): what was decided, for a caller that launches more kernels on the same working set.
+static int enqueue_step(SageScorer* s, const StepRequest& rq, Passes passes = Passes::Both, StepPlan* plan = nullptr) {
+    StepPlan local;
+    StepPlan& p = plan ? *plan : local;
+    int rc = plan_step(s, rq, passes, p);
+    if (rc != SAGE_HIP_OK) return rc;
+    rc = enqueue_first_pass(s, p, *rq.out, rq.stream);
+    if (rc != SAGE_HIP_OK) return rc;
+    if (p.two_pass && passes == Passes::Both) return enqueue_retry_pass(s, p, *rq.out, rq.stream);
+    HIP_TRY(hipGetLastError());
+    return SAGE_HIP_OK;
+}
+
+// The retry pass that a Passes::FirstOnly request left out, launched after all: the same plan again, the retry list's length put
+// back, the pass.
+static int enqueue_late_retry(SageScorer* s, const StepRequest& rq) {
+    OutSet& o = *rq.out;
+    StepPlan p;
+    const int rc = plan_step(s, rq, Passes::RetryOnly, p);
+    if (rc != SAGE_HIP_OK) return rc;
+    // the retry list's length: the first pass left it in the counter block, the epilogue sent it home and zeroed the block
+    HIP_TRY(hipMemcpyAsync(o.counters.p + CTR_RETRY, o.h_counters + CTR_RETRY, 4, hipMemcpyHostToDevice, rq.stream));
+    o.counters_clean = false;
+    if (o.timed) HIP_TRY(hipEventRecord(o.ev[2].e, rq.stream));
+    return enqueue_retry_pass(s, p, o, rq.stream);
+}
+
+// One pass's share of a step's figures (pass 0: the first, 1: the exact retry pass): its launches as the enqueuing function counted
+// them and, where the launch recorded events, its kernel times — a preliminary, r rescoring (the retry pass: one figure, a, where
+// the large-window kernels did not run).
+static int add_pass(SageScorer* s, const OutSet& o, int pass) {
+    SageTiming& t = s->timing;
+    t.n_launches += o.launches[pass];
+    if (!o.timed) return SAGE_HIP_OK;
+    float a = 0, r = 0;
+    if (pass == 0 || o.wide_launched) {
+        HIP_TRY(hipEventElapsedTime(&a, o.ev[2 * pass].e, o.ev[2 * pass + 1].e));
+        HIP_TRY(hipEventElapsedTime(&r, o.ev[2 * pass + 1].e, o.ev[2 * pass + 2].e));
+    } else {
+        HIP_TRY(hipEventElapsedTime(&a, o.ev[2].e, o.ev[4].e));
+    }
+    t.prelim_ms += a;
+    t.rescore_ms += o.with_rescore ? r : 0.f;
+    t.total_ms += a + (o.with_rescore ? r : 0.f);
+    if (pass) t.retry_ms += a + r;
     return SAGE_HIP_OK;
 }
 // what a pass's overflow counters are refused with
@@ -1023,7 +1111,6 @@ static int list_capacity_exceeded(uint32_t spectra) {
 // counters + timing of a finished batch (its comp_done / down_done event has completed); accumulates into s->timing.
 // *redo_wide: the batch was launched without the large-window kernels and turned out to need them — nothing is accumulated.
 static int collect(SageScorer* s, OutSet& o, bool* arena_overflow, bool* redo_wide = nullptr) {
-    o.in_flight = false;
     const uint32_t* c1 = o.h_counters;
     const uint32_t* c2 = o.h_counters + CTR_COUNT;
     if (!o.wide_launched && c1[CTR_QUEUED]) {
@@ -1033,21 +1120,11 @@ static int collect(SageScorer* s, OutSet& o, bool* arena_overflow, bool* redo_wi
         }
         return fail(SAGE_HIP_ERR_INTERNAL, "spectra queued for the large-window kernels, which were not launched");
     }
-    float a = 0, r = 0, a2 = 0, r2 = 0;
-    if (!o.timed) goto counters;
-    HIP_TRY(hipEventElapsedTime(&a, o.ev[0].e, o.ev[1].e));
-    HIP_TRY(hipEventElapsedTime(&r, o.ev[1].e, o.ev[2].e));
+    if (const int rc = add_pass(s, o, 0)) return rc;
     // (a deferred retry pass has not run: collect_retry adds its share if it does)
     if (o.two_pass && !o.retry_deferred)
-        if (const int rc = retry_pass_times(o, a2, r2)) return rc;
-counters:
+        if (const int rc = add_pass(s, o, 1)) return rc;
     SageTiming& t = s->timing;
-    t.prelim_ms += a + a2;
-    t.rescore_ms += o.with_rescore ? r + r2 : 0.f;
-    t.total_ms += a + a2 + (o.with_rescore ? r + r2 : 0.f);
-    t.retry_ms += a2 + r2;
-    t.n_launches += 1 + (o.wide_launched ? 4 : 0) + (o.with_rescore && (o.wide_launched || !o.fused) ? 1 : 0) +
-                    (o.two_pass && !o.retry_deferred ? 1 + (o.wide_launched ? 5 : 0) : 0);
     t.n_wide += c1[CTR_QUEUED];
     t.arena_entries = std::max(t.arena_entries, std::max(c1[CTR_ARENA_PTR], c2[CTR_ARENA_PTR]));
     t.n_retry += o.two_pass ? c1[CTR_RETRY] : 0;
@@ -1064,21 +1141,12 @@ counters:
     return SAGE_HIP_OK;
 }
 
-// ... of a retry pass that was launched by itself, behind a first pass that has been collected (enqueue_compute: phase 2)
+// ... of a retry pass that was launched by itself, behind a first pass that has been collected (enqueue_late_retry)
 static int collect_retry(SageScorer* s, OutSet& o) {
-    o.in_flight = false;
     o.retry_deferred = false;
     const uint32_t* c2 = o.h_counters + CTR_COUNT;
+    if (const int rc = add_pass(s, o, 1)) return rc;
     SageTiming& t = s->timing;
-    if (o.timed) {
-        float a2 = 0, r2 = 0;
-        if (const int rc = retry_pass_times(o, a2, r2)) return rc;
-        t.prelim_ms += a2;
-        t.rescore_ms += o.with_rescore ? r2 : 0.f;
-        t.total_ms += a2 + (o.with_rescore ? r2 : 0.f);
-        t.retry_ms += a2 + r2;
-    }
-    t.n_launches += 1 + (o.wide_launched ? 5 : 0);
     t.arena_entries = std::max(t.arena_entries, c2[CTR_ARENA_PTR]);
     if (c2[CTR_ARENA_OVERFLOW]) return arena_exhausted(s);
     if (c2[CTR_LIST_OVERFLOW]) return list_capacity_exceeded(c2[CTR_LIST_OVERFLOW]);
@@ -1098,6 +1166,221 @@ static hipError_t wait_for_stream(hipStream_t st) {
     }
 }
 
+// ---- resident steps --------------------------------------------------------------------------------------------------------
+// SAGE_HIP_STEP_TRACE=1: host-side clock of a resident step on stderr (microseconds since the call began, and since the
+// previous call returned) — where the host's share of a small step goes (scripts/experiments/r05_lab/gpu_r5i.sh)
+struct StepTrace {
+    using Clock = std::chrono::steady_clock;
+    const bool on;
+    const Clock::time_point enter = Clock::now();
+    double enq = 0, wait = 0;  // the step's last command enqueued, its kernels done
+    explicit StepTrace(bool on_) : on(on_) {}
+    double us() const { return std::chrono::duration<double, std::micro>(Clock::now() - enter).count(); }
+    ~StepTrace() {
+        if (!on) return;
+        static thread_local Clock::time_point prev_exit{};
+        const auto now = Clock::now();
+        fprintf(stderr, "[sage_hip] step: %.1f us since the previous call returned; enqueued at %.1f, kernels done at %.1f, returns at %.1f\n",
+                std::chrono::duration<double, std::micro>(enter - prev_exit).count(), enq, wait,
+                std::chrono::duration<double, std::micro>(now - enter).count());
+        prev_exit = now;
+    }
+};
+
+// the stream of part `wy` of a resident step (and of lane `wy` of the streaming pipeline)
+static hipStream_t part_stream(const SageScorer* s, uint32_t wy) { return wy ? s->way_stream[wy - 1] : s->stream; }
+
+// Wait for the streams of parts [0, k), the first parts first (they were launched first); every one of them is waited for
+// whatever the others report.
+static hipError_t wait_for_parts(const SageScorer* s, uint32_t k) {
+    hipError_t first = hipSuccess;
+    for (uint32_t wy = 0; wy < k; wy++) {
+        const hipError_t e = wait_for_stream(part_stream(s, wy));
+        if (first == hipSuccess) first = e;
+    }
+    return first;
+}
+
+// Part `wy` of `ways` of a resident batch as a request: its slice of the launch schedule (consecutive precursor masses), its start
+// in the arrays the parts share, its stream and its OutSet.  What differs between the passes is the caller's to fill in.
+static StepRequest part_request(SageScorer* s, const SageDeviceBatch* b, uint32_t wy, uint32_t ways, SageFeature* rec) {
+    const uint32_t start = (uint32_t)((uint64_t)b->n * wy / ways), end = (uint32_t)((uint64_t)b->n * (wy + 1) / ways);
+    StepRequest rq(b->view, s->outs[wy], part_stream(s, wy));
+    rq.view.order += start;
+    if (rq.view.sched) rq.view.sched += (size_t)rq.view.sched_stride * start;
+    rq.view.n = end - start;
+    rq.list_off = start;
+    rq.rec = rec;
+    return rq;
+}
+
+// A part's PSM counts — `counts`, unless the kernels stored them home already — and its counters in one launch, straight into the
+// page-locked destinations
+static int launch_part_epilogue(const StepRequest& part, const uint32_t* counts, bool counts_home, uint32_t* count_view, const uint32_t* order) {
+    EpilogueParts parts{};
+    parts.n = 1;
+    parts.src[0] = part.out->counters.p;
+    parts.dst[0] = part.out->h_counters_view;
+    launch_epilogue(counts, counts_home ? 0u : part.view.n, count_view, order, parts, part.stream);
+    HIP_TRY(hipGetLastError());
+    return SAGE_HIP_OK;
+}
+
+// The retry pass after all, behind a step whose parts left it out and have been collected: the parts that have something to
+// retry, each on its stream, and a second (short) wait.
+static int launch_deferred_retries(SageScorer* s, const SageDeviceBatch* b, uint32_t ways, SageFeature* rec, uint32_t* count_view) {
+    uint32_t launched = 0;
+    for (uint32_t wy = 0; wy < ways; wy++) {
+        if (s->outs[wy].h_counters[CTR_RETRY] == 0) {
+            s->outs[wy].retry_deferred = false;
+            continue;
+        }
+        StepRequest part = part_request(s, b, wy, ways, rec);
+        part.wide = false;
+        part.count_buf = ways > 1 ? count_view : s->outs[0].out_count.p;
+        int rc = enqueue_late_retry(s, part);
+        if (rc != SAGE_HIP_OK) {
+            (void)wait_for_parts(s, ways);
+            return rc;
+        }
+        rc = launch_part_epilogue(part, s->outs[0].out_count.p, part.count_buf == count_view, count_view, nullptr);
+        if (rc != SAGE_HIP_OK) return rc;
+        launched++;
+    }
+    if (!launched) return SAGE_HIP_OK;
+    HIP_TRY(wait_for_parts(s, ways));
+    for (uint32_t wy = 0; wy < ways; wy++) {
+        OutSet& ow = s->outs[wy];
+        ow.counters_clean = true;
+        if (!ow.retry_deferred) continue;
+        const int rc = collect_retry(s, ow);
+        if (rc != SAGE_HIP_OK) return rc;
+    }
+    return SAGE_HIP_OK;
+}
+
+// What a finished step of `ways` parts reports of its time: total_ms is the first part's start to the LATEST end.
+static int roll_up_timing(SageScorer* s, uint32_t ways) {
+    if (s->timed) {
+        float wall = 0.f;
+        for (uint32_t wy = 0; wy < ways; wy++) {
+            float w1 = 0.f;
+            HIP_TRY(hipEventElapsedTime(&w1, s->way_begin.e, s->way_end[wy].e));
+            wall = std::max(wall, w1);
+        }
+        s->timing.total_ms = wall;  // (prelim_ms / rescore_ms: summed over the parts, which overlap in time)
+        s->kept_prelim_ms = s->timing.prelim_ms;
+        s->kept_rescore_ms = s->timing.rescore_ms;
+        s->kept_retry_ms = s->timing.retry_ms;
+    } else {  // (an untimed step reports the kernel times of the last timed one; total_ms 0 says so)
+        s->timing.prelim_ms = s->kept_prelim_ms;
+        s->timing.rescore_ms = s->kept_rescore_ms;
+        s->timing.retry_ms = s->kept_retry_ms;
+        s->timing.total_ms = 0.f;
+    }
+    s->timing.n_ways = ways;
+    return SAGE_HIP_OK;
+}
+
+// One attempt at a resident step: kernels, record download, ONE host synchronisation (a second, short one where a deferred
+// retry pass is launched after all).  *needs_wide: the batch was launched without the large-window kernels and turned out to
+// need them — nothing was accumulated, and no OutSet is left waiting for a retry pass.
+static int resident_attempt(SageScorer* s, SageDeviceBatch* b, SageFeature* out, uint32_t* out_count, SageFeature* direct, StepTrace& trace,
+                            bool* needs_wide) {
+    *needs_wide = false;
+    OutSet& o = s->outs[0];
+    // A narrow-search batch in `ways` parts of the launch schedule (consecutive precursor masses), each on its own stream:
+    // a part's kernels fill the GPU while another part's kernel starts cold, drains, or waits on the few wavefronts of its
+    // retry pass.  Large-window batches go as one (their steps are long; the parts would fight over the candidate arena).
+    // Default (no SAGE_HIP_WAYS): two parts for batches up to 196 608 spectra — the shards of a rank of a 3- to 8-GPU
+    // strong-scaling run — where a good part of the step is cold starts, tails and the retry pass's handful of wavefronts (C3,
+    // 62 500 spectra: -6 %; 125 000 .. 170 000 with the heaviest-first schedule of round 6: -1 .. -1.6 %); one part above, where
+    // the kernels' durations are what the roofline is held against.
+    const uint32_t want = s->ways ? s->ways : (b->n <= 196608u ? 2u : 1u);
+    const uint32_t ways = (!b->maybe_wide && !s->exact_always && b->n >= 8192u * want) ? want : 1u;
+    // (sized for the whole batch: the parts of a step index the working set by spectrum and share outs[0]'s count buffer and,
+    // if any, its record buffer)
+    int rc = ensure_work(s, b->n, 0, b->maybe_wide || s->exact_always, s->stream);
+    if (rc != SAGE_HIP_OK) return rc;
+    rc = ensure_out(s, o, b->n, direct == nullptr);
+    if (rc != SAGE_HIP_OK) return rc;
+    SageFeature* const rec = direct ? direct : o.features.p;
+    uint32_t* const count_view = s->zero_copy && b->n ? (uint32_t*)device_view_cached(out_count) : nullptr;
+    const bool epilogue = count_view != nullptr;  // (page-locked count array: the small results go home in one launch)
+    // The exact retry pass (spectra with equal hyperscores at a reported rank that the rescoring kernel could not settle itself,
+    // undecided logarithms) is one more launch per part behind the rescoring kernel — ~10 us of a step's tail for a list that
+    // is empty in most searches (C3, C3T: 0 of 500 000 spectra).  A narrow-search step whose predecessor had nothing to retry
+    // does not launch it: the first pass's counters come home with the epilogue, and only if they name retries is the retry
+    // pass launched then, behind a second (short) wait.  The first step of a scorer, and any step after one that did retry,
+    // launches it unconditionally, as before.
+    const bool defer_retry = epilogue && direct && !b->maybe_wide && !s->exact_always && !s->retry_likely && !s->fused && !s->one_launch;
+    // No events between the parts' streams: every entry point of a scorer returns with its streams idle, so a part's
+    // stream has nothing to wait for at the start (round 4 forked the parts off the first stream with an event: the second
+    // part's first kernel started ~30 us after the first's), and at the end every part sends ITS counts and counters home
+    // with its own epilogue launch, back to back with its last kernel, and the host waits for each stream in turn (round 4
+    // joined the parts on one stream for a single epilogue: ~20 us of cross-stream wake-up behind the last kernel of every
+    // step; profiles/r05_small_step_timeline.txt).
+    for (uint32_t wy = 0; wy < ways; wy++) {
+        StepRequest part = part_request(s, b, wy, ways, rec);
+        if (wy == 0 && s->timed) HIP_TRY(hipEventRecord(s->way_begin.e, part.stream));  // (SageTiming::total_ms: first part's start to last part's end)
+        // the PSM counts: a step in parts has its kernels store them straight into the caller's page-locked array, as they do
+        // the records (4-byte stores spread over the kernels' lifetime cost nothing there; a part's counts are scattered over
+        // the array — its spectra are a range of the launch SCHEDULE — and gathering them at the end of the step costs 33 us of
+        // scattered stores across the link, joining the parts for one contiguous copy 20 us of cross-stream wake-up:
+        // profiles/r05_small_step_timeline.txt); a step in one part keeps them on the device and sends them home in one
+        // contiguous run behind its last kernel (round 13 had the kernels of a one-part step of 500 000 spectra store them home
+        // too, to save that run's ~35 us: rescore_kernel took 0.2 ms longer — DESIGN.md 10)
+        part.count_buf = (epilogue && ways > 1 && direct) ? count_view : o.out_count.p;
+        part.mode = s->exact_always ? MODE_EXACT : MODE_SCORE;
+        part.wide = b->maybe_wide;
+        part.widest = b->widest;
+        rc = enqueue_step(s, part, defer_retry ? Passes::FirstOnly : Passes::Both);
+        if (rc != SAGE_HIP_OK) {
+            (void)wait_for_parts(s, wy);
+            return rc;
+        }
+        if (epilogue) {  // (counts_home: the kernels stored the counts there already)
+            rc = launch_part_epilogue(part, o.out_count.p, part.count_buf == count_view, count_view, ways > 1 ? part.view.order : nullptr);
+            if (rc != SAGE_HIP_OK) return rc;
+        } else {
+            HIP_TRY(hipMemcpyAsync(part.out->h_counters, part.out->counters.p, 2 * CTR_COUNT * 4, hipMemcpyDeviceToHost, part.stream));
+        }
+        // (every part's end: the parts run side by side and any of them may finish last — SageTiming::total_ms is the first
+        // part's start to the LATEST end; round 5 recorded the last part's only and under-reported a step whose first part
+        // outlasted it: ADVICE r05)
+        if (s->timed) HIP_TRY(hipEventRecord(s->way_end[wy].e, part.stream));
+    }
+    const hipStream_t fin = part_stream(s, ways - 1);
+    if (!epilogue && b->n) {
+        HIP_TRY(wait_for_parts(s, ways - 1));
+        HIP_TRY(hipMemcpyAsync(out_count, o.out_count.p, (size_t)b->n * 4, hipMemcpyDeviceToHost, fin));
+    }
+    if (b->n && !direct) {
+        HIP_TRY(wait_for_parts(s, ways - 1));
+        HIP_TRY(hipMemcpyAsync(out, o.features.p, (size_t)b->n * s->params.report_psms * sizeof(SageFeature), hipMemcpyDeviceToHost, fin));
+    }
+    trace.enq = trace.us();
+    HIP_TRY(wait_for_parts(s, ways));
+    trace.wait = trace.us();
+    for (uint32_t wy = 0; wy < ways; wy++) {
+        if (epilogue) s->outs[wy].counters_clean = true;  // (the part's epilogue kernel zeroed them)
+        bool redo = false;
+        rc = collect(s, s->outs[wy], nullptr, &redo);
+        if (rc != SAGE_HIP_OK) return rc;
+        *needs_wide = *needs_wide || redo;
+    }
+    if (*needs_wide) {
+        for (uint32_t wy = 0; wy < ways; wy++) s->outs[wy].retry_deferred = false;
+        return SAGE_HIP_OK;
+    }
+    if (defer_retry) {
+        rc = launch_deferred_retries(s, b, ways, rec, count_view);
+        if (rc != SAGE_HIP_OK) return rc;
+    }
+    s->retry_likely = s->timing.n_retry != 0;
+    return roll_up_timing(s, ways);
+}
+
 // score a resident batch on the compute stream: kernels, record download, ONE host synchronisation.  Page-locked result
 // arrays receive the records straight from the kernels (the stores cross PCIe while the other wavefronts compute: no download
 // phase); pageable ones through the device buffer and a copy.
@@ -1105,198 +1388,23 @@ static int score_resident_locked(SageScorer* s, SageDeviceBatch* b, SageFeature*
     if (b->device != s->db->device) return fail(SAGE_HIP_ERR_INVALID, "batch and scorer live on different devices");
     HIP_TRY(hipSetDevice(s->db->device));
     reset_timing(s);
-    // SAGE_HIP_STEP_TRACE=1: host-side clock of a resident step on stderr (microseconds since the call began, and since the
-    // previous call returned) — where the host's share of a small step goes (scripts/experiments/r05_lab/gpu_r5i.sh)
     static const bool step_trace = getenv("SAGE_HIP_STEP_TRACE") != nullptr;
-    static thread_local std::chrono::steady_clock::time_point t_prev_exit{};
-    const auto t_enter = std::chrono::steady_clock::now();
-    double t_enq = 0, t_wait = 0;
-    auto us_since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
-    struct TraceOut {
-        bool on;
-        const std::chrono::steady_clock::time_point* enter;
-        std::chrono::steady_clock::time_point* prev;
-        const double *enq, *wait;
-        ~TraceOut() {
-            if (!on) return;
-            const auto now = std::chrono::steady_clock::now();
-            fprintf(stderr, "[sage_hip] step: %.1f us since the previous call returned; enqueued at %.1f, kernels done at %.1f, returns at %.1f\n",
-                    std::chrono::duration<double, std::micro>(*enter - *prev).count(), *enq, *wait,
-                    std::chrono::duration<double, std::micro>(now - *enter).count());
-            *prev = now;
-        }
-    } trace_out{step_trace, &t_enter, &t_prev_exit, &t_enq, &t_wait};
+    StepTrace trace(step_trace);
     s->timed = s->timing_every != 0 && (s->timing_calls++ % s->timing_every) == 0;
     struct Restore {  // (the other entry points — streaming, quick_score, initial_hits — always record their events)
         SageScorer* s;
         ~Restore() { s->timed = true; }
     } restore{s};
-    OutSet& o = s->outs[0];
-    SageFeature* direct = s->zero_copy && b->n ? (SageFeature*)device_view_cached(out) : nullptr;
-    const size_t rec_bytes = (size_t)b->n * s->params.report_psms * sizeof(SageFeature);
-    for (int attempt = 0;; attempt++) {
-        // A narrow-search batch in `ways` parts of the launch schedule (consecutive precursor masses), each on its own stream:
-        // a part's kernels fill the GPU while another part's kernel starts cold, drains, or waits on the few wavefronts of its
-        // retry pass.  Large-window batches go as one (their steps are long; the parts would fight over the candidate arena).
-        // Default (no SAGE_HIP_WAYS): two parts for batches up to 196 608 spectra — the shards of a rank of a 3- to 8-GPU
-        // strong-scaling run — where a good part of the step is cold starts, tails and the retry pass's handful of wavefronts (C3,
-        // 62 500 spectra: -6 %; 125 000 .. 170 000 with the heaviest-first schedule of round 6: -1 .. -1.6 %); one part above, where
-        // the kernels' durations are what the roofline is held against.
-        const uint32_t want = s->ways ? s->ways : (b->n <= 196608u ? 2u : 1u);
-        const uint32_t ways = (!b->maybe_wide && !s->exact_always && b->n >= 8192u * want) ? want : 1u;
-        // (sized for the whole batch: the parts of a step index the working set by spectrum and share outs[0]'s count buffer and,
-        // if any, its record buffer)
-        int rc = ensure_work(s, b->n, 0, b->maybe_wide || s->exact_always, s->stream);
-        if (rc != SAGE_HIP_OK) return rc;
-        rc = ensure_out(s, o, b->n, direct == nullptr);
-        if (rc != SAGE_HIP_OK) return rc;
-        SageFeature* const rec = direct ? direct : o.features.p;
-        uint32_t* const count_view = s->zero_copy && b->n ? (uint32_t*)device_view_cached(out_count) : nullptr;
-        const bool epilogue = count_view != nullptr;  // (page-locked count array: the small results go home in one launch)
-        bool reset_done = false;
-        // The exact retry pass (spectra with equal hyperscores at a reported rank that the rescoring kernel could not settle itself,
-        // undecided logarithms) is one more launch per part behind the rescoring kernel — ~10 us of a step's tail for a list that
-        // is empty in most searches (C3, C3T: 0 of 500 000 spectra).  A narrow-search step whose predecessor had nothing to retry
-        // does not launch it: the first pass's counters come home with the epilogue, and only if they name retries is the retry
-        // pass launched then, behind a second (short) wait.  The first step of a scorer, and any step after one that did retry,
-        // launches it unconditionally, as before.
-        const bool defer_retry = epilogue && direct && !b->maybe_wide && !s->exact_always && !s->retry_likely && !s->fused && !s->one_launch;
-        // No events between the parts' streams: every entry point of a scorer returns with its streams idle, so a part's
-        // stream has nothing to wait for at the start (round 4 forked the parts off the first stream with an event: the second
-        // part's first kernel started ~30 us after the first's), and at the end every part sends ITS counts and counters home
-        // with its own epilogue launch, back to back with its last kernel, and the host waits for each stream in turn (round 4
-        // joined the parts on one stream for a single epilogue: ~20 us of cross-stream wake-up behind the last kernel of every
-        // step; profiles/r05_small_step_timeline.txt).
-        for (uint32_t wy = 0; wy < ways; wy++) {
-            const uint32_t start = (uint32_t)((uint64_t)b->n * wy / ways), end = (uint32_t)((uint64_t)b->n * (wy + 1) / ways);
-            hipStream_t st = wy ? s->way_stream[wy - 1] : s->stream;
-            DevBatchView v = b->view;
-            v.order += start;
-            if (v.sched) v.sched += (size_t)v.sched_stride * start;
-            v.n = end - start;
-            OutSet& ow = s->outs[wy];
-            if (wy == 0 && s->timed) HIP_TRY(hipEventRecord(s->way_begin.e, st));  // (SageTiming::total_ms: first part's start to last part's end)
-            // the PSM counts: a step in parts has its kernels store them straight into the caller's page-locked array, as they do
-            // the records (4-byte stores spread over the kernels' lifetime cost nothing there; a part's counts are scattered over
-            // the array — its spectra are a range of the launch SCHEDULE — and gathering them at the end of the step costs 33 us of
-            // scattered stores across the link, joining the parts for one contiguous copy 20 us of cross-stream wake-up:
-            // profiles/r05_small_step_timeline.txt); a step in one part keeps them on the device and sends them home in one
-            // contiguous run behind its last kernel (round 13 had the kernels of a one-part step of 500 000 spectra store them home
-            // too, to save that run's ~35 us: rescore_kernel took 0.2 ms longer — DESIGN.md 10)
-            uint32_t* const counts_to = (epilogue && ways > 1 && direct) ? count_view : o.out_count.p;
-            rc = enqueue_compute(s, v, ow, true, s->exact_always ? MODE_EXACT : MODE_SCORE, st, rec, b->maybe_wide, start, counts_to, 0,
-                                 defer_retry ? 1 : 0, b->widest);
-            if (rc != SAGE_HIP_OK) {
-                for (uint32_t k = 0; k < wy; k++) (void)hipStreamSynchronize(k ? s->way_stream[k - 1] : s->stream);
-                return rc;
-            }
-            if (epilogue) {  // this part's PSM counts and counters in one launch, straight into the page-locked destinations
-                EpilogueParts parts{};
-                parts.n = 1;
-                parts.src[0] = ow.counters.p;
-                parts.dst[0] = ow.h_counters_view;
-                const bool counts_home = counts_to == count_view;  // (the kernels stored them there already)
-                launch_epilogue(o.out_count.p, counts_home ? 0u : v.n, count_view, ways > 1 ? v.order : nullptr, parts, st);
-                HIP_TRY(hipGetLastError());
-            } else {
-                HIP_TRY(hipMemcpyAsync(ow.h_counters, ow.counters.p, 2 * CTR_COUNT * 4, hipMemcpyDeviceToHost, st));
-            }
-            // (every part's end: the parts run side by side and any of them may finish last — SageTiming::total_ms is the first
-            // part's start to the LATEST end; round 5 recorded the last part's only and under-reported a step whose first part
-            // outlasted it: ADVICE r05)
-            if (s->timed) HIP_TRY(hipEventRecord(s->way_end[wy].e, st));
-        }
-        hipStream_t fin = ways > 1 ? s->way_stream[ways - 2] : s->stream;
-        if (epilogue) {
-            reset_done = true;
-        } else if (b->n) {
-            for (uint32_t wy = 0; wy + 1 < ways; wy++) HIP_TRY(wait_for_stream(wy ? s->way_stream[wy - 1] : s->stream));
-            HIP_TRY(hipMemcpyAsync(out_count, o.out_count.p, (size_t)b->n * 4, hipMemcpyDeviceToHost, fin));
-        }
-        if (b->n && !direct) {
-            for (uint32_t wy = 0; wy + 1 < ways; wy++) HIP_TRY(wait_for_stream(wy ? s->way_stream[wy - 1] : s->stream));
-            HIP_TRY(hipMemcpyAsync(out, o.features.p, rec_bytes, hipMemcpyDeviceToHost, fin));
-        }
-        t_enq = us_since(t_enter);
-        // the first parts first (they were launched first), the last one at the end
-        for (uint32_t wy = 0; wy < ways; wy++) HIP_TRY(wait_for_stream(wy ? s->way_stream[wy - 1] : s->stream));
-        t_wait = us_since(t_enter);
-        if (reset_done)
-            for (uint32_t wy = 0; wy < ways; wy++) s->outs[wy].counters_clean = true;
-        bool redo = false;
-        for (uint32_t wy = 0; wy < ways; wy++) {
-            bool r = false;
-            rc = collect(s, s->outs[wy], nullptr, &r);
-            if (rc != SAGE_HIP_OK) return rc;
-            redo = redo || r;
-        }
-        if (!redo && defer_retry) {
-            bool any = false;
-            for (uint32_t wy = 0; wy < ways; wy++) any = any || s->outs[wy].h_counters[CTR_RETRY] != 0;
-            if (any) {  // the retry pass after all: the parts that have something to retry, each on its stream
-                for (uint32_t wy = 0; wy < ways; wy++) {
-                    OutSet& ow = s->outs[wy];
-                    if (ow.h_counters[CTR_RETRY] == 0) {
-                        ow.retry_deferred = false;
-                        continue;
-                    }
-                    const uint32_t start = (uint32_t)((uint64_t)b->n * wy / ways), end = (uint32_t)((uint64_t)b->n * (wy + 1) / ways);
-                    hipStream_t st = wy ? s->way_stream[wy - 1] : s->stream;
-                    DevBatchView v = b->view;
-                    v.order += start;
-                    if (v.sched) v.sched += (size_t)v.sched_stride * start;
-                    v.n = end - start;
-                    uint32_t* const counts_to = (ways > 1) ? count_view : o.out_count.p;
-                    rc = enqueue_compute(s, v, ow, true, MODE_SCORE, st, rec, false, start, counts_to, 0, 2);
-                    if (rc != SAGE_HIP_OK) {
-                        for (uint32_t k = 0; k < ways; k++) (void)hipStreamSynchronize(k ? s->way_stream[k - 1] : s->stream);
-                        return rc;
-                    }
-                    EpilogueParts parts{};
-                    parts.n = 1;
-                    parts.src[0] = ow.counters.p;
-                    parts.dst[0] = ow.h_counters_view;
-                    launch_epilogue(o.out_count.p, counts_to == count_view ? 0u : v.n, count_view, nullptr, parts, st);
-                    HIP_TRY(hipGetLastError());
-                }
-                for (uint32_t wy = 0; wy < ways; wy++) HIP_TRY(wait_for_stream(wy ? s->way_stream[wy - 1] : s->stream));
-                for (uint32_t wy = 0; wy < ways; wy++) {
-                    OutSet& ow = s->outs[wy];
-                    ow.counters_clean = true;
-                    if (!ow.retry_deferred) continue;
-                    rc = collect_retry(s, ow);
-                    if (rc != SAGE_HIP_OK) return rc;
-                }
-            } else {
-                for (uint32_t wy = 0; wy < ways; wy++) s->outs[wy].retry_deferred = false;
-            }
-        }
-        if (!redo) {
-            s->retry_likely = s->timing.n_retry != 0;
-            if (s->timed) {
-                float wall = 0.f;
-                for (uint32_t wy = 0; wy < ways; wy++) {
-                    float w1 = 0.f;
-                    HIP_TRY(hipEventElapsedTime(&w1, s->way_begin.e, s->way_end[wy].e));
-                    wall = std::max(wall, w1);
-                }
-                s->timing.total_ms = wall;  // (prelim_ms / rescore_ms: summed over the parts, which overlap in time)
-                s->kept_prelim_ms = s->timing.prelim_ms;
-                s->kept_rescore_ms = s->timing.rescore_ms;
-                s->kept_retry_ms = s->timing.retry_ms;
-            } else {  // (an untimed step reports the kernel times of the last timed one; total_ms 0 says so)
-                s->timing.prelim_ms = s->kept_prelim_ms;
-                s->timing.rescore_ms = s->kept_rescore_ms;
-                s->timing.retry_ms = s->kept_retry_ms;
-                s->timing.total_ms = 0.f;
-            }
-            s->timing.n_ways = ways;
-            return SAGE_HIP_OK;
-        }
-        if (attempt) return fail(SAGE_HIP_ERR_INTERNAL, "large-window queue not drained");
-        reset_timing(s);
-        b->maybe_wide = true;  // (and stays so: the batch holds large windows after all)
-    }
+    SageFeature* const direct = s->zero_copy && b->n ? (SageFeature*)device_view_cached(out) : nullptr;
+    bool needs_wide = false;
+    int rc = resident_attempt(s, b, out, out_count, direct, trace, &needs_wide);
+    if (rc != SAGE_HIP_OK || !needs_wide) return rc;
+    // a wrong guess: once more, in one part and with the large-window kernels
+    reset_timing(s);
+    b->maybe_wide = true;  // (and stays so: the batch holds large windows after all)
+    rc = resident_attempt(s, b, out, out_count, direct, trace, &needs_wide);
+    if (rc == SAGE_HIP_OK && needs_wide) return fail(SAGE_HIP_ERR_INTERNAL, "large-window queue not drained");
+    return rc;
 }
 
 int sage_hip_score_resident(SageScorer* s, SageDeviceBatch* b, SageFeature* out, uint32_t* out_count) {
@@ -1337,10 +1445,9 @@ static int score_range(SageScorer* s, const SageSpectrumBatch* b, uint32_t r0, u
     // an error with chunks still in flight: nothing may keep writing into the caller's arrays after the call has returned
     auto bail = [&](int rc) -> int {
         (void)hipStreamSynchronize(s->up_stream);
-        (void)hipStreamSynchronize(s->stream);
-        (void)hipStreamSynchronize(s->way_stream[0]);
+        (void)hipStreamSynchronize(part_stream(s, 0));
+        (void)hipStreamSynchronize(part_stream(s, 1));
         (void)hipStreamSynchronize(s->down_stream);
-        for (OutSet& o : s->outs) o.in_flight = false;
         return rc;
     };
 #define HIP_TRY_BAIL(expr)                                                                  \
@@ -1357,9 +1464,14 @@ static int score_range(SageScorer* s, const SageSpectrumBatch* b, uint32_t r0, u
         SageDeviceBatch& in = s->slots[slot];
         OutSet& o = s->outs[slot];
         const int lane = lane_of(slot, wide);
-        hipStream_t cs = lane ? s->way_stream[0] : s->stream;
+        hipStream_t cs = part_stream(s, (uint32_t)lane);
         HIP_TRY_BAIL(hipStreamWaitEvent(cs, in.up_done.e, 0));
-        int rc = enqueue_compute(s, in.view, o, true, mode, cs, direct ? direct + (size_t)c0 * rp : nullptr, wide, 0, nullptr, lane);
+        StepRequest rq(in.view, o, cs);
+        rq.mode = mode;
+        rq.rec = direct ? direct + (size_t)c0 * rp : nullptr;
+        rq.wide = wide;
+        rq.lane = lane;
+        int rc = enqueue_step(s, rq);
         if (rc != SAGE_HIP_OK) return bail(rc);
         HIP_TRY_BAIL(hipEventRecord(o.comp_done.e, cs));
         // the next upload into this slot (chunk k + 4) is enqueued only after finish(slot) has waited for this chunk's
@@ -1457,7 +1569,6 @@ static int score_batch(SageScorer* s, const SageSpectrumBatch* b, const uint8_t*
     reset_timing(s);
     const uint32_t n = b->n_spectra;
     if (n == 0) return SAGE_HIP_OK;
-    const auto t_call = std::chrono::steady_clock::now();
     const bool peaks_locked = is_page_locked(b->masses) && is_page_locked(b->intensities);
     // The window estimate (1 024 sampled spectra x two searches over the peptide masses: ~0.5 ms of cache misses on a 4.75 M
     // peptide list) runs on a helper thread while this one stages the first chunk and enqueues its upload, which need neither
@@ -1468,7 +1579,6 @@ static int score_batch(SageScorer* s, const SageSpectrumBatch* b, const uint8_t*
     WindowEstimate est{};
     est.probe = 1;
     est.maybe_wide = false;
-    (void)t_call;
     std::vector<std::pair<uint32_t, uint32_t>> todo, next;
     rc = score_range(s, b, 0, n, out, out_count, s->chunk, peaks_locked, est, todo, &pending);
     if (pending.valid()) est = pending.get();  // (score_range left before its first chunk: an error)
@@ -1498,16 +1608,16 @@ int sage_hip_quick_score_resident(SageScorer* s, SageDeviceBatch* b, int prefilt
     HIP_TRY(hipSetDevice(s->db->device));
     reset_timing(s);
     OutSet& o = s->outs[0];
-    int rc = enqueue_compute(s, b->view, o, false, MODE_FAST, s->stream);  // Scorer::initial_hits
+    StepRequest rq(b->view, o, s->stream);
+    rq.mode = MODE_FAST;  // Scorer::initial_hits
+    rq.with_rescore = false;
+    StepPlan plan;
+    int rc = enqueue_step(s, rq, Passes::Both, &plan);
     if (rc != SAGE_HIP_OK) return rc;
     const uint64_t np = s->db->view.np;
     HIP_TRY(s->keep.reserve(np));
     HIP_TRY(hipMemsetAsync(s->keep.p, 0, std::max<uint64_t>(np, 1), s->stream));
-    DevWork w = make_work(s, o, 0);
-    if (s->ws.hugebuf.p && o.huge) {  // (enqueue_compute above decided: the wide-list kernels' arrays live in the global workspace)
-        w.hugebuf = s->ws.hugebuf.p;
-        w.huge_stride = (uint32_t)huge_stride_bytes(s->dev);
-    }
+    const DevWork& w = plan.w1;  // (the lists the first pass just filled, in the global workspace where the plan put them)
     if (prefilter_low_memory) {
         s->last_rescore = rescore_instance_code(s->dev, w, true);
         HIP_TRY((hipError_t)launch_rescore(s->db->view, s->dev, b->view, w, s->lnfact.p, (uint32_t)s->lnfact.n, s->db->max_ions, o.features.p,
@@ -1534,7 +1644,10 @@ int sage_hip_initial_hits(SageScorer* s, SageDeviceBatch* b, uint64_t* packed, u
     HIP_TRY(hipSetDevice(s->db->device));
     reset_timing(s);
     OutSet& o = s->outs[0];
-    int rc = enqueue_compute(s, b->view, o, false, MODE_EXACT, s->stream);  // the reference's heap layouts
+    StepRequest rq(b->view, o, s->stream);
+    rq.mode = MODE_EXACT;  // the reference's heap layouts
+    rq.with_rescore = false;
+    int rc = enqueue_step(s, rq);
     if (rc != SAGE_HIP_OK) return rc;
     HIP_TRY(hipMemcpyAsync(o.h_counters, o.counters.p, 2 * CTR_COUNT * 4, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));

@@ -139,13 +139,11 @@ struct OutSet {
     Pinned h_out;                    // landing block for the records when the caller's arrays are pageable
     Event ev[5];                     // start, prelim 1, rescore 1, prelim 2, rescore 2
     Event comp_done, down_done;
-    bool in_flight = false, two_pass = false, with_rescore = false;
-    bool fused = false;          // the narrow spectra were scored by the fused kernel (ev[0] -> ev[1])
+    bool two_pass = false, with_rescore = false;
     bool wide_launched = true;   // the large-window kernels ran behind it (else: the batch was expected to hold narrow windows only)
     bool timed = true;           // ev[] were recorded for this launch (SageScorer::timing_every)
-    bool retry_deferred = false; // two_pass, but the retry pass has not been launched (score_resident_locked: phase 1)
-    bool huge = false;           // this launch's wide-list kernels kept their lists in WorkSet::hugebuf
-    uint32_t n = 0;
+    bool retry_deferred = false; // two_pass, but the retry pass has not been launched (resident steps: Passes::FirstOnly)
+    uint32_t launches[2] = {0, 0};  // what each pass adds to SageTiming::n_launches, counted as it is enqueued (enqueue_first_pass)
     ~OutSet() {
         if (h_counters) (void)hipHostFree(h_counters);
     }
@@ -219,10 +217,10 @@ struct SageScorer {
     Event side_fork, side_join;
     // a resident narrow-search step in `ways` parts, each with its own stream (part 0: `stream`): the parts' kernels overlap each
     // other's cold starts, tails and retry chains (what two scorer handles on two host threads get, inside one call)
-    uint32_t ways = 0;               // SAGE_HIP_WAYS=1..4; 0: by batch size (score_resident_locked).  Measured on C3: two parts
+    uint32_t ways = 0;               // SAGE_HIP_WAYS=1..4; 0: by batch size (resident_attempt).  Measured on C3: two parts
                                      // -1 % wall at 500 000 spectra, -6 % at 62 500, nothing more with three or four
     hipStream_t way_stream[3] = {nullptr, nullptr, nullptr};
-    Event way_fork, way_join[3], way_begin, way_end[4];  // (way_end[p]: behind the last command of part p)
+    Event way_begin, way_end[4];  // (way_end[p]: behind the last command of part p)
     DevBuf<uint32_t> win_max;   // exact_window_check's result word
     bool retry_likely = true;   // the last resident step had spectra to retry (or there was none yet): the next one launches its
                                 // retry pass unconditionally
@@ -255,7 +253,7 @@ struct SageScorer {
     bool fast_ties = true;      // one reported PSM, no chimera: ties at the top settled by rescore_kernel from stored window counts
                                 // (SAGE_HIP_NO_FAST_TIES=1: every tie through the exact retry pass, as in round 3)
     uint32_t cnt_stride = 0;    // words per spectrum of WorkSet::cnt_store
-    bool hand_rows = true;      // the narrow first pass hands its lists over in schedule order (DevWork::hand) where enqueue_compute
+    bool hand_rows = true;      // the narrow first pass hands its lists over in schedule order (DevWork::hand) where plan_step
                                 // allows it (SAGE_HIP_DEBUG_FLAGS=131072, read at scorer creation: always by spectrum)
     bool last_hand = false;     // ... and the last first pass enqueued did (sage_hip_debug_handover_route)
     uint32_t last_rescore = RESCORE_INST_NONE;  // the rescoring instance the last first pass (or quick_score) launched (sage_hip_debug_rescore_instance)

@@ -30,7 +30,7 @@ CONFIGS = {
     "second": ScorerParams(report_psms=3, precursor_tol=Tolerance("da", -200.0, 200.0)),
 }
 # batches scored under each configuration
-BATCHES_OF = {"main": ("R", "Q", "Q2", "E", "S1", "S65", "BIG", "BIGQ"), "second": ("W", "N")}
+BATCHES_OF = {"main": ("R", "Q", "Q2", "E", "S1", "S65", "BIG", "BIGQ"), "second": ("W", "N", "BIG")}
 N_BIG = 24576
 HEAVY_LO, HEAVY_HI, HEAVY_STEP = 6900.0, 8200.0, 26.0  # target masses of the heavy block's peptides
 N_TWIN_SPECTRA, N_HEAVY_SPECTRA = 300, 600

@@ -1,9 +1,9 @@
 """One scorer handle held to the oracle across sequences of DIFFERENT steps, as the command line drives it (cli.search_file: one
 handle per device for the whole run, file after file) — the state a handle carries from step to step in csrc/capi.hip:
-retry_likely and the deferred retry pass with its late launch (score_resident_locked / enqueue_compute phase 2 / collect_retry),
+retry_likely and the deferred retry pass with its late launch (resident_attempt / launch_deferred_retries / enqueue_late_retry / collect_retry),
 per part of a step in parts; counters_clean; the timing interval (steps without events); page-locked and pageable result arrays;
 working sets that grow and shrink; outs[] shared by the parts of a resident step and the lanes of the streaming entry; large-window
-batches behind narrow ones; the entry points that put `timed` back.
+batches behind narrow ones; a wrongly guessed step in parts repeated as one; the entry points that put `timed` back.
 
 ONE invariant: a step's results do not depend on what the handle did before.  tests/handle_sequences.py holds every scoring step to
 the oracle (initial_hits, quick_score and annotate to theirs; score_candidates and localise byte for byte to the same calls on a fresh
@@ -15,11 +15,13 @@ Wall time per test on the MI355X, 5.0 s for the 25 tests: the module fixture (wo
 the reach test 0.64 s (it measures most batches first); drawn sequences 0.09 to 0.28 s each; the sequences in parts 0.17 to
 0.20 s; the command line's loop 0.13 s; every other test 0.04 to 0.10 s.  A second run, on a machine busy with other work, took
 33 s, every test about seven times as long: the slowest were drawn sequence 0 with 5.5 s (it is the first to ask the oracle for
-the annotations of Q and R) and the reach test with 4.3 s; no other test was above 2.8 s."""
+the annotations of Q and R) and the reach test with 4.3 s; no other test was above 2.8 s.  The repeated step's sequence, added
+since: 0.28 s asked for two parts, 0.42 to 0.51 s for three; the module's 27 tests 8.7 s."""
 import numpy as np
 import pytest
 
 import handle_sequences as H
+from parity_utils import assert_features_equal
 from sage_amd.api import DeviceDatabase
 
 pytestmark = pytest.mark.gpu
@@ -202,6 +204,47 @@ def test_large_windows_behind_narrow_steps_and_back(env):
         assert (t["n_wide"] > 0) == (name == "W"), (name, t["n_wide"])
         assert t["n_retry"] > 10 if name == "W" else t["n_retry"] == 0
     assert ts[1]["records"] == ts[4]["records"] == ts[5]["records"] and ts[0]["records"] == ts[2]["records"] == ts[6]["records"]
+
+
+@pytest.mark.parametrize("ways", [None, "3"])
+def test_a_wrong_guess_in_parts_is_repeated_as_one(env, monkeypatch, ways):
+    """BIG under the second configuration, uploaded with SAGE_HIP_ASSUME_NARROW=1 (the upload then says "no large windows" and
+    skips the exact check): the step starts without the large-window kernels, its twin spectra queue for them, and the step is
+    repeated as ONE part with them (score_resident_locked).  Then N, the SAME device batch again — it now remembers maybe_wide —
+    and W.  Every step matches the oracle; the repeated step reports what a fresh handle reports for a batch known to be wide
+    (n_wide > 0, one part, both passes' launches: the first attempt leaves nothing in the figures); the second BIG step matches
+    the first byte for byte; N behind it is a fresh handle's N, launches included.
+    ASSUMED, not observed: that the first attempt went in two parts (three with SAGE_HIP_WAYS=3).  It follows from
+    resident_attempt — 24 576 >= 8192 x parts and maybe_wide == false — but n_ways is the repeated attempt's and the
+    SAGE_HIP_STEP_TRACE line does not name the parts.  tests/test_handle_sequences_cpu.py holds the windows to what is needed."""
+    w, _, fresh = env
+    if ways:
+        monkeypatch.setenv("SAGE_HIP_WAYS", ways)
+    want, want_n = fresh("second", "BIG"), fresh("second", "N")  # (measured without the switch: the upload's exact check says "wide")
+    assert want["n_wide"] > 0 and want["n_ways"] == 1 and want["n_retry"] > 0
+    h = handle(env, "second")
+    batch, oracle = w.batch("BIG"), w.oracle("second", "BIG")
+    monkeypatch.setenv("SAGE_HIP_ASSUME_NARROW", "1")
+    dbatch = h.scorer.upload(batch)
+    try:
+        gf, gc, t1 = h._resident(dbatch, batch.n)
+        monkeypatch.delenv("SAGE_HIP_ASSUME_NARROW")
+        assert_features_equal(gf, gc, *oracle, "BIG, the repeated step")
+        assert t1["n_wide"] > 0 and t1["n_ways"] == 1, t1
+        assert {k: t1[k] for k in ("n_retry", "n_launches", "n_wide", "n_ways")} == {k: want[k] for k in ("n_retry", "n_launches", "n_wide", "n_ways")}
+        first = H.valid_bytes(gf, gc)
+        tn = h.step("pinned", "N")  # (held to the oracle and to a fresh handle's n_retry / n_wide / n_ways in Handle.step)
+        assert tn["n_launches"] == want_n["n_launches"], "N behind a step with retries launches its retry pass, like a fresh handle"
+        monkeypatch.setenv("SAGE_HIP_ASSUME_NARROW", "1")
+        gf, gc, t3 = h._resident(dbatch, batch.n)
+        monkeypatch.delenv("SAGE_HIP_ASSUME_NARROW")
+        assert_features_equal(gf, gc, *oracle, "BIG again")
+        assert H.valid_bytes(gf, gc) == first
+        assert {k: t3[k] for k in ("n_retry", "n_launches", "n_wide", "n_ways")} == {k: want[k] for k in ("n_retry", "n_launches", "n_wide", "n_ways")}
+    finally:
+        dbatch.close()
+    tw = h.step("pinned", "W")
+    assert tw["n_wide"] > 0 and tw["n_retry"] > 10
 
 
 @pytest.mark.parametrize("seed", range(12))

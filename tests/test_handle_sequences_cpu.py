@@ -53,6 +53,22 @@ def test_big_is_separated_by_mass_and_a_third_at_most_is_retry_rich(w):
         assert name in ("BIG", "BIGQ") or len(idx) <= 1000
 
 
+def test_big_under_the_second_configuration_is_wide_in_its_twin_spectra_only(w):
+    """What test_gpu_handle_sequences.test_a_wrong_guess_in_parts_is_repeated_as_one rests on: under ±200 Da the twin spectra
+    of BIG have windows beyond the narrow kernel's capacity (DevScorer::wcap, 1024 candidate slots) — the step must be repeated
+    with the large-window kernels — and the heavy ones, three quarters of the batch and the whole of one part, have none."""
+    wcap = 1024
+    c = w.window_counts("second", "BIG")
+    from_r = w.index["BIG"] < H.N_TWIN_SPECTRA
+    print(f"twin windows {int(c[from_r].min())} .. {int(c[from_r].max())}, heavy windows {int(c[~from_r].min())} .. {int(c[~from_r].max())}")
+    assert c[from_r].max() > wcap and np.mean(c[from_r] > wcap) > 0.5
+    assert c[~from_r].max() < H.trim_k(H.CONFIGS["second"])
+    assert H.N_BIG >= 2 * 8192 and "BIG" in H.BATCHES_OF["second"]
+    # the oracle of BIG under the second configuration is a gather over the same unique spectra as under the first
+    used = w.oracle_unique("second")[2]
+    assert set(w.index["BIG"]) <= set(used)
+
+
 def test_the_oracle_reports_on_r_and_its_last_rank_is_tied(w):
     """At least 2 n / 3 PSMs on R, and for at least 50 of its spectra the last reported hyperscore equals that of another
     candidate in the window — the tie the retry pass exists for.  Read from the oracle with report_psms one higher: rank 2 against
