@@ -900,6 +900,60 @@ int sage_hip_protein_lfq(int device, const SageProteinLfqInput* in, SageProteinL
 int sage_hip_write_protein_lfq(const char* path, const char* const* protein_names, uint32_t n_proteins, const uint32_t* rows,
                                uint32_t n_out, const SageProteinLfqOutput* result, const char* const* filenames, uint32_t n_files);
 
+/* ---- precursor purity of reported PSMs from MS1 scans ("precursor ion fraction", "isolation interference").  An addition over the
+ * reference, additive to ABI 6; the contract is DESIGN.md 7h and sage_amd/csrc/purity.h, stated again in tests/purity_reference.py.
+ * One query: an MS1 spectrum (raw m/z, peaks in the order given), a precursor m/z, a charge z (0: unknown), isolation offsets
+ * (lo, hi) in Da (either NaN, or either array NULL: the settings' default pair).  All m/z arithmetic is f32 without FMA.
+ *   window    [mz + lo, mz + hi], both ends inside; a NaN m/z is in no interval.
+ *   envelope  c_k = mz + (k * NEUTRON) / z, k = 0 .. max_isotope (z == 0: c_0 = mz alone); a peak of the window is matched when it
+ *             lies inside the ppm bounds (Tolerance::bounds of Ppm(-t, t)) of at least one c_k, and is counted once.
+ *   below     every peak of the spectrum, in the window or not, inside the ppm bounds of mz - NEUTRON / z (z == 0: none).
+ *   total, matched, below: f64 sums of (double)intensity from +0.0, peak after peak in ascending position in the spectrum; NaN, +-inf,
+ *   negative and -0.0 intensities pass through.  purity = (float)(matched / total), stored as computed; -1.0f (with zero sums and
+ *   counts) when no peak is in the window or ms1_index is UINT64_MAX.
+ * Checked before the device is touched, each SAGE_HIP_ERR_INVALID: a NULL array with n_queries > 0, an ms1_index that is neither
+ * UINT64_MAX nor below the number of spectra, max_isotope > 16, a ppm_tolerance that is negative or not finite, a peak_off that
+ * decreases.  A spectrum of more than 2^31 - 1 peaks: SAGE_HIP_ERR_UNSUPPORTED.  No query, or none with a spectrum: SAGE_HIP_OK
+ * without a launch.  The MS1 batches go through the device one at a time (a batch without a query is skipped), so device memory is
+ * bounded by the largest batch.  A spectrum whose m/z are non-decreasing and NaN-free is read by partition points (n_sorted_spectra),
+ * any other is scanned whole (n_scanned_spectra); SAGE_HIP_PURITY_SCAN=1 scans all; the results are the same bits. */
+typedef struct SagePuritySettings {
+    float ppm_tolerance, default_isolation_lo, default_isolation_hi;
+    uint32_t max_isotope;
+} SagePuritySettings;
+
+typedef struct SagePurityInput {
+    uint32_t n_ms1;
+    const SageRawBatch* ms1;          /* peak_off, mz, intensities are read */
+    uint64_t n_queries;
+    const uint64_t* ms1_index;        /* spectrum number counted through the batches in order; UINT64_MAX: none */
+    const float* precursor_mz;
+    const uint8_t* charge;
+    const float* isolation_lo;        /* either NULL: the default pair for every query */
+    const float* isolation_hi;
+    SagePuritySettings settings;
+} SagePurityInput;
+
+typedef struct SagePurityOutput {     /* caller-allocated, [n_queries] each */
+    uint32_t* n_window;
+    uint32_t* n_matched;
+    double* total;
+    double* matched;
+    double* below;
+    float* purity;
+    uint64_t n_sorted_spectra, n_scanned_spectra; /* spectra with at least one query, by route */
+    float upload_ms, kernel_ms, device_ms;        /* HIP events, summed over the batches */
+} SagePurityOutput;
+
+int sage_hip_precursor_purity(int device, const SagePurityInput* in, SagePurityOutput* out);
+
+/* purity.sage.tsv: psm_id, filename, scannr, charge, ms1_scannr (empty where ms1_ids[r] is NULL or ""), isolation_lo, isolation_hi,
+ * peaks_in_window, peaks_matched, total_intensity, precursor_intensity, below_intensity, purity; one row per entry, in the order
+ * given; f32 / f64 as ryu writes them.  `result` holds [n_rows] arrays. */
+int sage_hip_write_purity(const char* path, uint64_t n_rows, const uint64_t* psm_id, const uint32_t* file_id, const char* const* spec_ids,
+                          const uint8_t* charge, const char* const* ms1_ids, const float* isolation_lo, const float* isolation_hi,
+                          const SagePurityOutput* result, const char* const* filenames, uint32_t n_files);
+
 const char* sage_hip_last_error(void);
 int sage_hip_abi_version(void);
 

@@ -264,6 +264,23 @@ class SageProteinLfqOutput(C.Structure):
                 ("n_batches", C.c_uint32)]
 
 
+class SagePuritySettings(C.Structure):
+    _fields_ = [("ppm_tolerance", C.c_float), ("default_isolation_lo", C.c_float), ("default_isolation_hi", C.c_float),
+                ("max_isotope", C.c_uint32)]
+
+
+class SagePurityInput(C.Structure):
+    _fields_ = [("n_ms1", C.c_uint32), ("ms1", C.POINTER(SageRawBatch)), ("n_queries", C.c_uint64), ("ms1_index", c_u64_p),
+                ("precursor_mz", c_float_p), ("charge", c_u8_p), ("isolation_lo", c_float_p), ("isolation_hi", c_float_p),
+                ("settings", SagePuritySettings)]
+
+
+class SagePurityOutput(C.Structure):
+    _fields_ = [("n_window", c_u32_p), ("n_matched", c_u32_p), ("total", C.POINTER(C.c_double)), ("matched", C.POINTER(C.c_double)),
+                ("below", C.POINTER(C.c_double)), ("purity", c_float_p), ("n_sorted_spectra", C.c_uint64),
+                ("n_scanned_spectra", C.c_uint64), ("upload_ms", C.c_float), ("kernel_ms", C.c_float), ("device_ms", C.c_float)]
+
+
 class SagePostColumns(C.Structure):
     _fields_ = [(k, c_float_p) for k in ("discriminant_score", "posterior_error", "spectrum_q", "peptide_q", "protein_q",
                                          "aligned_rt", "predicted_rt", "delta_rt_model", "predicted_ims", "delta_ims_model")]
@@ -425,6 +442,9 @@ def load():
         "sage_hip_protein_lfq": (C.c_int, [C.c_int, C.POINTER(SageProteinLfqInput), C.POINTER(SageProteinLfqOutput)]),
         "sage_hip_write_protein_lfq": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, c_u32_p, C.c_uint32,
                                                  C.POINTER(SageProteinLfqOutput), C.POINTER(C.c_char_p), C.c_uint32]),
+        "sage_hip_precursor_purity": (C.c_int, [C.c_int, C.POINTER(SagePurityInput), C.POINTER(SagePurityOutput)]),
+        "sage_hip_write_purity": (C.c_int, [C.c_char_p, C.c_uint64, c_u64_p, c_u32_p, C.POINTER(C.c_char_p), c_u8_p, C.POINTER(C.c_char_p),
+                                            c_float_p, c_float_p, C.POINTER(SagePurityOutput), C.POINTER(C.c_char_p), C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
@@ -453,6 +473,7 @@ EXPORTED_SYMBOLS = [
     "sage_hip_hostdb_isomer_groups", "sage_hip_score_candidates_resident", "sage_hip_last_candidates_timing",
     "sage_hip_localise_resident", "sage_hip_ascore_from_counts", "sage_hip_last_localise_timing",
     "sage_hip_protein_lfq", "sage_hip_write_protein_lfq",
+    "sage_hip_precursor_purity", "sage_hip_write_purity",
 ]
 
 

@@ -1301,6 +1301,88 @@ def protein_lfq(areas, protein_of_row, n_proteins: int, min_ratio_count: int = 1
     return r
 
 
+# ---- precursor purity of reported PSMs from MS1 scans (sage_hip_precursor_purity) ------------------------------------------------
+NO_MS1 = 0xFFFFFFFFFFFFFFFF  # ms1_index of a query without an MS1 spectrum
+
+
+@dataclass
+class PurityResult:
+    """Outputs of sage_hip_precursor_purity, one entry per query: peaks in the isolation window and those of them on
+    the precursor's isotope envelope, the f64 sums of their intensities and of the peaks one neutron below the precursor, and
+    purity = f32(matched / total) (-1.0: no peak in the window, or no MS1 spectrum).  n_sorted_spectra / n_scanned_spectra: the
+    spectra with at least one query, by the route they took."""
+    n_window: np.ndarray
+    n_matched: np.ndarray
+    total: np.ndarray
+    matched: np.ndarray
+    below: np.ndarray
+    purity: np.ndarray
+    n_sorted_spectra: int
+    n_scanned_spectra: int
+    stage_ms: dict
+
+    def to_c(self, keep: list) -> "L.SagePurityOutput":
+        arr = lambda a, t: (keep.append(a), L.as_ptr(a, t))[1]
+        return L.SagePurityOutput(arr(self.n_window, C.c_uint32), arr(self.n_matched, C.c_uint32), arr(self.total, C.c_double),
+                                  arr(self.matched, C.c_double), arr(self.below, C.c_double), arr(self.purity, C.c_float))
+
+
+def precursor_purity(ms1: Sequence[RawBatch], ms1_index, precursor_mz, charge, isolation_lo=None, isolation_hi=None,
+                     ppm_tolerance: float = 10.0, max_isotope: int = 4, default_isolation: Tuple[float, float] = (-0.5, 0.5),
+                     device: int = 0) -> PurityResult:
+    """Precursor purity of one query per entry.  ms1_index: the query's MS1 spectrum, counted through `ms1` in
+    order, NO_MS1 for none (assign_ms1 picks them); charge 0 = unknown; isolation offsets in Da, NaN (or no arrays) = the default
+    pair, which follows the reference's own fallback (tmt.rs:95-97)."""
+    idx = np.ascontiguousarray(ms1_index, dtype=np.uint64).reshape(-1)
+    n = len(idx)
+    mz = np.ascontiguousarray(precursor_mz, dtype=np.float32).reshape(-1)
+    z = np.ascontiguousarray(charge, dtype=np.uint8).reshape(-1)
+    assert len(mz) == n and len(z) == n
+    lo = hi = None
+    if isolation_lo is not None and isolation_hi is not None:
+        lo = np.ascontiguousarray(isolation_lo, dtype=np.float32).reshape(-1)
+        hi = np.ascontiguousarray(isolation_hi, dtype=np.float32).reshape(-1)
+        assert len(lo) == n and len(hi) == n
+    r = PurityResult(np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n), np.zeros(n), np.zeros(n), np.full(n, -1.0, np.float32),
+                     0, 0, {})
+    cb = [b.to_c() for b in ms1]
+    arr = (L.SageRawBatch * max(len(cb), 1))(*cb)
+    cin = L.SagePurityInput(len(cb), arr, n, L.as_ptr(idx, C.c_uint64), L.as_ptr(mz, C.c_float), L.as_ptr(z, C.c_uint8),
+                            None if lo is None else L.as_ptr(lo, C.c_float), None if hi is None else L.as_ptr(hi, C.c_float),
+                            L.SagePuritySettings(float(ppm_tolerance), float(default_isolation[0]), float(default_isolation[1]),
+                                                 int(max_isotope)))
+    keep = []
+    cout = r.to_c(keep)
+    L.check(L.load().sage_hip_precursor_purity(device, C.byref(cin), C.byref(cout)))
+    r.n_sorted_spectra, r.n_scanned_spectra = int(cout.n_sorted_spectra), int(cout.n_scanned_spectra)
+    r.stage_ms = {"upload_ms": float(cout.upload_ms), "kernel_ms": float(cout.kernel_ms), "device_ms": float(cout.device_ms)}
+    return r
+
+
+def assign_ms1(ms1: Sequence[RawBatch], file_id, scan_start_time) -> np.ndarray:
+    """The MS1 spectrum of each query (file_id, scan_start_time of its MS2 scan), numbered through `ms1` in order: of the spectra of
+    the same file_id, the one with the greatest scan_start_time <= t, the later one in the given order among equal times; NO_MS1
+    where there is none (a file read as MGF has no MS1).  Host-side numpy."""
+    fid = np.asarray(file_id, dtype=np.uint32).reshape(-1)
+    t = np.asarray(scan_start_time, dtype=np.float32).reshape(-1)
+    assert len(fid) == len(t)
+    out = np.full(len(fid), NO_MS1, np.uint64)
+    if not len(fid) or not len(ms1):
+        return out
+    s_fid = np.concatenate([np.asarray(b.file_id, np.uint32) for b in ms1])
+    s_t = np.concatenate([np.asarray(b.scan_start_time, np.float32) for b in ms1])
+    for f in np.unique(fid):
+        spectra = np.flatnonzero((s_fid == f) & ~np.isnan(s_t))
+        mine = np.flatnonzero(fid == f)
+        if not len(spectra) or not len(mine):
+            continue
+        by_time = spectra[np.argsort(s_t[spectra], kind="stable")]  # equal times keep the given order: the last one is the later
+        k = np.searchsorted(s_t[by_time], t[mine], side="right")     # spectra with time <= t (a NaN t sorts last: guarded below)
+        ok = (k > 0) & ~np.isnan(t[mine])
+        out[mine[ok]] = by_time[k[ok] - 1].astype(np.uint64)
+    return out
+
+
 # ---- TMT reporter-ion quantification (sage_hip_tmt) ----------------------------------------------------------------------------
 # tmt.rs:216-231, as f32
 TMT6PLEX = np.array([126.127726, 127.124761, 128.134436, 129.131471, 130.141145, 131.138180], dtype=np.float32)

@@ -26,7 +26,7 @@ from . import output
 from ._lib import FEATURE_DTYPE as L_FEATURE_DTYPE
 from .api import (LFQ_INTEGRATION, LFQ_SCORING, DatabaseParameters, DeviceDatabase, Isobaric, LfqSettings, RawBatch, Scorer,
                   ScorerParams, SpectrumBatch, SpectrumProcessor, TmtSettings, Tolerance, device_count, lfq, peptide_compositions,
-                  predict_rt, protein_groups, protein_lfq, rescore, tmt)
+                  NO_MS1, assign_ms1, precursor_purity, predict_rt, protein_groups, protein_lfq, rescore, tmt)
 from .mgf import TOL_DA, is_mgf, read_mgf_native, read_spectra
 
 
@@ -100,6 +100,22 @@ def protein_lfq_settings(cfg: dict):
         raise SystemExit("quant.protein_lfq_settings.min_ratio_count must not be negative")
     if on and not (q.get("lfq") is not None and bool(q.get("lfq"))):
         raise SystemExit("`quant.protein_lfq: true` needs `quant.lfq: true`: the protein roll-up reads the precursor areas of lfq.tsv")
+    return on, st
+
+
+def purity_settings(cfg: dict):
+    """precursor_purity / purity_settings, top-level keys — an addition over the reference, whose serde schema ignores them
+    (DESIGN.md 7h): (on, {"ppm_tolerance", "max_isotope", "default_isolation"})."""
+    on = bool(cfg.get("precursor_purity", False))
+    o = cfg.get("purity_settings") or {}
+    iso = o.get("default_isolation")
+    st = {"ppm_tolerance": 10.0 if o.get("ppm_tolerance") is None else float(o["ppm_tolerance"]),
+          "max_isotope": 4 if o.get("max_isotope") is None else int(o["max_isotope"]),
+          "default_isolation": (-0.5, 0.5) if iso is None else (float(iso[0]), float(iso[1]))}
+    if not (0.0 <= st["ppm_tolerance"] < float("inf")):
+        raise SystemExit("purity_settings.ppm_tolerance must be finite and not negative")
+    if not 0 <= st["max_isotope"] <= 16:
+        raise SystemExit("purity_settings.max_isotope must be between 0 and 16")
     return on, st
 
 
@@ -454,6 +470,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     lfq_on, lfq_settings = quant_settings(cfg, log)
     protein_lfq_on, protein_lfq_st = protein_lfq_settings(cfg)
     isobaric, tmt_st = tmt_settings(cfg, log)
+    purity_on, purity_st = purity_settings(cfg)
     # runner.rs:391-410: S/N division at the quant level; at level 2 the reporter region is kept out of deisotoping
     sn_level = tmt_st.level if (isobaric is not None and tmt_st.sn) else None
     ms2_sn = sn_level if sn_level == 2 else None
@@ -526,7 +543,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         t0 = time.time()
         # (read_spectra: .mgf / .mgf.gz to the MGF reader, which has MS2 only and no S/N option; anything else as mzML)
         raw = read_spectra(path, file_id=file_id, ms_level=2, check_searchable=True, sn_level=ms2_sn)
-        ms1 = read_spectra(path, file_id=file_id, ms_level=1)[0] if lfq_on else None  # (runner.rs:361-363: only for LFQ)
+        ms1 = read_spectra(path, file_id=file_id, ms_level=1)[0] if lfq_on or purity_on else None  # (runner.rs:361-363: only for LFQ; 7h)
         # TMT at a level other than 2 (SPS-MS3): that level's spectra (level 1 quantifies nothing: tmt.rs:330)
         msn = (read_spectra(path, file_id=file_id, ms_level=tmt_st.level, sn_level=sn_level)[0]
                if isobaric is not None and tmt_st.level not in (1, 2) else None)
@@ -535,6 +552,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
 
     mzml_paths = list(mzml_paths)
     ms1_batches = []
+    purity_parts = []  # per file: (precursor m/z, isolation_lo, isolation_hi, scan start time) of every PSM's spectrum
     tmt_parts, tmt_ms = [], 0.0  # per file: (file_id, spectrum ids, ion injection times, intensities[n, labels])
     reader = ThreadPoolExecutor(max_workers=1)
     ahead = reader.submit(read_file, 0, mzml_paths[0]) if mzml_paths else None
@@ -591,6 +609,11 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
             localise_parts.append(tuple(a[spec_of, rank_of] for a in found[5]))
             localise_ms += getattr(search_file, "last_localise_ms", 0.0)
         meta += [(psm_id + j, name, ids[i]) for j, i in enumerate(spec_of.tolist())]
+        if purity_on:
+            at = {s: k for k, s in enumerate(search_raw.ids)}
+            row = np.array([at[ids[i]] for i in spec_of.tolist()], dtype=np.int64)
+            purity_parts.append((search_raw.precursor_mz[row], search_raw.isolation_lo[row], search_raw.isolation_hi[row],
+                                 search_raw.scan_start_time[row]))
         if arr is not None:
             for j, (i, r) in enumerate(zip(spec_of.tolist(), rank_of.tolist())):
                 slot = i * params.report_psms + r
@@ -719,6 +742,26 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         log(f"- protein roll-up (MaxLFQ): {int(protein_lfq_ms):8d} ms ({n_written} proteins from {len(used)} precursors)")
         protein_lfq_summary = {"protein_lfq_rows": n_written, "protein_lfq_ms": protein_lfq_ms,
                                "protein_lfq_device_ms": rolled.stage_ms["device_ms"]}
+    purity_summary = {}
+    if purity_on:  # one query per reported PSM, in results.sage.tsv's order, on the first device
+        t0 = time.time()
+        o = np.array(list(order), dtype=np.int64)
+        cols = [np.concatenate([p[j] for p in purity_parts])[o] if purity_parts else np.zeros(0, np.float32) for j in range(4)]
+        fid, charge = flat["file_id"][o], flat["charge"][o].astype(np.uint8)
+        ms1_index = assign_ms1(ms1_batches, fid, cols[3])
+        pur = precursor_purity(ms1_batches, ms1_index, cols[0], charge, cols[1], cols[2], purity_st["ppm_tolerance"],
+                               purity_st["max_isotope"], purity_st["default_isolation"], device=device)
+        ms1_ids = [s for b in ms1_batches for s in b.ids]
+        missing = np.isnan(cols[1]) | np.isnan(cols[2])
+        used_lo = np.where(missing, np.float32(purity_st["default_isolation"][0]), cols[1]).astype(np.float32)
+        used_hi = np.where(missing, np.float32(purity_st["default_isolation"][1]), cols[2]).astype(np.float32)
+        up = os.path.join(output_directory, "purity.sage.tsv")
+        output.write_purity_native(up, [psm_ids[i] for i in o], filenames, fid, [spec_ids[i] for i in o], charge,
+                                   ["" if int(k) == NO_MS1 else ms1_ids[int(k)] for k in ms1_index], used_lo, used_hi, pur)
+        paths.append(up)
+        purity_ms = (time.time() - t0) * 1000.0
+        log(f"- precursor purity: {int(purity_ms):8d} ms ({len(o)} PSMs, {pur.stage_ms['device_ms']:.1f} ms on the device)")
+        purity_summary = {"purity_rows": len(o), "purity_ms": purity_ms}
     if write_pin:  # runner.rs:655-660
         pp = os.path.join(output_directory, "results.sage.pin")
         output.write_results_native(pp, "pin", host, flat, list(order), psm_ids, filenames, spec_ids, [rtp, post])
@@ -734,7 +777,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     stage_totals["total_after_index_ms"] = (time.time() - t_run) * 1e3
     summary = {"version": "sage-hip 0.1 (search-and-score path of sage 0.15.0-beta.2)", "psms": len(flat),
                "spectra_searched": n_searched, "search_ms": search_ms, "stages": stage_totals, "output_paths": paths, **rescore_summary,
-               **lfq_summary, **tmt_summary, **isomer_summary, **localise_summary, **protein_lfq_summary}
+               **lfq_summary, **tmt_summary, **isomer_summary, **localise_summary, **protein_lfq_summary, **purity_summary}
     with open(os.path.join(output_directory, "results.json"), "w") as fh:
         json.dump(dict(cfg, output_paths=paths, summary=summary), fh, indent=2, default=str)
     return summary

@@ -1,6 +1,7 @@
 // capi_host.cpp — the entry points of the C ABI (include/sage_hip.h) that take no scorer: the error string, the FASTA database,
 // the mzML / MGF readers, the writers, the group graph, and the thin entry points of the post-search stages.
 #include "capi_state.h"
+#include "purity.h"
 
 static thread_local std::string g_last_error;
 
@@ -224,6 +225,62 @@ int sage_hip_write_protein_lfq(const char* path, const char* const* protein_name
             return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_protein_lfq: protein id out of range or null name");
     std::string err;
     if (!write_protein_lfq(path, protein_names, rows, n_out, *result, filenames, n_files, err)) return fail(SAGE_HIP_ERR_INVALID, err);
+    return SAGE_HIP_OK;
+}
+
+// precursor purity of reported PSMs from MS1 scans (purity.hip); every check comes before the device is touched
+int sage_hip_precursor_purity(int device, const SagePurityInput* in, SagePurityOutput* out) {
+    const char* const who = "sage_hip_precursor_purity";
+    if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": null argument");
+    out->n_sorted_spectra = out->n_scanned_spectra = 0;
+    out->upload_ms = out->kernel_ms = out->device_ms = 0.0f;
+    const SagePuritySettings& st = in->settings;
+    if (st.max_isotope > purity::MAX_ISOTOPE) return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": max_isotope above 16");
+    if (!(st.ppm_tolerance >= 0.0f) || std::isinf(st.ppm_tolerance))
+        return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": ppm_tolerance must be finite and not negative");
+    if (in->n_queries == 0) return SAGE_HIP_OK;
+    if (!in->ms1_index || !in->precursor_mz || !in->charge || (in->n_ms1 && !in->ms1) || !out->n_window || !out->n_matched || !out->total ||
+        !out->matched || !out->below || !out->purity)
+        return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": null array");
+    uint64_t n_spectra = 0;
+    for (uint32_t b = 0; b < in->n_ms1; ++b) {
+        const SageRawBatch& r = in->ms1[b];
+        n_spectra += r.n_spectra;
+        if (!r.n_spectra) continue;
+        if (!r.peak_off) return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": null MS1 array");
+        for (uint32_t i = 0; i < r.n_spectra; ++i) {
+            if (r.peak_off[i + 1] < r.peak_off[i]) return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": peak_off is not monotone");
+            if (r.peak_off[i + 1] - r.peak_off[i] > (uint64_t)INT32_MAX)
+                return fail(SAGE_HIP_ERR_UNSUPPORTED, std::string(who) + ": a spectrum of more than 2^31 - 1 peaks");
+        }
+        if (r.peak_off[r.n_spectra] && (!r.mz || !r.intensities)) return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": null MS1 array");
+    }
+    bool any = false;
+    for (uint64_t i = 0; i < in->n_queries; ++i) {
+        if (in->ms1_index[i] == purity::NO_MS1) continue;
+        if (in->ms1_index[i] >= n_spectra) return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": an ms1_index that is not below the number of spectra");
+        any = true;
+    }
+    if (any)
+        if (const int rc = stage_guard(who, 0)) return rc;
+    std::string err;
+    const int rc = purity_on_device(device, *in, *out, err);  // (no query with a spectrum: fills the outputs, no device call)
+    return rc == SAGE_HIP_OK ? rc : fail(rc, err);
+}
+
+int sage_hip_write_purity(const char* path, uint64_t n_rows, const uint64_t* psm_id, const uint32_t* file_id, const char* const* spec_ids,
+                          const uint8_t* charge, const char* const* ms1_ids, const float* isolation_lo, const float* isolation_hi,
+                          const SagePurityOutput* result, const char* const* filenames, uint32_t n_files) {
+    if (!path || !result || (n_files && !filenames) ||
+        (n_rows && (!psm_id || !file_id || !spec_ids || !charge || !ms1_ids || !isolation_lo || !isolation_hi || !result->n_window ||
+                    !result->n_matched || !result->total || !result->matched || !result->below || !result->purity)))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_purity: null argument");
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (file_id[r] >= n_files || !filenames[file_id[r]] || !spec_ids[r])
+            return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_purity: file id out of range or null id");
+    std::string err;
+    if (!write_purity(path, n_rows, psm_id, file_id, spec_ids, charge, ms1_ids, isolation_lo, isolation_hi, *result, filenames, err))
+        return fail(SAGE_HIP_ERR_INVALID, err);
     return SAGE_HIP_OK;
 }
 

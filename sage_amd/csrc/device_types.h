@@ -300,6 +300,8 @@ int lfq_on_device(int device, const SageLfqInput& in, const SageLfqMobility* mob
 int tmt_on_device(int device, const SageTmtInput& in, SageTmtOutput& out, std::string& err);
 // protein_lfq.hip: sage_hip_protein_lfq behind its argument checks (n_rows, n_files and n_proteins all non-zero)
 int protein_lfq_on_device(int device, const SageProteinLfqInput& in, SageProteinLfqOutput& out, std::string& err);
+// purity.hip: sage_hip_precursor_purity behind its argument checks (n_queries non-zero, every array present and in range)
+int purity_on_device(int device, const SagePurityInput& in, SagePurityOutput& out, std::string& err);
 // launch schedule of a batch (index_build.hip): order[k] = spectrum scored by block k, ascending neutral precursor mass
 size_t schedule_temp_bytes(uint32_t n);
 int schedule_on_device(uint32_t n, const float* d_precursor_mz, const uint8_t* d_charge, uint32_t min_charge, uint32_t* d_keys_a,

@@ -390,4 +390,43 @@ bool write_protein_lfq(const char* path, const char* const* protein_names, const
     return ok;
 }
 
+// purity.sage.tsv: one row per reported PSM in the order given; ms1_scannr is empty for a PSM without an MS1 scan.
+bool write_purity(const char* path, uint64_t n_rows, const uint64_t* psm_id, const uint32_t* file_id, const char* const* spec_ids,
+                  const uint8_t* charge, const char* const* ms1_ids, const float* isolation_lo, const float* isolation_hi,
+                  const SagePurityOutput& result, const char* const* filenames, std::string& err) {
+    FILE* fh = std::fopen(path, "wb");
+    if (!fh) {
+        err = std::string("cannot open ") + path;
+        return false;
+    }
+    std::string out =
+        "psm_id\tfilename\tscannr\tcharge\tms1_scannr\tisolation_lo\tisolation_hi\tpeaks_in_window\tpeaks_matched\ttotal_intensity\t"
+        "precursor_intensity\tbelow_intensity\tpurity\n";
+    bool ok = true;
+    for (uint64_t r = 0; r < n_rows && ok; ++r) {
+        itoa(out, psm_id[r]);
+        str(out, filenames[file_id[r]]);
+        str(out, spec_ids[r]);
+        itoa(out, (unsigned)charge[r]);
+        str(out, ms1_ids[r] ? ms1_ids[r] : "");
+        f32(out, isolation_lo[r]);
+        f32(out, isolation_hi[r]);
+        itoa(out, result.n_window[r]);
+        itoa(out, result.n_matched[r]);
+        f64(out, result.total[r]);
+        f64(out, result.matched[r]);
+        f64(out, result.below[r]);
+        f32(out, result.purity[r]);
+        out.back() = '\n';
+        if (out.size() >= (1 << 20)) {
+            ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+            out.clear();
+        }
+    }
+    if (ok && !out.empty()) ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+    if (std::fclose(fh) != 0) ok = false;
+    if (!ok && err.empty()) err = std::string("write to ") + path + " failed";
+    return ok;
+}
+
 }  // namespace sagehip

@@ -380,6 +380,48 @@ def write_protein_lfq_native(path: str, names: Sequence[str], result, filenames:
     return len(rows)
 
 
+PURITY_HEADERS = ["psm_id", "filename", "scannr", "charge", "ms1_scannr", "isolation_lo", "isolation_hi", "peaks_in_window",
+                  "peaks_matched", "total_intensity", "precursor_intensity", "below_intensity", "purity"]
+
+
+def purity_rows(psm_ids, filenames: Sequence[str], file_id, spec_ids, charge, ms1_ids, isolation_lo, isolation_hi, result) -> List[List[str]]:
+    """purity.sage.tsv's rows for a PurityResult-like object: one per reported PSM in the order given.  ms1_ids: the
+    id of the MS1 scan used, "" or None where there is none; isolation_lo / isolation_hi: the pair used (f32)."""
+    lo, hi = np.asarray(isolation_lo, dtype=np.float32), np.asarray(isolation_hi, dtype=np.float32)
+    return [[str(int(psm_ids[r])), filenames[int(file_id[r])], spec_ids[r], str(int(charge[r])), ms1_ids[r] or "", ryu_f32(lo[r]),
+             ryu_f32(hi[r]), str(int(result.n_window[r])), str(int(result.n_matched[r])), ryu_f64(np.float64(result.total[r])),
+             ryu_f64(np.float64(result.matched[r])), ryu_f64(np.float64(result.below[r])), ryu_f32(np.float32(result.purity[r]))]
+            for r in range(len(spec_ids))]
+
+
+def write_purity(path: str, rows: Sequence[List[str]]) -> None:
+    with open(path, "w", newline="") as fh:
+        fh.write(_record(PURITY_HEADERS) + "\n")
+        for r in rows:
+            fh.write(_record(r) + "\n")
+
+
+def write_purity_native(path: str, psm_ids, filenames: Sequence[str], file_id, spec_ids, charge, ms1_ids, isolation_lo, isolation_hi,
+                        result) -> None:
+    """purity.sage.tsv through the C++ writer (sage_hip_write_purity): the bytes of purity_rows + write_purity."""
+    import ctypes as C
+
+    from . import _lib as L
+    n = len(spec_ids)
+    pid = np.ascontiguousarray(psm_ids, dtype=np.uint64)
+    fid = np.ascontiguousarray(file_id, dtype=np.uint32)
+    z = np.ascontiguousarray(charge, dtype=np.uint8)
+    lo, hi = np.ascontiguousarray(isolation_lo, dtype=np.float32), np.ascontiguousarray(isolation_hi, dtype=np.float32)
+    assert len(pid) == n and len(fid) == n and len(z) == n and len(lo) == n and len(hi) == n and len(ms1_ids) == n
+    keep = []
+    cout = result.to_c(keep)
+    ids = (C.c_char_p * max(n, 1))(*[s.encode() for s in spec_ids])
+    ms1 = (C.c_char_p * max(n, 1))(*[(s or "").encode() for s in ms1_ids])
+    names = (C.c_char_p * max(len(filenames), 1))(*[s.encode() for s in filenames])
+    L.check(L.load().sage_hip_write_purity(path.encode(), n, L.as_ptr(pid, C.c_uint64), L.as_ptr(fid, C.c_uint32), ids, L.as_ptr(z, C.c_uint8),
+                                           ms1, L.as_ptr(lo, C.c_float), L.as_ptr(hi, C.c_float), C.byref(cout), names, len(filenames)))
+
+
 TMT_HEADERS = ["filename", "scannr", "ion_injection_time"]
 
 
