@@ -42,9 +42,14 @@ def tol_mul(tol, rhs):
 
 
 def binary_search_slice(sorted_f32, low, high):
-    """database.rs:549-561 over an ascending f32 array (total_cmp == numeric order for the finite values used here)."""
-    left = max(int(np.searchsorted(sorted_f32, low, side="left")) - 1, 0)
-    right = left + int(np.searchsorted(sorted_f32[left:], high, side="right"))
+    """database.rs:549-561 over an f32 array ascending in f32::total_cmp, which is the order both partition points search by:
+    -NaN first, then -inf … -0.0, +0.0 … +inf, +NaN last (numeric order only where every value is finite and no zero is signed)."""
+    def key(x):
+        b = np.asarray(x, np.float32).view(np.int32).astype(np.int64)
+        return np.where(b < 0, b ^ 0x7FFFFFFF, b)
+    keys = key(sorted_f32)
+    left = max(int(np.searchsorted(keys, key(low), side="left")) - 1, 0)
+    right = left + int(np.searchsorted(keys[left:], key(high), side="right"))
     return left, right
 
 

@@ -156,5 +156,60 @@ def test_oracle_equals_second_reading(name):
     assert n_psm >= batch.n // 3, f"{name}: only {n_psm} PSMs over {batch.n} spectra — the case does not exercise the scoring"
 
 
+# ---- hostile peak lists and precursors (tests/hostile_peaks.py): unsorted raw peaks, NaN / infinite / negative m/z and intensities ----
+@pytest.fixture(scope="module")
+def hostile_world():
+    import hostile_peaks as H
+    fasta, dbp = H.fasta_text(), DatabaseParameters(**H.TRYPTIC)
+    prod = dbp.build(fasta)
+    orc = oracle_lib.OracleDb.build(fasta, dbp)
+    assert orc.n_peptides == prod.n_peptides
+    return H, dbp, prod, orc
+
+
+HOSTILE_SETTINGS = ["chimera", "da3_report5", "da_fragments", "isotope_errors", "narrow", "wide_window_chimera"]
+
+
+@pytest.mark.parametrize("mode", ["deisotope", "heap"])
+@pytest.mark.parametrize("name", HOSTILE_SETTINGS)
+def test_oracle_equals_second_reading_on_hostile_peaks(hostile_world, name, mode):
+    """The processed spectra hold -NaN masses in front, +NaN masses behind, infinite and negative masses between them, NaN and
+    infinite intensities: binary_search_slice's partition points run in f32::total_cmp on both sides, Feature fields become
+    non-finite.  At least two thirds of the spectra keep a PSM."""
+    H, dbp, prod, orc = hostile_world
+    kw, chimeric, annotated = H.scorer_settings()[name]
+    raws, _ = H.peak_spectra(prod, chimeric)
+    if not annotated:
+        for r in raws:
+            r.precursor_charge = None
+    batch = SpectrumBatch.from_spectra(H.oracle_processed(raws, 150, mode == "deisotope"))
+    params = ScorerParams(**kw)
+    _, oc, _, _ = orc.score(params, batch)
+    assert (oc > 0).sum() >= H.MIN_PEAK_FRACTION * batch.n, f"{name}: {(oc > 0).sum()} of {batch.n} spectra have a PSM"
+    assert np.isnan(batch.masses).any() and np.isinf(batch.masses).any() and (batch.masses < 0).any()
+    n_psm = hold_oracle_to_second_reading(orc, dbp, params, batch, context=f"hostile peaks, {name}, {mode}")
+    assert n_psm == int(oc.sum())
+
+
+@pytest.mark.parametrize("name", HOSTILE_SETTINGS)
+def test_oracle_equals_second_reading_on_hostile_precursors(hostile_world, name):
+    """Every second spectrum has a precursor m/z of NaN, +-inf, 0, -500, 3e38 or PROTON (mass 0), with the charge known and
+    unknown: the precursor window's bounds are NaN, infinite or negative.  At least half of the untouched spectra keep a PSM."""
+    H, dbp, prod, orc = hostile_world
+    kw, _, annotated = H.scorer_settings()[name]
+    raws, touched = H.precursor_spectra(prod, annotated)
+    batch = SpectrumBatch.from_spectra(H.oracle_processed(raws))
+    params = ScorerParams(**kw)
+    _, oc, _, _ = orc.score(params, batch)
+    assert (oc[~touched] > 0).sum() >= H.MIN_PRECURSOR_FRACTION * (~touched).sum()
+    n_psm = hold_oracle_to_second_reading(orc, dbp, params, batch, context=f"hostile precursors, {name}")
+    assert n_psm == int(oc.sum())
+
+
+def test_the_hostile_settings_are_all_named():
+    import hostile_peaks as H
+    assert sorted(H.scorer_settings()) == HOSTILE_SETTINGS
+
+
 def test_the_cases_cover_five_hundred_spectra():
     assert sum(c[0]["n_spectra"] for c in CASES.values()) >= 500
