@@ -1041,7 +1041,7 @@ class ProteinGroupResult:
 def protein_groups(db: "IndexedDatabase", features: np.ndarray, peptide_q, discriminant_score, protein_grouping: bool = True,
                    peptide_fdr: float = 0.01, device: int = 0) -> ProteinGroupResult:
     """generate_protein_groups + picked_protein_group (sage-cli runner.rs:539-549) over ALL Features of a run: IDPicker protein
-    groups in two passes, the fallback protein list, and the picked protein-group FDR, on the device (rescore.hip) with the
+    groups in two passes, the fallback protein list, and the picked protein-group FDR, on the device (protein_groups.hip) with the
     graph and the strings built on the host (groups.cpp).  `features`: 1-D array of FEATURE_DTYPE."""
     f = np.ascontiguousarray(features, dtype=L.FEATURE_DTYPE).reshape(-1)
     n = len(f)

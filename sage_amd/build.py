@@ -13,8 +13,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("SAGE_HIP_LIB") or os.path.join(HERE, "libsage_hip.so")  # (override: kernel experiments)
-SOURCES = ["kernels.hip", "process.hip", "index_build.hip", "rescore.hip", "lfq.hip", "tmt.hip", "protein_lfq.hip", "purity.hip", "capi.hip", "capi_db.hip", "capi_psm.hip", "capi_host.cpp", "host_db.cpp", "groups.cpp", "writers.cpp", "mzml_reader.cpp", "mgf_reader.cpp"]
-HEADERS = ["capi_state.h", "localise_math.h", "maxlfq.h", "purity.h", "core.h", "cover.h", "crlog.h", "crlog_tables.h", "detmath.h", "device_types.h", "hip_host.h", "host_db.hpp", os.path.join("..", "..", "include", "sage_hip.h")]
+SOURCES = ["kernels.hip", "process.hip", "index_build.hip", "rescore.hip", "rt_model.hip", "protein_groups.hip", "lfq.hip", "tmt.hip", "protein_lfq.hip", "purity.hip", "capi.hip", "capi_db.hip", "capi_psm.hip", "capi_host.cpp", "host_db.cpp", "groups.cpp", "writers.cpp", "mzml_reader.cpp", "mgf_reader.cpp"]
+HEADERS = ["capi_state.h", "localise_math.h", "maxlfq.h", "post_search.h", "purity.h", "core.h", "cover.h", "crlog.h", "crlog_tables.h", "detmath.h", "device_types.h", "hip_host.h", "host_db.hpp", os.path.join("..", "..", "include", "sage_hip.h")]
 ARCH = "gfx950"
 
 
@@ -79,7 +79,8 @@ def build(force=False, verbose=True):
         return obj
 
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as pool:  # translation units are independent
+    jobs = int(os.environ.get("MAX_JOBS") or 16)  # (os.cpu_count() counts every CPU, also where a build may use a few of them)
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1, jobs)) as pool:  # translation units are independent
         objs = list(pool.map(compile_one, SOURCES))
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", LIB, "-lpthread", "-lz"]
     if verbose:

@@ -11,7 +11,7 @@ device: rescore.hip), label-free MS1 quantification when `quant.lfq` is true (ru
 MaxLFQ roll-up to proteins when `quant.protein_lfq` is true too (an addition, protein_lfq.hip: `protein_lfq.tsv`),
 isobaric-tag (TMT) reporter-ion quantification when `quant.tmt` is set (runner.rs:334-359, 398-410, tmt.hip: `tmt.tsv`),
 IDPicker protein groups with the picked protein-group FDR when the configuration names `protein_grouping` or
-`protein_grouping_peptide_fdr` (runner.rs:539-549, rescore.hip + groups.cpp; see run()) and the optional percolator .pin file;
+`protein_grouping_peptide_fdr` (runner.rs:539-549, protein_groups.hip + groups.cpp; see run()) and the optional percolator .pin file;
 parquet and cloud IO are out of scope.  The search itself runs on the GPU through libsage_hip.so; there is no CPU fallback.
 """
 import argparse

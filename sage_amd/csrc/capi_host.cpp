@@ -47,7 +47,7 @@ int sage_hip_rescore(int device, const SageRescoreInput* in, SageRescoreOutput* 
     return rc == SAGE_HIP_OK ? rc : fail(rc, err);
 }
 
-// protein groups and picked protein-group FDR (rescore.hip, groups.cpp)
+// protein groups and picked protein-group FDR (protein_groups.hip, groups.cpp)
 int sage_hip_protein_groups(int device, const SageHostDb* db, const SageGroupInput* in, SageGroupOutput* out) {
     if (!db || !in || !out) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_protein_groups: null argument");
     if (const int rc = stage_guard("sage_hip_protein_groups", in->n)) return rc;

@@ -1,5 +1,5 @@
 // cover.h — the round logic of the greedy set cover of protein groups (left nodes) over meta-peptides (right nodes),
-// crates/sage/src/protein_grouping.rs:59-156 (BipartiteGraph::into_cover), shared by the device kernels of rescore.hip and by the
+// crates/sage/src/protein_grouping.rs:59-156 (BipartiteGraph::into_cover), shared by the device kernels of protein_groups.hip and by the
 // host (tests/hostemu/cover_emu.cpp runs it on the CPU).  Like core.h: plain functions, no HIP types.
 //
 //   into_cover   while edges remain: trim(); if edges remain: add_largest_to_cover()

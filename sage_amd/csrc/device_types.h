@@ -293,6 +293,7 @@ int rebuild_peptide_major_on_device(const SageTheoretical* d_tm_frag, uint64_t n
 // (build_tile_copy_on_device, build_succinct_lut_on_device, build_peptide_mass_lut: hip_host.h — they fill owning buffers)
 // rescore.hip
 int rescore_on_device(int device, const SageRescoreInput& in, SageRescoreOutput& out, std::string& err);
+// rt_model.hip
 int predict_rt_on_device(int device, const SageRtInput& in, SageRtOutput& out, std::string& err);
 // lfq.hip
 int lfq_on_device(int device, const SageLfqInput& in, const SageLfqMobility* mobility, SageLfqOutput& out, std::string& err);

@@ -1,6 +1,6 @@
 // groups.cpp — the host half of protein grouping (crates/sage/src/protein_grouping.rs:159-231, ProteinGrouper::build): protein
 // numbering, meta-peptides, groups and the edge list of the set cover, from the ascending list of selected peptides.  Strings and
-// orderings of vectors live here; the device (rescore.hip) sees the dense ids this file hands out.
+// orderings of vectors live here; the device (protein_groups.hip) sees the dense ids this file hands out.
 #include <algorithm>
 #include <numeric>
 #include <unordered_map>

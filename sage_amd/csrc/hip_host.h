@@ -103,8 +103,39 @@ struct Ctx {
         if (_e != hipSuccess) return HIP_FAILED(_e, #expr);       \
     } while (0)
 
+// The entry of a whole-call product (sage_hip_rescore, _predict_rt, _protein_groups, _lfq): choose the device, create the call's
+// stream, run body(cx) on it, wait for the stream, and turn a failure into the status and `err`.  `name` heads the message of a
+// failed hipSetDevice, `prefix` is Ctx::prefix.  A Scope is constructed from (device, stream) before the body and destroyed when
+// the call returns: post_search.h's ScratchScope for the calls that allocate from the pool.
+struct NoScope {
+    NoScope(int, hipStream_t) {}
+};
+template <class Scope = NoScope, class Body>
+int run_on_device(int device, const char* name, const char* prefix, std::string& err, Body&& body) {
+    Ctx cx;
+    cx.prefix = prefix;
+    if (hipSetDevice(device) != hipSuccess) {
+        err = std::string(name) + ": hipSetDevice failed";
+        return SAGE_HIP_ERR_NO_DEVICE;
+    }
+    Stream stream;
+    if (!cx.check(stream.create(), "hipStreamCreate")) {
+        err = cx.err;
+        return cx.code;
+    }
+    cx.stream = stream.s;
+    Scope scope(device, cx.stream);
+    const bool ok = body(cx);
+    (void)hipStreamSynchronize(cx.stream);
+    if (!ok) {
+        err = cx.err;
+        return cx.code ? cx.code : SAGE_HIP_ERR_HIP;
+    }
+    return SAGE_HIP_OK;
+}
+
 // rocPRIM's two-call protocol: call(nullptr, bytes) asks for the size of the scratch, call(scratch, bytes) runs in it.  `tmp` (a
-// DevBuf, or rescore.hip's pooled Buf) has to outlive the work, so it is the caller's — or, in the second form, freed on return.
+// DevBuf, or post_search.h's pooled Buf) has to outlive the work, so it is the caller's — or, in the second form, freed on return.
 template <class Scratch, class Call>
 hipError_t with_scratch(Scratch& tmp, Call&& call) {
     size_t bytes = 0;

@@ -140,7 +140,7 @@ struct NameIndex {  // HostDb protein id -> dense id of its name (two FASTA entr
 void build_group_graph(const HostDb& db, const NameIndex& names, const uint32_t* peptides, uint64_t n, GroupGraph& out);
 // ProteinGroup::format: the group's names (decoy tag where decoy && generate_decoys), sorted, joined by '/'
 std::string group_string(const HostDb& db, const GroupGraph& g, uint32_t group);
-// rescore.hip: sage_hip_protein_groups on the device; `strings` receives the distinct protein_groups strings
+// protein_groups.hip: sage_hip_protein_groups on the device; `strings` receives the distinct protein_groups strings
 int protein_groups_on_device(int device, const HostDb& db, const SageGroupInput& in, SageGroupOutput& out, std::vector<std::string>& strings,
                              std::string& err);
 bool write_results_grouped(const char* path, int format, const HostDb& db, const SageFeature* f, uint64_t n, const uint64_t* order,

@@ -956,25 +956,7 @@ bool lfq_impl(Ctx& cx, const SageLfqInput& in, const SageLfqMobility* mobility, 
 }  // namespace
 
 int lfq_on_device(int device, const SageLfqInput& in, const SageLfqMobility* mobility, SageLfqOutput& out, std::string& err) {
-    Ctx cx;
-    cx.prefix = "sage_hip_lfq: ";
-    if (hipSetDevice(device) != hipSuccess) {
-        err = "sage_hip_lfq: hipSetDevice failed";
-        return SAGE_HIP_ERR_NO_DEVICE;
-    }
-    Stream stream;
-    if (!cx.check(stream.create(), "hipStreamCreate")) {
-        err = cx.err;
-        return cx.code;
-    }
-    cx.stream = stream.s;
-    const bool ok = lfq_impl(cx, in, mobility, out);
-    (void)hipStreamSynchronize(cx.stream);
-    if (!ok) {
-        err = cx.err;
-        return cx.code ? cx.code : SAGE_HIP_ERR_HIP;
-    }
-    return SAGE_HIP_OK;
+    return run_on_device(device, "sage_hip_lfq", "sage_hip_lfq: ", err, [&](Ctx& cx) { return lfq_impl(cx, in, mobility, out); });
 }
 
 }  // namespace sagehip

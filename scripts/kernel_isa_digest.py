@@ -8,7 +8,8 @@ hipcc --cuda-device-only -S, gfx950, the flags of sage_amd/build.py.  No GPU nee
 .Lfunc_end, which has its .amdhsa_kernel block inside.  So that a digest moves with the kernel's code and with nothing else, lines
 naming the per-compilation __hip_cuid_<hash> symbol are dropped, runs of blanks collapsed, local labels lose the function's ordinal
 in the file (a neighbour may leave) and the kernel's own symbol is written `@` (a renamed kernel keeps its digest).  The instances
-of a library's templates (rocprim::) are one row: their count and a digest over their rows."""
+of a library's templates (rocprim::) are one row: their count and a digest over their rows.  --library-rows prints them as rows
+of their own instead (the full demangled name, insns, digest), so that their union across translation units can be compared."""
 import hashlib
 import os
 import re
@@ -20,7 +21,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 LIBRARY = "rocprim::"
 
 
-def table(src, extra=()):
+def table(src, extra=(), library_rows=False):
     run = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra, "-x", "hip", src, "-o", "-"], capture_output=True, text=True)
     if run.returncode:
         sys.exit(run.stderr)
@@ -36,9 +37,12 @@ def table(src, extra=()):
         # an instruction line: not blank, not a label, a directive or a comment
         insns = sum(1 for ln in body if ln and not re.match(r"([.;]|\S+: ?(;.*)?$)", ln))
         dem = dem.replace("sagehip::(anonymous namespace)::", "").replace("sagehip::", "").replace("void ", "")
-        dem = re.sub(r"\((?!anonymous).*$", "", dem)
+        if not (library_rows and dem.startswith(LIBRARY)):
+            dem = re.sub(r"\((?!anonymous).*$", "", dem)
         row = (dem, insns, hashlib.sha256("\n".join(body).encode()).hexdigest())
         (library if dem.startswith(LIBRARY) else rows).append(row)
+    if library_rows:
+        return rows + sorted(library)
     if library:
         rows.append((f"{LIBRARY}* ({len(library)} instances)", sum(r[1] for r in library),
                      hashlib.sha256("\n".join(f"{r[0]} {r[2]}" for r in library).encode()).hexdigest()))
@@ -48,7 +52,7 @@ def table(src, extra=()):
 def compare(before, after):
     def read(path):
         with open(path) as fh:
-            return dict((ln[:72].rstrip(), ln.split()[-1]) for ln in fh.read().split("\n")[2:] if ln.strip())
+            return dict((ln.rsplit(None, 2)[0], ln.split()[-1]) for ln in fh.read().split("\n")[2:] if ln.strip())  # (a name may pass column 72)
     a, b = read(before), read(after)
     moved = [k for k in a if k in b and a[k] != b[k]]
     print(f"{len(a)} rows before, {len(b)} after, {sum(k in b for k in a)} in both, {len(moved)} of those with another digest")
@@ -66,8 +70,9 @@ if __name__ == "__main__":
     if args[:1] == ["--compare"]:
         sys.exit(compare(args[1], args[2]))
     src = next((a for a in args if not a.startswith("-")), os.path.join(ROOT, "sage_amd", "csrc", "kernels.hip"))
-    extra = [a for a in args if a.startswith("-")]
+    library_rows = "--library-rows" in args
+    extra = [a for a in args if a.startswith("-") and a != "--library-rows"]
     print(f"# hipcc {' '.join(FLAGS + extra)} {os.path.relpath(src, ROOT)}")
     print(f"{'kernel':<72} {'insns':>7}  sha256")
-    for r in table(src, extra):
+    for r in table(src, extra, library_rows):
         print(f"{r[0]:<72} {r[1]:>7}  {r[2]}")

@@ -1,6 +1,6 @@
 """A second reading of the predict_rt block (sage-cli runner.rs:513-530) in numpy and Python integers, written from the
 reference's ml/qvalue.rs, ml/retention_alignment.rs, ml/retention_model.rs, ml/mobility_model.rs and ml/regression.rs.  It shares
-nothing with linreg_fit / rt_embed / im_embed of oracle/rescore_oracle.cpp or with sage_amd/csrc/rescore.hip, except the
+nothing with linreg_fit / rt_embed / im_embed of oracle/rescore_oracle.cpp or with sage_amd/csrc/rt_model.hip, except the
 Gauss-Jordan solve, which it takes from the oracle (oracle_lib.gauss_solve, held to gauss.rs by tests/test_rescore_oracle.py).
 
 It is for the order-free worlds of tests/rt_model_worlds.py: X^T X, X^T y, sum y, sum y^2 and the count are accumulated as exact

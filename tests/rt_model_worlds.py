@@ -1,5 +1,5 @@
 """Order-free worlds for the retention-time and ion-mobility models of the predict_rt block (xtx_kernel, fold_partials_kernel,
-predict_kernel and the host gauss_solve of sage_amd/csrc/rescore.hip).
+predict_kernel of sage_amd/csrc/rt_model.hip and the host gauss_solve of rescore.hip).
 
 The normal equations of both models are rank deficient and solved through a 1e-8 regulariser, so a last-bit difference in
 X^T X grows, and a comparison of predictions needs a tolerance that also lets a lost training row through.  Here every entry of
@@ -29,7 +29,7 @@ import numpy as np
 from sage_amd.synthetic import _AA, _FREQ, synthetic_rt_world
 
 N_FILES = 3
-# fit_and_predict's launch (rescore.hip): nb = min(256, max(1, ceil(n / 256))) blocks of xtx_kernel, per = ceil(n / nb) rows per
+# fit_and_predict's launch (rt_model.hip): nb = min(256, max(1, ceil(n / 256))) blocks of xtx_kernel, per = ceil(n / nb) rows per
 # block, embedded XTX_STAGE rows at a time; predict_kernel runs PRED_THREADS rows per block
 XTX_MAX_BLOCKS, XTX_ROWS, XTX_STAGE, PRED_THREADS = 256, 256, 16, 64
 SIZES = (255, 256, 257, 4097, 65536, 65537)

@@ -82,6 +82,26 @@ def test_small_random_worlds(gpu_required):
     assert both == 30
 
 
+def test_without_the_pool_the_outputs_are_the_pooled_ones(gpu_required, monkeypatch):
+    """the first world of test_small_random_worlds with SAGE_HIP_NO_POOL=1 (read once per call): every scratch buffer a plain
+    hipMalloc, the outputs those of the pooled call and of the restatement"""
+    rng = np.random.default_rng(77)
+    blocks = make_blocks(rng, 160)
+    n_proteins = int(rng.integers(30, 51))
+    built = build_world(random_incidence(rng, n_proteins, int(rng.integers(n_proteins, 161)), shared=float(rng.uniform(0.2, 0.8))), blocks)
+    f = feature_table(built, rng, 150)
+    q, score = draw_peptide_q(f, rng), scores_for(f, rng)
+    monkeypatch.delenv("SAGE_HIP_NO_POOL", raising=False)
+    pooled = protein_groups(built.host, f, q, score)
+    monkeypatch.setenv("SAGE_HIP_NO_POOL", "1")
+    got = protein_groups(built.host, f, q, score)
+    assert_equal(got, expected_of(built.world, f, q, score), "no pool")
+    for name, x in vars(got).items():
+        if name not in ("device_ms", "host_graph_ms"):  # (the two measured times)
+            y = getattr(pooled, name)
+            assert x == y if isinstance(x, (list, int)) else np.array_equal(x, y, equal_nan=True), name
+
+
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_large_worlds_on_both_routes(seed, gpu_required, monkeypatch):
     """3 000 proteins, 12 000 blocks, 20 000 features, rings that need add_largest_to_cover picks: the default cap, the bulk route

@@ -242,6 +242,33 @@ def test_predict_rt_degenerate_inputs(gpu_required):
         predict_rt(f, 1, off, seq, mono)  # file_id 1 with n_files 1
 
 
+def _same_fields(a, b, context):
+    """every output of two calls equal, NaNs matched; device_ms, the one field that is a measured time, aside"""
+    for name, x in vars(a).items():
+        y = getattr(b, name)
+        if name == "alignments":  # a structured array: column by column
+            assert all(_same(x[k], y[k]) for k in x.dtype.names), (context, name)
+        elif name != "device_ms":
+            assert _same(x, y), (context, name)
+
+
+def test_without_the_pool_the_outputs_are_the_pooled_ones(gpu_required, monkeypatch):
+    """SAGE_HIP_NO_POOL=1, read once per call: every scratch buffer of the call is a plain hipMalloc.  2 500 rows with a constant
+    ims column cross the 1 024-element block of the blocked sums and the 1 024-row tile of the picked competitions' sequential sum."""
+    from sage_amd.api import predict_rt
+    from sage_amd.synthetic import synthetic_rt_world
+    tol = Tolerance("ppm", -10.0, 10.0)
+    calls = [(f"rescore n={n}", lambda a=synthetic_features(n, seed=seed, **kw): rescore(a[0], tol, *a[1:]))
+             for n, seed, kw in ((300, 6, {}), (2500, 17, {"zero_ims": True}))]
+    world = synthetic_rt_world(500, 1, seed=10)
+    calls.append(("predict_rt", lambda: predict_rt(world[0], 1, *world[1:])))
+    for context, call in calls:
+        monkeypatch.delenv("SAGE_HIP_NO_POOL", raising=False)
+        pooled = call()
+        monkeypatch.setenv("SAGE_HIP_NO_POOL", "1")
+        _same_fields(call(), pooled, context)
+
+
 def test_search_predict_rescore_chain(gpu_required):
     """search -> predict_rt -> rescore with the model outputs as LDA features, against the oracle's chain"""
     from sage_amd.api import predict_rt
