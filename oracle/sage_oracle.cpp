@@ -887,6 +887,12 @@ int get_log_mode() { return g_log_mode; }
 double ln_correctly_rounded(double x) { return (double)logq((__float128)x); }
 double ln(double x) { return g_log_mode ? ln_correctly_rounded(x) : std::log(x); }
 
+// f32::ln_1p of the second score type (scoring.rs:187-199) follows the same two modes: Rust lowers it to the platform's
+// `log1pf`, which glibc 2.35 does NOT round correctly (0.65 % of the positive arguments are one ulp off: tests/test_ln1pf_cpu.py),
+// so mode 0 is a property of the host's libm.  Mode 1 is libquadmath's 113-bit log1pq rounded once to f32: the value the
+// product computes (crlog.h: cr_log1pf), obtained independently of it.
+float ln_1p_f32(float x) { return g_log_mode ? (float)log1pq((__float128)x) : log1pf(x); }
+
 double lnfact(uint16_t n) {  // scoring.rs:170-177
     if (n == 0) return 1.0;
     double x = (double)n;
@@ -901,7 +907,7 @@ double score_type_score(ScoreType t, uint16_t matched_b, uint16_t matched_y, flo
         score = ln(i) + lnfact(matched_b) + lnfact(matched_y);
     } else {
         float summed_intensity = summed_b + summed_y;
-        score = (double)log1pf(summed_intensity) + lnfact(matched_b) + lnfact(matched_y);
+        score = (double)ln_1p_f32(summed_intensity) + lnfact(matched_b) + lnfact(matched_y);
     }
     return std::isfinite(score) ? score : 255.0;
 }

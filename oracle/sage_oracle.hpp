@@ -334,6 +334,7 @@ void set_log_mode(int mode);
 int get_log_mode();
 double ln(double x);
 double ln_correctly_rounded(double x);
+float ln_1p_f32(float x);  // f32::ln_1p: mode 0 = the platform's log1pf, 1 = log1pq rounded once
 double score_type_score(ScoreType t, uint16_t matched_b, uint16_t matched_y, float summed_b,
                         float summed_y);  // scoring.rs:179-201
 uint8_t max_fragment_charge(std::optional<uint8_t> max_fragment_charge, uint8_t precursor_charge);  // :239-247

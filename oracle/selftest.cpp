@@ -90,6 +90,19 @@ static void test_scoring_units() {  // scoring.rs:799-830
     CHECK(max_fragment_charge(uint8_t(2), 4) == 3);
     CHECK(max_fragment_charge(uint8_t(4), 1) == 2);
     CHECK(lnfact(0) == 1.0);  // the reference's quirk, scoring.rs:171-172
+    // f32::ln_1p of OpenMSHyperScore in the two log modes: 8.4726 (0x41078feb) is an argument where the correctly rounded double
+    // rounds to the wrong float (0x400fe5e8 for 0x400fe5e7)
+    const int mode = get_log_mode();
+    volatile float hard_arg = 0x1.0f1fd6p+3f;  // (volatile: the compiler would fold log1pf of a constant, correctly rounded)
+    const float hard = hard_arg;
+    set_log_mode(1);
+    CHECK(ln_1p_f32(hard) == 0x1.1fcbcep+1f && ln_1p_f32(hard) != (float)std::log1p((double)hard));
+    CHECK(ln_1p_f32(0.0f) == 0.0f && std::signbit(ln_1p_f32(-0.0f)) && ln_1p_f32(-1.0f) == -INFINITY && std::isnan(ln_1p_f32(-2.0f)));
+    CHECK(score_type_score(ScoreType::OpenMSHyperScore, 1, 0, hard, 0.0f) == (double)0x1.1fcbcep+1f + lnfact(1) + lnfact(0));
+    CHECK(score_type_score(ScoreType::OpenMSHyperScore, 1, 0, -1.0f, 0.0f) == 255.0);
+    set_log_mode(0);
+    CHECK(ln_1p_f32(hard) == log1pf(hard));
+    set_log_mode(mode);
 }
 
 static bool within(const std::vector<float>& obs, const std::vector<float>& exp, float charge, float add = 0.f) {

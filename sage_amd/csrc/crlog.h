@@ -221,4 +221,56 @@ SAGE_HD double cr_log(double x) {
     return cr_log_accurate(a.e, a.t, a.r);
 }
 
+// ---- f32::ln_1p, correctly rounded: the `ln_1p()` of OpenMSHyperScore (scoring.rs:187-199) ------------------------------------
+// The IEEE round-to-nearest-even f32 of the exact ln(1 + x) for every one of the 2^32 bit patterns (+0 -> +0, -0 -> -0,
+// -1 -> -inf, x < -1 and NaN -> NaN, +inf -> +inf), in two pieces so that a kernel runs its ONE inlined cr_log on either score
+// type's argument:
+//     cr_log1pf(x) = cr_ln1p_round(x, cr_log(cr_ln1p_arg(x)))
+//   |x| <  2^-29: the result is x.  ln(1 + x) = x (1 - x/2 + x^2/3 - ...) lies within |x|^2/2 (1 + |x|) < 2^-30 |x| of x, and the
+//                 nearest rounding boundary next to an f32 x is at least 2^-26 |x| away (a power of two's lower neighbour; a
+//                 subnormal's are farther).  The logarithm's value is not looked at: 1 + x is not exact there.
+//   |x| >= 2^-29: 1.0 + (double)x is exact up to 2^53 (24 bits between 2^-52 and 2^53); above, its error is below 2^-53 of
+//                 the argument: 2^-58 of the result.  So d = cr_log(1 + x) is the correctly rounded DOUBLE of ln(1 + x) (or within
+//                 2^-58 of it), and (float)d is the correctly rounded float unless d sits on the midpoint of two floats — then
+//                 the second rounding goes to even without knowing on which side of d the logarithm lies (ln(1 + x) is never
+//                 a midpoint itself: it is transcendental).  That happens for the arguments of CR_LOG1PF_EXCEPT and for no
+//                 others: tests/test_ln1pf_cpu.py compares all 2^32 patterns with libquadmath's log1pq rounded once.  The table
+//                 holds the argument and the result (the way CORE-MATH closes its f32 functions): no second logarithm, no
+//                 tail carried out of cr_log — the callers are kernels at the edge of their register budget.
+SAGE_HD uint32_t crl_bits32(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __float_as_uint(x);
+#else
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    return u;
+#endif
+}
+SAGE_HD float crl_from_bits32(uint32_t u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __uint_as_float(u);
+#else
+    float x;
+    memcpy(&x, &u, 4);
+    return x;
+#endif
+}
+SAGE_HD double cr_ln1p_arg(float x) { return 1.0 + (double)x; }
+// (argument, result): the nine arguments whose double logarithm ends in 0x10000000 — the midpoint — and whose logarithm lies on
+// the odd side of it.  0x41078feb is 8.4726; the negative three are -7.15e-7, -8.58e-6 and -2.18e-3.
+#define SAGE_CR_LOG1PF_EXCEPT(X)                                                                                                  \
+    X(0x35400003u, 0x353fffffu) X(0x3710001bu, 0x370ffff3u) X(0x3efd81adu, 0x3ecdeee1u) X(0x41078febu, 0x400fe5e7u)             \
+    X(0x65d890d3u, 0x4254d1f9u) X(0x6f31a8ecu, 0x42845a89u) X(0xb53ffffdu, 0xb5400001u) X(0xb70fffe5u, 0xb710000du)             \
+    X(0xbb0ec8c4u, 0xbb0ef0a5u)
+SAGE_HD float cr_ln1p_round(float x, double ln_arg) {  // ln_arg = cr_log(cr_ln1p_arg(x))
+    const uint32_t u = crl_bits32(x);
+    if ((u & 0x7FFFFFFFu) < 0x31000000u) return x;  // |x| < 2^-29, both zeros
+    uint32_t y = crl_bits32((float)ln_arg);
+#define X(arg, res) y = u == arg ? res : y;
+    SAGE_CR_LOG1PF_EXCEPT(X)
+#undef X
+    return crl_from_bits32(y);
+}
+SAGE_HD float cr_log1pf(float x) { return cr_ln1p_round(x, cr_log(cr_ln1p_arg(x))); }
+
 }  // namespace sagecore

@@ -2809,16 +2809,15 @@ __device__ __forceinline__ double lnfact_dev(uint32_t n, const double* __restric
 }
 
 // ScoreType::score, scoring.rs:179-201.  `ln_i` = ln((summed_b + 1) as f64 * (summed_y + 1) as f64), correctly rounded
-// (cr_log_pair below); OpenMSHyperScore takes its f32 ln_1p here.
-__device__ __forceinline__ double hyperscore_arg(const Score& s) { return (double)(s.summed_b + 1.0f) * (double)(s.summed_y + 1.0f); }
+// (cr_log_pair below).  OpenMSHyperScore's f32 `ln_1p(summed_b + summed_y)` comes out of the SAME logarithm: its argument is
+// 1 + (summed_b + summed_y) as a double, and `ln_i` of that is rounded once more to f32 (crlog.h: cr_ln1p_arg, cr_ln1p_round —
+// correctly rounded for every f32, tests/test_ln1pf_cpu.py).  The score type costs the kernels a select between two arguments.
+__device__ __forceinline__ double hyperscore_arg(int score_type, const Score& s) {
+    return score_type == 0 ? (double)(s.summed_b + 1.0f) * (double)(s.summed_y + 1.0f) : cr_ln1p_arg(s.summed_b + s.summed_y);
+}
 __device__ __forceinline__ double hyperscore_dev(int score_type, const Score& s, const double ln_i, const double* table, uint32_t tn) {
-    double score;
-    if (score_type == 0) {
-        score = ln_i + lnfact_dev(s.matched_b, table, tn) + lnfact_dev(s.matched_y, table, tn);
-    } else {
-        const float si = s.summed_b + s.summed_y;
-        score = (double)log1pf(si) + lnfact_dev(s.matched_b, table, tn) + lnfact_dev(s.matched_y, table, tn);
-    }
+    const double ln = score_type == 0 ? ln_i : (double)cr_ln1p_round(s.summed_b + s.summed_y, ln_i);
+    const double score = ln + lnfact_dev(s.matched_b, table, tn) + lnfact_dev(s.matched_y, table, tn);
     return __builtin_isfinite(score) ? score : 255.0;
 }
 // The two logarithms of a rescoring round through ONE inlined copy of cr_log (crlog.h): ln(x) always, ln(lambda) when
@@ -3856,7 +3855,7 @@ __device__ __forceinline__ bool rescore_spectrum(const DevDbView& db, const DevS
         double h = 0.0;
         bool pass = false;
         bool ln_undecided;
-        const double ln_i = cr_log_pair<ACC>(hyperscore_arg(s), lambda, round == 0, ((__ballot(valid) >> 63) & 1ull) == 0ull, ln_lambda, ln_undecided);
+        const double ln_i = cr_log_pair<ACC>(hyperscore_arg(la.score_type(), s), lambda, round == 0, ((__ballot(valid) >> 63) & 1ull) == 0ull, ln_lambda, ln_undecided);
         if (__builtin_expect(!ACC && __ballot(ln_undecided && (valid || round == 0)) != 0ull, 0)) {
             // (the hot instance carries the logarithm's fast phase only: this spectrum again in the retry pass, like a tie)
             if (queue_on_tie && lane == 0) {
@@ -4163,7 +4162,7 @@ __global__ __launch_bounds__(64) void rescore_big_kernel(DevDbView db, DevScorer
                 double h = 0.0;
                 bool pass = false;
                 bool ln_undecided;  // (never: both phases)
-                const double ln_i = cr_log_pair<true>(hyperscore_arg(s), lambda, round == 0 && base == 0, false, ln_lambda, ln_undecided);
+                const double ln_i = cr_log_pair<true>(hyperscore_arg(sc.score_type, s), lambda, round == 0 && base == 0, false, ln_lambda, ln_undecided);
                 if (valid) {
                     s.ppm_difference /= s.summed_b + s.summed_y;  // scoring.rs:759
                     h = hyperscore_dev(sc.score_type, s, ln_i, lnfact_table, lnfact_n);
@@ -4770,7 +4769,7 @@ __global__ __launch_bounds__(64) void candidates_kernel(DevDbView db, DevScorer 
             }
             double ln_lambda;
             bool undecided;
-            const double ln_i = cr_log_pair<true>(hyperscore_arg(mine), 1.0, false, false, ln_lambda, undecided);
+            const double ln_i = cr_log_pair<true>(hyperscore_arg(sc.score_type, mine), 1.0, false, false, ln_lambda, undecided);
             const double h = hyperscore_dev(sc.score_type, mine, ln_i, lnfact_table, lnfact_n);
             if (lane < nb) {
                 SageCandidateScore* o = out + cb + lane;

@@ -66,6 +66,23 @@ def lnfact(n):
     return n * math.log(n) - n + 0.5 * math.log(n) + 0.5 * math.log(math.pi * 2.0 * n)
 
 
+def ln_1p_f32(x):
+    """f32::ln_1p, correctly rounded: ln(1 + x) to 200 bits (mpmath), then the nearest f32 chosen by exact comparison among the
+    double-rounded value and its two neighbours — ONE rounding, independent of crlog.h and of the oracle's libquadmath."""
+    import mpmath
+    x = f32(x)
+    if np.isnan(x) or x < f32(-1.0):
+        return f32(np.nan)
+    if x == f32(-1.0):
+        return f32(-np.inf)
+    if x == 0 or np.isinf(x):
+        return x
+    with mpmath.workprec(200), np.errstate(all="ignore"):
+        v = mpmath.log1p(mpmath.mpf(float(x)))
+        c = f32(float(v))
+        return min((np.nextafter(c, f32(-np.inf)), c, np.nextafter(c, f32(np.inf))), key=lambda t: abs(mpmath.mpf(float(t)) - v))
+
+
 def score_type_score(score_type, matched_b, matched_y, summed_b, summed_y):
     """ScoreType::score, scoring.rs:179-201"""
     with np.errstate(all="ignore"):
@@ -73,7 +90,7 @@ def score_type_score(score_type, matched_b, matched_y, summed_b, summed_y):
             i = float(f32(summed_b) + f32(1.0)) * float(f32(summed_y) + f32(1.0))
             s = (math.log(i) if i > 0 else (float("-inf") if i == 0 else float("nan"))) + lnfact(matched_b) + lnfact(matched_y)
         else:
-            s = float(np.log1p(f32(summed_b) + f32(summed_y))) + lnfact(matched_b) + lnfact(matched_y)
+            s = float(ln_1p_f32(f32(summed_b) + f32(summed_y))) + lnfact(matched_b) + lnfact(matched_y)
     return s if math.isfinite(s) else 255.0
 
 

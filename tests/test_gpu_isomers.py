@@ -105,11 +105,9 @@ def _hold_to_the_oracle(w, params, batch, context):
             assert int(g["longest_b"]) == int(o["longest_b"]) and int(g["longest_y"]) == int(o["longest_y"]), ctx
             assert np.float32(g["average_ppm"]).view(np.uint32) == np.float32(o["average_ppm"]).view(np.uint32), ctx
             assert (np.float32(g["summed_b"]) + np.float32(g["summed_y"])).view(np.uint32) == np.float32(o["ms2_intensity"]).view(np.uint32), ctx
-            if params.score_type == "SageHyperScore":
-                assert np.float64(g["hyperscore"]).view(np.uint64) == np.float64(o["hyperscore"]).view(np.uint64), \
-                    f"{ctx}: hyperscore {g['hyperscore']!r} vs {o['hyperscore']!r}"
-            else:  # f32 ln_1p: the 1e-6 tests/test_gpu_parity.py grants this score type
-                assert abs(float(g["hyperscore"]) - float(o["hyperscore"])) <= 1e-6 * max(abs(float(o["hyperscore"])), 1.0), ctx
+            # (both score types: the f64 ln and the f32 ln_1p are correctly rounded on both sides)
+            assert np.float64(g["hyperscore"]).view(np.uint64) == np.float64(o["hyperscore"]).view(np.uint64), \
+                f"{ctx}: hyperscore {g['hyperscore']!r} vs {o['hyperscore']!r}"
             seen_charges.add(int(o["charge"]))
             n += 1
     return n, seen_charges, mixed

@@ -21,10 +21,8 @@ def product_process(top_n, deiso, min_mz, mz, it, z):
 def check(dev, orc, batch, params, context, hits=True, every=1):
     """One scorer configuration on a ready device database, oracle and batch: the preliminary lists, every Feature field, a second
     step on the same handle and the host-to-host entry point.  Returns (PSMs, the first step's timing)."""
-    # OpenMSHyperScore goes through f32 ln_1p: device libm and glibc may differ by an f32 ulp (~6e-8 relative).
-    # SageHyperScore uses f64 ln only — correctly rounded on both sides: the f64 fields are held to EQUALITY
-    # (parity_utils.assert_features_equal).  North-star tolerance: 1e-4.
-    rel_tol = 1e-6 if params.score_type == "OpenMSHyperScore" else None
+    # Both score types: the f64 fields are held to EQUALITY (parity_utils.assert_features_equal).  SageHyperScore's f64 ln and
+    # OpenMSHyperScore's f32 ln_1p are correctly rounded on both sides (crlog.h: cr_log, cr_log1pf; the oracle's libquadmath).
     scorer = Scorer(dev, params)
     dbatch = scorer.upload(batch)
     if hits:
@@ -33,7 +31,7 @@ def check(dev, orc, batch, params, context, hits=True, every=1):
     gf, gc = gf.copy(), gc.copy()
     t_first = scorer.last_timing()
     of, oc, _, _ = orc.score(params, batch)
-    n = assert_features_equal(gf, gc, of, oc, context, rel_tol)
+    n = assert_features_equal(gf, gc, of, oc, context)
     # once more on the same handle: the first step of a handle launches its exact retry pass; a later narrow-search step only when
     # the step before had something to retry.  This repeat of the SAME batch reaches "left out, nothing found" or "not left out",
     # never the late launch (left out, retries found): tests/test_gpu_handle_sequences.py walks that route
@@ -42,7 +40,7 @@ def check(dev, orc, batch, params, context, hits=True, every=1):
         gfb[np.arange(gf.shape[1])[None, :] < gc[:, None]].tobytes(), f"{context}: the second step on the same scorer differs"
     assert scorer.last_timing()["n_retry"] == t_first["n_retry"], context
     gf2, gc2 = scorer.score(batch)  # the upload+score+download entry point
-    assert_features_equal(gf2, gc2, of, oc, context + " (score_batch)", rel_tol)
+    assert_features_equal(gf2, gc2, of, oc, context + " (score_batch)")
     return n, t_first
 
 
@@ -97,6 +95,32 @@ def test_hyperscores_against_the_platform_libm(small_world):
     assert n > 1000
     of1, oc1, _, _ = w.orc.score(params, w.batch)
     assert_features_equal(gf, gc, of1, oc1, "correctly rounded")
+
+
+def test_openms_hyperscores_against_the_platform_libm(small_world):
+    """OpenMSHyperScore against the oracle with the platform's log1pf (the reference's arithmetic on this host), without a
+    tolerance: the oracle ALONE says which PSMs the platform's libm leaves as they are — those whose records under the platform
+    libm and under correct rounding are identical — and on exactly those the device must equal the platform-libm oracle, every
+    field.  Their share is a fact about the host's libm (glibc 2.35's log1pf is an ulp off on ~2.4 % of [1, 1e7]): printed, no
+    threshold.  Under correct rounding every record is equal (check())."""
+    w = small_world
+    params = ScorerParams(report_psms=5, min_matched_peaks=1, precursor_tol=Tolerance("da", -3.0, 3.0), score_type="OpenMSHyperScore")
+    scorer = Scorer(w.dev, params)
+    gf, gc = scorer.score_resident(scorer.upload(w.batch))
+    of1, oc1, _, _ = w.orc.score(params, w.batch)
+    n = assert_features_equal(gf, gc, of1, oc1, "OpenMS, correctly rounded")
+    with oracle_lib.LogMode(0):
+        of0, oc0, _, _ = w.orc.score(params, w.batch)
+    assert np.array_equal(oc0, oc1)
+    reported = np.arange(of1.shape[1])[None, :] < oc1[:, None]
+    names = [k for k in of1.dtype.names if k != "pad"]
+    untouched = reported & np.logical_and.reduce([(of0[k] == of1[k]) | ((of0[k] != of0[k]) & (of1[k] != of1[k])) for k in names])
+    print(f"OpenMSHyperScore: {int(untouched.sum())} of {n} PSMs ({100.0 * untouched.sum() / n:.2f} %) are the same under the "
+          f"platform's log1pf and under correct rounding")
+    for k in names:
+        a, b = gf[k][untouched], of0[k][untouched]
+        assert np.all((a == b) | ((a != a) & (b != b))), f"platform libm: field {k} differs on a PSM the libm leaves as it is"
+    assert n > 1000 and untouched.any()
 
 
 def test_narrow_search_known_charge(small_world):

@@ -83,8 +83,7 @@ def test_second_reading_reproduces_the_references_known_answer():
         p = integration_scorer()
         for k, v in kw.items():
             setattr(p, k, v)
-        hold_oracle_to_second_reading(orc, dbp, p, batch, f64_tol=1e-6 if p.score_type != "SageHyperScore" else 1e-12,
-                                      context=f"C1 {kw}")
+        hold_oracle_to_second_reading(orc, dbp, p, batch, context=f"C1 {kw}")
 
 
 def _world(n_proteins, seed, dbkw, n_spectra, spec_seed, speckw, quantize=None):
@@ -124,9 +123,9 @@ CASES = {
                             dict(wide_window=True, chimera=True, report_psms=3), 1e-12),
     "chimera_narrow": (dict(n_proteins=1000, seed=15, dbkw=_TRYPTIC, n_spectra=40, spec_seed=105, speckw=dict(chimeric=2)),
                        dict(chimera=True, report_psms=3, min_matched_peaks=3), 1e-12),
-    # the other ScoreType (f32 ln_1p: numpy's log1pf and the oracle's may differ by an f32 ulp → 1e-6)
+    # the other ScoreType: f32 ln_1p, correctly rounded on both sides (the oracle's log1pq, second_reading.ln_1p_f32 through mpmath)
     "openms_score": (dict(n_proteins=1000, seed=16, dbkw=_TRYPTIC, n_spectra=60, spec_seed=106, speckw=dict()),
-                     dict(score_type="OpenMSHyperScore", report_psms=4, min_matched_peaks=1), 1e-6),
+                     dict(score_type="OpenMSHyperScore", report_psms=4, min_matched_peaks=1), 1e-12),
     # all six ion kinds, min_ion_index 1, no decoys, Da fragment tolerance, asymmetric precursor tolerance
     "abcxyz_da": (dict(n_proteins=1500, seed=17, dbkw=dict(bucket_size=256, ion_kinds=["a", "b", "c", "x", "y", "z"],
                                                          min_ion_index=1, generate_decoys=False,
