@@ -954,6 +954,65 @@ int sage_hip_write_purity(const char* path, uint64_t n_rows, const uint64_t* psm
                           const uint8_t* charge, const char* const* ms1_ids, const float* isolation_lo, const float* isolation_hi,
                           const SagePurityOutput* result, const char* const* filenames, uint32_t n_files);
 
+/* ---- protein-level roll-up of TMT reporter intensities (what follows tmt.tsv in every TMT workflow: filter, equalise the channel
+ * loading, one abundance per protein and channel).  An addition over the reference, additive to ABI 6; the contract is DESIGN.md 7i
+ * and sage_amd/csrc/tmt_rollup.h, stated again in tests/tmt_rollup_reference.py.  One call is one plex: rows that share their
+ * channels.  All arithmetic is IEEE f64 without FMA.  For rows r, channels k, groups g:
+ *   1. v = (double)intensity[r][k]; the cell is present when v > 0 && v < +inf (NaN, +-0.0, negatives and +inf are missing).  A row
+ *      is used when group_of_row[r] != 0xFFFFFFFF and it has at least max(min_present, 1) present cells.
+ *   2. block b holds the input rows [1024 b, 1024 (b + 1)).  P[b][k] = the sum of the present cells of channel k over the used rows
+ *      of block b, from +0.0 in ascending row index; S[k] (column_sum) = the sum of P[b][k] from +0.0 in ascending b; C[k] = the
+ *      number of present cells of channel k over the used rows.
+ *   3. normalise None: f[k] = 1.0.  Total: M = (the sum of S[k] over the channels with C[k] > 0, ascending k, from +0.0) / their
+ *      number; f[k] (factor) = M / S[k] where C[k] > 0, else 1.0.  w[r][k] = v * f[k].
+ *   4. summary Sum: abundance[g][k] = the sum of w[r][k] over the used rows of g whose cell is present, from +0.0 in ascending row
+ *      index; n_cells[g][k] their number; log_abundance = the correctly rounded ln(abundance) (crlog.h) where n_cells > 0, else NaN
+ *      with abundance +0.0.
+ *   5. summary Median: l = ln(w) (correctly rounded) of every present cell; the row's centre c[r] = (the sum of its present l,
+ *      ascending k, from +0.0) / their number; d[r][k] = l - c[r]; med[g][k] = the exact median of d over the used rows of g whose
+ *      cell is present (ranks (n - 1) / 2 and n / 2 in ascending order; odd n: the middle element, even: (lo + hi) * 0.5);
+ *      a[g] = (the sum of c[r] over the used rows of g, ascending row index, from +0.0) / n_rows_used[g];
+ *      log_abundance = med + a, NaN where n_cells == 0; abundance = det_exp(log_abundance) (detmath.h), 0.0 where not quantified.
+ * Checked before the device is touched: a NULL array with n_rows > 0, a group id >= n_groups other than 0xFFFFFFFF, normalise or
+ * summary out of range, n_labels == 0 with n_rows > 0: SAGE_HIP_ERR_INVALID.  n_labels > 65 535 or n_rows >= 2^31:
+ * SAGE_HIP_ERR_UNSUPPORTED.  n_groups == 0: SAGE_HIP_OK, nothing written.  n_rows == 0, or no used row: SAGE_HIP_OK without a
+ * summary launch, every group not quantified, factors 1.0, column sums 0.0.
+ * n_used_rows: the used rows.  n_long_groups: the groups whose medians were selected by passes over their columns in global memory
+ * (more used rows than a wavefront's LDS slice holds, 1 024; 0 for Sum).  n_label_slabs: the slabs of 64 channels a wavefront of
+ * the summary kernel walks for one group, ceil(n_labels / 64); 0 without a summary launch.  norm_ms: upload, presence, grouping,
+ * column sums and factors; summary_ms: centres and the summary kernels; device_ms: all of it, copies back included (HIP events). */
+enum { SAGE_TMT_NORMALISE_NONE = 0, SAGE_TMT_NORMALISE_TOTAL = 1 };
+enum { SAGE_TMT_SUMMARY_SUM = 0, SAGE_TMT_SUMMARY_MEDIAN = 1 };
+
+typedef struct SageTmtRollupInput {
+    uint64_t n_rows;
+    uint32_t n_labels, n_groups, min_present;
+    int32_t normalise, summary;
+    const float* intensity;           /* [n_rows * n_labels], row-major (SageTmtOutput.intensity) */
+    const uint32_t* group_of_row;     /* [n_rows] */
+} SageTmtRollupInput;
+
+typedef struct SageTmtRollupOutput {  /* caller-allocated */
+    double* abundance;                /* [n_groups * n_labels] */
+    double* log_abundance;
+    uint32_t* n_cells;
+    uint32_t* n_rows_used;            /* [n_groups] */
+    double* factor;                   /* [n_labels] */
+    double* column_sum;
+    uint64_t n_used_rows;
+    uint32_t n_long_groups, n_label_slabs;
+    float norm_ms, summary_ms, device_ms;
+} SageTmtRollupOutput;
+
+int sage_hip_tmt_rollup(int device, const SageTmtRollupInput* in, SageTmtRollupOutput* out);
+
+/* tmt_proteins.tsv / tmt_peptides.tsv: `first_header` ("proteins" or "peptide"), plex, n_psms, n_peptides, then one abundance per
+ * channel header (ryu f64; 0.0 where not quantified); one row per entry, in the order given: names[r], plex[r], n_psms[r],
+ * n_peptides[r], abundance[r * n_labels ..]. */
+int sage_hip_write_tmt_rollup(const char* path, const char* first_header, const char* const* headers, uint32_t n_labels, uint64_t n_out,
+                              const char* const* names, const uint32_t* plex, const uint32_t* n_psms, const uint32_t* n_peptides,
+                              const double* abundance);
+
 const char* sage_hip_last_error(void);
 int sage_hip_abi_version(void);
 

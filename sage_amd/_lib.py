@@ -264,6 +264,18 @@ class SageProteinLfqOutput(C.Structure):
                 ("n_batches", C.c_uint32)]
 
 
+class SageTmtRollupInput(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_labels", C.c_uint32), ("n_groups", C.c_uint32), ("min_present", C.c_uint32),
+                ("normalise", C.c_int32), ("summary", C.c_int32), ("intensity", c_float_p), ("group_of_row", c_u32_p)]
+
+
+class SageTmtRollupOutput(C.Structure):
+    _fields_ = [("abundance", C.POINTER(C.c_double)), ("log_abundance", C.POINTER(C.c_double)), ("n_cells", c_u32_p),
+                ("n_rows_used", c_u32_p), ("factor", C.POINTER(C.c_double)), ("column_sum", C.POINTER(C.c_double)),
+                ("n_used_rows", C.c_uint64), ("n_long_groups", C.c_uint32), ("n_label_slabs", C.c_uint32),
+                ("norm_ms", C.c_float), ("summary_ms", C.c_float), ("device_ms", C.c_float)]
+
+
 class SagePuritySettings(C.Structure):
     _fields_ = [("ppm_tolerance", C.c_float), ("default_isolation_lo", C.c_float), ("default_isolation_hi", C.c_float),
                 ("max_isotope", C.c_uint32)]
@@ -442,6 +454,9 @@ def load():
         "sage_hip_protein_lfq": (C.c_int, [C.c_int, C.POINTER(SageProteinLfqInput), C.POINTER(SageProteinLfqOutput)]),
         "sage_hip_write_protein_lfq": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, c_u32_p, C.c_uint32,
                                                  C.POINTER(SageProteinLfqOutput), C.POINTER(C.c_char_p), C.c_uint32]),
+        "sage_hip_tmt_rollup": (C.c_int, [C.c_int, C.POINTER(SageTmtRollupInput), C.POINTER(SageTmtRollupOutput)]),
+        "sage_hip_write_tmt_rollup": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.POINTER(C.c_char_p),
+                                                c_u32_p, c_u32_p, c_u32_p, C.POINTER(C.c_double)]),
         "sage_hip_precursor_purity": (C.c_int, [C.c_int, C.POINTER(SagePurityInput), C.POINTER(SagePurityOutput)]),
         "sage_hip_write_purity": (C.c_int, [C.c_char_p, C.c_uint64, c_u64_p, c_u32_p, C.POINTER(C.c_char_p), c_u8_p, C.POINTER(C.c_char_p),
                                             c_float_p, c_float_p, C.POINTER(SagePurityOutput), C.POINTER(C.c_char_p), C.c_uint32]),
@@ -474,6 +489,7 @@ EXPORTED_SYMBOLS = [
     "sage_hip_localise_resident", "sage_hip_ascore_from_counts", "sage_hip_last_localise_timing",
     "sage_hip_protein_lfq", "sage_hip_write_protein_lfq",
     "sage_hip_precursor_purity", "sage_hip_write_purity",
+    "sage_hip_tmt_rollup", "sage_hip_write_tmt_rollup",
 ]
 
 

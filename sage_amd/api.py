@@ -1301,6 +1301,56 @@ def protein_lfq(areas, protein_of_row, n_proteins: int, min_ratio_count: int = 1
     return r
 
 
+# ---- roll-up of TMT reporter intensities to proteins / peptides (sage_hip_tmt_rollup) -------------------------------------------
+TMT_NORMALISE = {"None": 0, "Total": 1}
+TMT_SUMMARY = {"Sum": 0, "Median": 1}
+
+
+@dataclass
+class TmtRollupResult:
+    """Outputs of sage_hip_tmt_rollup.  abundance (0.0 = not quantified), log_abundance (natural log, NaN = not
+    quantified) and n_cells: [n_groups, n_labels]; n_rows_used: [n_groups]; factor and column_sum: [n_labels].  n_long_groups: the
+    groups whose medians were selected over global memory; n_label_slabs: the slabs of 64 channels a wavefront walks per group."""
+    abundance: np.ndarray
+    log_abundance: np.ndarray
+    n_cells: np.ndarray
+    n_rows_used: np.ndarray
+    factor: np.ndarray
+    column_sum: np.ndarray
+    n_used_rows: int
+    n_long_groups: int
+    n_label_slabs: int
+    stage_ms: dict
+
+
+def tmt_rollup(intensity, group_of_row, n_groups: int, min_present: int = 1, normalise: str = "Total", summary: str = "Sum",
+               device: int = 0) -> TmtRollupResult:
+    """One plex of reporter intensities rolled up to groups (sage_hip_tmt_rollup).  intensity: [n_rows, n_labels] f32,
+    as TmtResult.intensity (a cell that is not a positive finite number is missing); group_of_row: [n_rows] ids below n_groups,
+    0xFFFFFFFF = the row is ignored; a row counts with at least max(min_present, 1) present cells.  normalise: "Total" | "None";
+    summary: "Sum" | "Median"."""
+    if normalise not in TMT_NORMALISE:
+        raise ValueError(f"normalise: unknown variant `{normalise}`, expected one of " + ", ".join(f"`{v}`" for v in TMT_NORMALISE))
+    if summary not in TMT_SUMMARY:
+        raise ValueError(f"summary: unknown variant `{summary}`, expected one of " + ", ".join(f"`{v}`" for v in TMT_SUMMARY))
+    x = np.ascontiguousarray(intensity, dtype=np.float32)
+    assert x.ndim == 2
+    n_rows, n_labels = x.shape
+    gor = np.ascontiguousarray(group_of_row, dtype=np.uint32).reshape(-1)
+    assert len(gor) == n_rows
+    n_groups = int(n_groups)
+    r = TmtRollupResult(np.zeros((n_groups, n_labels)), np.full((n_groups, n_labels), np.nan), np.zeros((n_groups, n_labels), np.uint32),
+                        np.zeros(n_groups, np.uint32), np.ones(n_labels), np.zeros(n_labels), 0, 0, 0, {})
+    cin = L.SageTmtRollupInput(n_rows, n_labels, n_groups, int(min_present), TMT_NORMALISE[normalise], TMT_SUMMARY[summary],
+                               L.as_ptr(x, C.c_float), L.as_ptr(gor, C.c_uint32))
+    cout = L.SageTmtRollupOutput(L.as_ptr(r.abundance, C.c_double), L.as_ptr(r.log_abundance, C.c_double), L.as_ptr(r.n_cells, C.c_uint32),
+                                 L.as_ptr(r.n_rows_used, C.c_uint32), L.as_ptr(r.factor, C.c_double), L.as_ptr(r.column_sum, C.c_double))
+    L.check(L.load().sage_hip_tmt_rollup(device, C.byref(cin), C.byref(cout)))
+    r.n_used_rows, r.n_long_groups, r.n_label_slabs = int(cout.n_used_rows), int(cout.n_long_groups), int(cout.n_label_slabs)
+    r.stage_ms = {"norm_ms": float(cout.norm_ms), "summary_ms": float(cout.summary_ms), "device_ms": float(cout.device_ms)}
+    return r
+
+
 # ---- precursor purity of reported PSMs from MS1 scans (sage_hip_precursor_purity) ------------------------------------------------
 NO_MS1 = 0xFFFFFFFFFFFFFFFF  # ms1_index of a query without an MS1 spectrum
 

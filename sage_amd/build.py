@@ -13,8 +13,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("SAGE_HIP_LIB") or os.path.join(HERE, "libsage_hip.so")  # (override: kernel experiments)
-SOURCES = ["kernels.hip", "process.hip", "index_build.hip", "rescore.hip", "rt_model.hip", "protein_groups.hip", "lfq.hip", "tmt.hip", "protein_lfq.hip", "purity.hip", "capi.hip", "capi_db.hip", "capi_psm.hip", "capi_host.cpp", "host_db.cpp", "groups.cpp", "writers.cpp", "mzml_reader.cpp", "mgf_reader.cpp"]
-HEADERS = ["capi_state.h", "localise_math.h", "maxlfq.h", "post_search.h", "purity.h", "core.h", "cover.h", "crlog.h", "crlog_tables.h", "detmath.h", "device_types.h", "hip_host.h", "host_db.hpp", os.path.join("..", "..", "include", "sage_hip.h")]
+SOURCES = ["kernels.hip", "process.hip", "index_build.hip", "rescore.hip", "rt_model.hip", "protein_groups.hip", "lfq.hip", "tmt.hip", "protein_lfq.hip", "purity.hip", "tmt_rollup.hip", "capi.hip", "capi_db.hip", "capi_psm.hip", "capi_host.cpp", "host_db.cpp", "groups.cpp", "writers.cpp", "mzml_reader.cpp", "mgf_reader.cpp"]
+HEADERS = ["capi_state.h", "localise_math.h", "maxlfq.h", "post_search.h", "purity.h", "tmt_rollup.h", "core.h", "cover.h", "crlog.h", "crlog_tables.h", "detmath.h", "device_types.h", "hip_host.h", "host_db.hpp", os.path.join("..", "..", "include", "sage_hip.h")]
 ARCH = "gfx950"
 
 

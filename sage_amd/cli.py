@@ -10,6 +10,7 @@ of Scorer::score is limited to the LDA rescoring, q-values and picked peptide / 
 device: rescore.hip), label-free MS1 quantification when `quant.lfq` is true (runner.rs:562-575, lfq.hip: `lfq.tsv`) and its
 MaxLFQ roll-up to proteins when `quant.protein_lfq` is true too (an addition, protein_lfq.hip: `protein_lfq.tsv`),
 isobaric-tag (TMT) reporter-ion quantification when `quant.tmt` is set (runner.rs:334-359, 398-410, tmt.hip: `tmt.tsv`),
+its roll-up to proteins when `quant.tmt_rollup` is true too (an addition, tmt_rollup.hip: `tmt_proteins.tsv`),
 IDPicker protein groups with the picked protein-group FDR when the configuration names `protein_grouping` or
 `protein_grouping_peptide_fdr` (runner.rs:539-549, protein_groups.hip + groups.cpp; see run()) and the optional percolator .pin file;
 parquet and cloud IO are out of scope.  The search itself runs on the GPU through libsage_hip.so; there is no CPU fallback.
@@ -26,7 +27,7 @@ from . import output
 from ._lib import FEATURE_DTYPE as L_FEATURE_DTYPE
 from .api import (LFQ_INTEGRATION, LFQ_SCORING, DatabaseParameters, DeviceDatabase, Isobaric, LfqSettings, RawBatch, Scorer,
                   ScorerParams, SpectrumBatch, SpectrumProcessor, TmtSettings, Tolerance, device_count, lfq, peptide_compositions,
-                  NO_MS1, assign_ms1, precursor_purity, predict_rt, protein_groups, protein_lfq, rescore, tmt)
+                  NO_MS1, assign_ms1, precursor_purity, predict_rt, protein_groups, protein_lfq, rescore, tmt, tmt_rollup)
 from .mgf import TOL_DA, is_mgf, read_mgf_native, read_spectra
 
 
@@ -100,6 +101,37 @@ def protein_lfq_settings(cfg: dict):
         raise SystemExit("quant.protein_lfq_settings.min_ratio_count must not be negative")
     if on and not (q.get("lfq") is not None and bool(q.get("lfq"))):
         raise SystemExit("`quant.protein_lfq: true` needs `quant.lfq: true`: the protein roll-up reads the precursor areas of lfq.tsv")
+    return on, st
+
+
+def tmt_rollup_settings(cfg: dict, n_files=None):
+    """quant.tmt_rollup / quant.tmt_rollup_settings — an addition over the reference, whose serde structs ignore the keys
+    (DESIGN.md 7i): (on, {"by", "summary", "normalise", "psm_q_value", "min_channels", "min_purity", "plex_of_file"}).  The roll-up
+    reads tmt.tsv's rows, so it needs quant.tmt; min_purity reads purity.sage.tsv's column, so it needs precursor_purity.  n_files:
+    the number of input files, when known (plex_of_file names the plex of each)."""
+    q = cfg.get("quant") or {}
+    on = bool(q.get("tmt_rollup")) if q.get("tmt_rollup") is not None else False
+    o = q.get("tmt_rollup_settings") or {}
+    pick = lambda k, d: d if o.get(k) is None else o[k]
+    st = {"by": pick("by", "protein"), "summary": pick("summary", "Sum"), "normalise": pick("normalise", "Total"),
+          "psm_q_value": float(pick("psm_q_value", 0.01)), "min_channels": int(pick("min_channels", 1)),
+          "min_purity": None if o.get("min_purity") is None else float(o["min_purity"]),
+          "plex_of_file": None if o.get("plex_of_file") is None else [int(x) for x in o["plex_of_file"]]}
+    for key, allowed in (("by", ("protein", "peptide")), ("summary", ("Sum", "Median")), ("normalise", ("Total", "None"))):
+        if st[key] not in allowed:
+            raise SystemExit(f"quant.tmt_rollup_settings.{key}: unknown variant `{st[key]}`, expected one of "
+                             + ", ".join(f"`{v}`" for v in allowed))
+    if st["min_channels"] < 0:
+        raise SystemExit("quant.tmt_rollup_settings.min_channels must not be negative")
+    if st["plex_of_file"] is not None and any(x < 0 for x in st["plex_of_file"]):
+        raise SystemExit("quant.tmt_rollup_settings.plex_of_file must not hold negative plex ids")
+    if on and q.get("tmt") is None:
+        raise SystemExit("`quant.tmt_rollup: true` needs `quant.tmt`: the roll-up reads the reporter intensities of tmt.tsv")
+    if on and st["min_purity"] is not None and not bool(cfg.get("precursor_purity", False)):
+        raise SystemExit("`quant.tmt_rollup_settings.min_purity` needs `precursor_purity: true`: the filter reads the purity of "
+                         "purity.sage.tsv")
+    if on and n_files is not None and st["plex_of_file"] is not None and len(st["plex_of_file"]) != n_files:
+        raise SystemExit(f"quant.tmt_rollup_settings.plex_of_file names {len(st['plex_of_file'])} files, the run has {n_files}")
     return on, st
 
 
@@ -471,6 +503,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     protein_lfq_on, protein_lfq_st = protein_lfq_settings(cfg)
     isobaric, tmt_st = tmt_settings(cfg, log)
     purity_on, purity_st = purity_settings(cfg)
+    tmt_rollup_on, tmt_rollup_st = tmt_rollup_settings(cfg, len(list(mzml_paths)))
     # runner.rs:391-410: S/N division at the quant level; at level 2 the reporter region is kept out of deisotoping
     sn_level = tmt_st.level if (isobaric is not None and tmt_st.sn) else None
     ms2_sn = sn_level if sn_level == 2 else None
@@ -762,6 +795,37 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
         purity_ms = (time.time() - t0) * 1000.0
         log(f"- precursor purity: {int(purity_ms):8d} ms ({len(o)} PSMs, {pur.stage_ms['device_ms']:.1f} ms on the device)")
         purity_summary = {"purity_rows": len(o), "purity_ms": purity_ms}
+    tmt_rollup_summary = {}
+    if tmt_rollup_on and tmt_parts and isobaric.headers():  # tmt.tsv's rows joined to the PSMs, filtered, rolled up plex by plex
+        t0 = time.time()
+        st = tmt_rollup_st
+        row_file = np.concatenate([np.full(len(p[1]), p[0], np.uint32) for p in tmt_parts])
+        row_ids = [s for p in tmt_parts for s in p[1]]
+        reporter = np.concatenate([p[3] for p in tmt_parts]).reshape(len(row_ids), -1)
+        purity_of = None
+        if st["min_purity"] is not None:  # (purity's block above: its results are in results.sage.tsv's order)
+            purity_of = np.full(len(flat), -1.0, np.float32)
+            purity_of[o] = pur.purity
+        spectrum_q = post.spectrum_q if post is not None else np.zeros(0, np.float32)
+        ids, names, peptide_of = output.tmt_rollup_assignment(host, flat, spec_ids, spectrum_q, row_file, row_ids, groups, purity_of,
+                                                              st["psm_q_value"], st["min_purity"], st["by"])
+        plex_of_file = st["plex_of_file"] if st["plex_of_file"] is not None else [0] * len(filenames)
+        row_plex = np.array(plex_of_file, np.int64)[row_file.astype(np.int64)]
+        plexes, rollup_device_ms = [], 0.0
+        for plex in sorted(set(row_plex.tolist())):
+            at = np.flatnonzero(row_plex == plex)
+            rolled = tmt_rollup(reporter[at], ids[at], len(names), st["min_channels"], st["normalise"], st["summary"], device=device)
+            rollup_device_ms += rolled.stage_ms["device_ms"]
+            plexes.append((plex, rolled, ids[at], peptide_of[at], reporter[at]))
+        table = output.tmt_rollup_table(plexes, st["min_channels"])
+        rp = os.path.join(output_directory, "tmt_proteins.tsv" if st["by"] == "protein" else "tmt_peptides.tsv")
+        n_written = output.write_tmt_rollup_native(rp, "proteins" if st["by"] == "protein" else "peptide", isobaric.headers(), names, table)
+        paths.append(rp)
+        tmt_rollup_ms = (time.time() - t0) * 1000.0
+        log(f"- TMT roll-up ({st['summary']}, {st['normalise']}): {int(tmt_rollup_ms):8d} ms ({n_written} rows of {len(names)} "
+            f"{'proteins' if st['by'] == 'protein' else 'peptides'} from {int((ids != output.NO_GROUP).sum())} of {len(ids)} spectra, "
+            f"{len(plexes)} plex{'es' if len(plexes) != 1 else ''})")
+        tmt_rollup_summary = {"tmt_rollup_rows": n_written, "tmt_rollup_ms": tmt_rollup_ms, "tmt_rollup_device_ms": rollup_device_ms}
     if write_pin:  # runner.rs:655-660
         pp = os.path.join(output_directory, "results.sage.pin")
         output.write_results_native(pp, "pin", host, flat, list(order), psm_ids, filenames, spec_ids, [rtp, post])
@@ -777,7 +841,7 @@ def run(cfg: dict, mzml_paths, output_directory: str, device: int = 0, log=print
     stage_totals["total_after_index_ms"] = (time.time() - t_run) * 1e3
     summary = {"version": "sage-hip 0.1 (search-and-score path of sage 0.15.0-beta.2)", "psms": len(flat),
                "spectra_searched": n_searched, "search_ms": search_ms, "stages": stage_totals, "output_paths": paths, **rescore_summary,
-               **lfq_summary, **tmt_summary, **isomer_summary, **localise_summary, **protein_lfq_summary, **purity_summary}
+               **lfq_summary, **tmt_summary, **isomer_summary, **localise_summary, **protein_lfq_summary, **purity_summary, **tmt_rollup_summary}
     with open(os.path.join(output_directory, "results.json"), "w") as fh:
         json.dump(dict(cfg, output_paths=paths, summary=summary), fh, indent=2, default=str)
     return summary

@@ -2,6 +2,7 @@
 // the mzML / MGF readers, the writers, the group graph, and the thin entry points of the post-search stages.
 #include "capi_state.h"
 #include "purity.h"
+#include "tmt_rollup.h"
 
 static thread_local std::string g_last_error;
 
@@ -225,6 +226,68 @@ int sage_hip_write_protein_lfq(const char* path, const char* const* protein_name
             return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_protein_lfq: protein id out of range or null name");
     std::string err;
     if (!write_protein_lfq(path, protein_names, rows, n_out, *result, filenames, n_files, err)) return fail(SAGE_HIP_ERR_INVALID, err);
+    return SAGE_HIP_OK;
+}
+
+// roll-up of TMT reporter intensities to groups (tmt_rollup.hip); every check comes before the device is touched
+int sage_hip_tmt_rollup(int device, const SageTmtRollupInput* in, SageTmtRollupOutput* out) {
+    const char* const who = "sage_hip_tmt_rollup";
+    if (!in || !out) return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": null argument");
+    out->n_used_rows = 0;
+    out->n_long_groups = out->n_label_slabs = 0;
+    out->norm_ms = out->summary_ms = out->device_ms = 0.0f;
+    if (in->normalise != SAGE_TMT_NORMALISE_NONE && in->normalise != SAGE_TMT_NORMALISE_TOTAL)
+        return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": unknown normalise " + std::to_string(in->normalise));
+    if (in->summary != SAGE_TMT_SUMMARY_SUM && in->summary != SAGE_TMT_SUMMARY_MEDIAN)
+        return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": unknown summary " + std::to_string(in->summary));
+    if (in->n_labels > tmtroll::MAX_LABELS) return fail(SAGE_HIP_ERR_UNSUPPORTED, std::string(who) + ": more than 65535 channels");
+    if (in->n_rows >= (1ull << 31)) return fail(SAGE_HIP_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 rows");
+    if (in->n_rows && in->n_labels == 0) return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": n_labels == 0");
+    if (in->n_rows && (!in->group_of_row || !in->intensity)) return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": null input array");
+    bool any = false;
+    for (uint64_t r = 0; r < in->n_rows; ++r) {
+        const uint32_t g = in->group_of_row[r];
+        if (g == tmtroll::NONE) continue;
+        if (g >= in->n_groups)
+            return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": group id " + std::to_string(g) + " of row " + std::to_string(r) +
+                                                  " is not below n_groups");
+        any = true;
+    }
+    if (in->n_groups == 0) return SAGE_HIP_OK;
+    if (!out->n_rows_used || (in->n_labels && (!out->abundance || !out->log_abundance || !out->n_cells || !out->factor || !out->column_sum)))
+        return fail(SAGE_HIP_ERR_INVALID, std::string(who) + ": null output array");
+    if (!any) {  // nothing to launch: no group is quantified
+        const uint64_t cells = (uint64_t)in->n_groups * in->n_labels;
+        for (uint32_t g = 0; g < in->n_groups; ++g) out->n_rows_used[g] = 0;
+        for (uint32_t k = 0; k < in->n_labels; ++k) {
+            out->factor[k] = 1.0;
+            out->column_sum[k] = 0.0;
+        }
+        for (uint64_t i = 0; i < cells; ++i) {
+            out->abundance[i] = 0.0;
+            out->log_abundance[i] = std::nan("");
+            out->n_cells[i] = 0;
+        }
+        return SAGE_HIP_OK;
+    }
+    if (const int rc = stage_guard(who, in->n_rows)) return rc;
+    std::string err;
+    const int rc = tmt_rollup_on_device(device, *in, *out, err);
+    return rc == SAGE_HIP_OK ? rc : fail(rc, err);
+}
+
+int sage_hip_write_tmt_rollup(const char* path, const char* first_header, const char* const* headers, uint32_t n_labels, uint64_t n_out,
+                              const char* const* names, const uint32_t* plex, const uint32_t* n_psms, const uint32_t* n_peptides,
+                              const double* abundance) {
+    if (!path || !first_header || (n_labels && !headers) || (n_out && (!names || !plex || !n_psms || !n_peptides || (n_labels && !abundance))))
+        return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_tmt_rollup: null argument");
+    for (uint32_t k = 0; k < n_labels; ++k)
+        if (!headers[k]) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_tmt_rollup: null header");
+    for (uint64_t r = 0; r < n_out; ++r)
+        if (!names[r]) return fail(SAGE_HIP_ERR_INVALID, "sage_hip_write_tmt_rollup: null name");
+    std::string err;
+    if (!write_tmt_rollup(path, first_header, headers, n_labels, n_out, names, plex, n_psms, n_peptides, abundance, err))
+        return fail(SAGE_HIP_ERR_INVALID, err);
     return SAGE_HIP_OK;
 }
 

@@ -303,6 +303,8 @@ int tmt_on_device(int device, const SageTmtInput& in, SageTmtOutput& out, std::s
 int protein_lfq_on_device(int device, const SageProteinLfqInput& in, SageProteinLfqOutput& out, std::string& err);
 // purity.hip: sage_hip_precursor_purity behind its argument checks (n_queries non-zero, every array present and in range)
 int purity_on_device(int device, const SagePurityInput& in, SagePurityOutput& out, std::string& err);
+// tmt_rollup.hip: sage_hip_tmt_rollup behind its argument checks (n_rows, n_labels and n_groups all non-zero, every id in range)
+int tmt_rollup_on_device(int device, const SageTmtRollupInput& in, SageTmtRollupOutput& out, std::string& err);
 // launch schedule of a batch (index_build.hip): order[k] = spectrum scored by block k, ascending neutral precursor mass
 size_t schedule_temp_bytes(uint32_t n);
 int schedule_on_device(uint32_t n, const float* d_precursor_mz, const uint8_t* d_charge, uint32_t min_charge, uint32_t* d_keys_a,

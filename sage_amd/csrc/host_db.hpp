@@ -114,6 +114,9 @@ bool write_tmt(const char* path, const char* const* headers, uint32_t n_labels, 
                uint32_t n_files, std::string& err);
 bool write_protein_lfq(const char* path, const char* const* protein_names, const uint32_t* rows, uint32_t n_out,
                        const SageProteinLfqOutput& result, const char* const* filenames, uint32_t n_files, std::string& err);
+bool write_tmt_rollup(const char* path, const char* first_header, const char* const* headers, uint32_t n_labels, uint64_t n_out,
+                      const char* const* names, const uint32_t* plex, const uint32_t* n_psms, const uint32_t* n_peptides,
+                      const double* abundance, std::string& err);
 bool write_purity(const char* path, uint64_t n_rows, const uint64_t* psm_id, const uint32_t* file_id, const char* const* spec_ids,
                   const uint8_t* charge, const char* const* ms1_ids, const float* isolation_lo, const float* isolation_hi,
                   const SagePurityOutput& result, const char* const* filenames, std::string& err);

@@ -390,6 +390,43 @@ bool write_protein_lfq(const char* path, const char* const* protein_names, const
     return ok;
 }
 
+// tmt_proteins.tsv / tmt_peptides.tsv: one row per entry in the order given; the abundances as ryu f64, 0.0 where not
+// quantified.
+bool write_tmt_rollup(const char* path, const char* first_header, const char* const* headers, uint32_t n_labels, uint64_t n_out,
+                      const char* const* names, const uint32_t* plex, const uint32_t* n_psms, const uint32_t* n_peptides,
+                      const double* abundance, std::string& err) {
+    FILE* fh = std::fopen(path, "wb");
+    if (!fh) {
+        err = std::string("cannot open ") + path;
+        return false;
+    }
+    std::string out;
+    field(out, first_header);
+    out += "\tplex\tn_psms\tn_peptides";
+    for (uint32_t k = 0; k < n_labels; ++k) {
+        out += '\t';
+        field(out, headers[k]);
+    }
+    out += '\n';
+    bool ok = true;
+    for (uint64_t r = 0; r < n_out && ok; ++r) {
+        str(out, names[r]);
+        itoa(out, plex[r]);
+        itoa(out, n_psms[r]);
+        itoa(out, n_peptides[r]);
+        for (uint32_t k = 0; k < n_labels; ++k) f64(out, abundance[r * n_labels + k]);
+        out.back() = '\n';
+        if (out.size() >= (1 << 20)) {
+            ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+            out.clear();
+        }
+    }
+    if (ok && !out.empty()) ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+    if (std::fclose(fh) != 0) ok = false;
+    if (!ok && err.empty()) err = std::string("write to ") + path + " failed";
+    return ok;
+}
+
 // purity.sage.tsv: one row per reported PSM in the order given; ms1_scannr is empty for a PSM without an MS1 scan.
 bool write_purity(const char* path, uint64_t n_rows, const uint64_t* psm_id, const uint32_t* file_id, const char* const* spec_ids,
                   const uint8_t* charge, const char* const* ms1_ids, const float* isolation_lo, const float* isolation_hi,

@@ -380,6 +380,105 @@ def write_protein_lfq_native(path: str, names: Sequence[str], result, filenames:
     return len(rows)
 
 
+TMT_ROLLUP_HEADERS = ["plex", "n_psms", "n_peptides"]
+NO_GROUP = 0xFFFFFFFF  # group_of_row of a tmt.tsv row that takes no part in the roll-up
+
+
+def tmt_rollup_assignment(db, features, spec_ids, spectrum_q, tmt_file_id, tmt_spec_ids, groups=None, purity=None,
+                          psm_q_value: float = 0.01, min_purity=None, by: str = "protein"):
+    """The input of api.tmt_rollup from a run's PSMs and its tmt.tsv rows: (group id of every tmt.tsv row, names by
+    id, peptide index of every row or -1).  features / spec_ids / spectrum_q / purity: the run's PSMs (purity: f32 per PSM or None);
+    tmt_file_id / tmt_spec_ids: tmt.tsv's rows in its own order (the scannr is the MS2's id: at another quant level the MS3's
+    precursor_ref).  A row takes the group of the first rank-1 target PSM of its (file, scannr), when that PSM has spectrum_q <=
+    psm_q_value (f32), a peptide of one protein only — with `groups` (a ProteinGroupResult over the PSMs) one protein group, by the
+    rule of protein_lfq_assignment — and, with min_purity, a purity >= min_purity (f32; -1.0 fails).  Any other row: NO_GROUP.
+    by: "protein" (the proteins / protein_groups string names the group) or "peptide" (the peptide's modified sequence).  Ids by
+    first appearance in tmt.tsv's order."""
+    assert by in ("protein", "peptide")
+    first = {}
+    fid, rank, label = np.asarray(features["file_id"]), np.asarray(features["rank"]), np.asarray(features["label"])
+    for i in range(len(fid)):
+        if int(rank[i]) == 1 and int(label[i]) == 1:
+            first.setdefault((int(fid[i]), spec_ids[i]), i)
+    ids, peptide, names, id_of = [], [], [], {}
+    for f, s in zip(np.asarray(tmt_file_id).tolist(), tmt_spec_ids):
+        i = first.get((int(f), s))
+        ids.append(NO_GROUP)
+        peptide.append(-1)
+        if i is None or not np.float32(spectrum_q[i]) <= np.float32(psm_q_value):
+            continue
+        if min_purity is not None and not np.float32(purity[i]) >= np.float32(min_purity):
+            continue
+        pep = int(features["peptide_idx"][i])
+        if groups is not None:
+            name, count = groups.protein_groups(i), int(groups.num_protein_groups[i])
+        else:
+            name, count = db.peptide_proteins(pep), db.peptide_info(pep)[0]
+        if count != 1:
+            continue
+        if by == "peptide":
+            name = db.peptide_string(pep)
+        if name not in id_of:
+            id_of[name] = len(names)
+            names.append(name)
+        ids[-1], peptide[-1] = id_of[name], pep
+    return np.array(ids, np.uint32), names, np.array(peptide, np.int64)
+
+
+def tmt_rollup_table(plexes, min_present: int = 1):
+    """The rows of tmt_proteins.tsv from the plexes' results: plexes = [(plex id, TmtRollupResult-like, group_of_row, peptide_of_row,
+    intensity)] over the rows of each plex.  One row per (group, plex) with at least one used row, ascending group id, then plex:
+    (group ids, plex ids, n_psms, n_peptides, abundance [rows, n_labels]).  n_peptides: the distinct peptides of the used rows (those
+    with at least max(min_present, 1) present cells)."""
+    out = []
+    for plex, result, group_of_row, peptide_of_row, intensity in plexes:
+        x = np.asarray(intensity, dtype=np.float32).reshape(len(group_of_row), -1).astype(np.float64)
+        n_present = ((x > 0) & (x < np.inf)).sum(axis=1)
+        peptides = {}
+        for g, pep, c in zip(np.asarray(group_of_row).tolist(), np.asarray(peptide_of_row).tolist(), n_present.tolist()):
+            if g != NO_GROUP and c >= max(int(min_present), 1):
+                peptides.setdefault(g, set()).add(pep)
+        for g in np.flatnonzero(np.asarray(result.n_rows_used) > 0).tolist():
+            assert len(peptides.get(g, ())) > 0
+            out.append((g, int(plex), int(result.n_rows_used[g]), len(peptides[g]), np.asarray(result.abundance[g], np.float64)))
+    out.sort(key=lambda r: (r[0], r[1]))
+    n_labels = len(out[0][4]) if out else 0
+    return (np.array([r[0] for r in out], np.uint32), np.array([r[1] for r in out], np.uint32), np.array([r[2] for r in out], np.uint32),
+            np.array([r[3] for r in out], np.uint32), np.array([r[4] for r in out], np.float64).reshape(len(out), n_labels))
+
+
+def tmt_rollup_rows(names: Sequence[str], table) -> List[List[str]]:
+    """tmt_proteins.tsv's rows for a tmt_rollup_table: the abundances as ryu f64, 0.0 = not quantified."""
+    gid, plex, n_psms, n_peptides, abundance = table
+    return [[names[int(g)], str(int(p)), str(int(a)), str(int(b))] + [ryu_f64(np.float64(x)) for x in row]
+            for g, p, a, b, row in zip(gid, plex, n_psms, n_peptides, abundance)]
+
+
+def write_tmt_rollup(path: str, first_header: str, headers: Sequence[str], rows: Sequence[List[str]]) -> None:
+    with open(path, "w", newline="") as fh:
+        fh.write(_record([first_header] + TMT_ROLLUP_HEADERS + list(headers)) + "\n")
+        for r in rows:
+            fh.write(_record(r) + "\n")
+
+
+def write_tmt_rollup_native(path: str, first_header: str, headers: Sequence[str], names: Sequence[str], table) -> int:
+    """tmt_proteins.tsv through the C++ writer (sage_hip_write_tmt_rollup): the bytes of tmt_rollup_rows + write_tmt_rollup.
+    Returns the number of rows written."""
+    import ctypes as C
+
+    from . import _lib as L
+    gid, plex, n_psms, n_peptides, abundance = table
+    plex, n_psms, n_peptides = (np.ascontiguousarray(a, dtype=np.uint32) for a in (plex, n_psms, n_peptides))
+    ab = np.ascontiguousarray(abundance, dtype=np.float64).reshape(-1)
+    n = len(gid)
+    assert len(plex) == n and len(n_psms) == n and len(n_peptides) == n and len(ab) == n * len(headers)
+    hs = (C.c_char_p * max(len(headers), 1))(*[h.encode() for h in headers])
+    ns = (C.c_char_p * max(n, 1))(*[names[int(g)].encode() for g in gid])
+    L.check(L.load().sage_hip_write_tmt_rollup(path.encode(), first_header.encode(), hs, len(headers), n, ns, L.as_ptr(plex, C.c_uint32),
+                                               L.as_ptr(n_psms, C.c_uint32), L.as_ptr(n_peptides, C.c_uint32), L.as_ptr(ab, C.c_double)))
+    return n
+
+
 PURITY_HEADERS = ["psm_id", "filename", "scannr", "charge", "ms1_scannr", "isolation_lo", "isolation_hi", "peaks_in_window",
                   "peaks_matched", "total_intensity", "precursor_intensity", "below_intensity", "purity"]
 
